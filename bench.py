@@ -9,8 +9,12 @@ all-gather of 16 B).  `--chain separate` issues the three entry points one by on
 on the device inside the step (omb_eval_argmax_sobol, what the maximiser runs).  Workload per GPU: ZDT1 (n_var=6) surrogate with n_train=512 and
 N = 2^20 unscrambled-Sobol candidates; rank g scores Sobol indices [g·N, (g+1)·N) (weak scaling).
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
         python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N  (multi-GPU)
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what the headline
+figure does not need: the oracle's CPU baseline, the reference's recorded CPU figures, the posterior's event-timed
+roofline, the stand-alone K-block roofline and the model-state install time (null in a plain run's line).
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (float64).
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts its own N ranks (one child
 process per GPU, MASTER_ADDR 127.0.0.1) before anything touches the GPU, and exits with their status.
 Prints ONE JSON line on rank 0.
@@ -146,6 +150,22 @@ def cpu_baseline(X, targets, ls, variances, Xc, acq_fn, label, seconds):
                       f"used (threadpoolctl; the job's CPU share)"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: all files of one run together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as ``path/<name>.npy`` in float64.  The arrays share DUMP_LIMIT_BYTES equally;
+    one larger than its share is written as a fixed sample of its flattened elements (numpy default_rng(0),
+    without replacement, in ascending index order), the same elements in every run."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays)) // 8
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.size > share:
+            a = a.ravel()[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def run_solve(args, cfg, world_size, rank):
     """README MyProblem (README.md:28-45): MultiSurrogateOptimiser + Tchebicheff, budget 100,
     n_init 20, sample_exponent 3, timed end to end with the fit / maximiser split."""
@@ -161,7 +181,7 @@ def run_solve(args, cfg, world_size, rank):
         def _evaluate(self, x, out, *a, **k):
             out["F"] = [100 * (x[0] ** 2 + x[1] ** 2), (x[0] - 1) ** 2 + x[1] ** 2]
 
-    budget = args.steps if args.steps != 50 else cfg["budget"]
+    budget = args.steps                   # main(): the config's budget of 100 when --steps is not given
     np.random.seed(0)
     opt = opti.MultiSurrogateOptimiser(MyProblem(), [0, 0], [700, 12], seed=1)
     split = {"fit": 0.0, "maximise": 0.0}
@@ -181,6 +201,9 @@ def run_solve(args, cfg, world_size, rank):
                     acquisition_func=sc.Tchebicheff([0, 0], [700, 12]))
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"Xsample": res.Xsample, "ysample": res.ysample,
+                                         "hypervolume_convergence": res.hypervolume_convergence})
     if rank == 0:
         print(json.dumps({
             "metric": "README MyProblem MultiSurrogateOptimiser.solve() BO iterations/sec (BASELINE config 1)",
@@ -193,7 +216,7 @@ def run_solve(args, cfg, world_size, rank):
             "split_s": {"gp_fit": split["fit"], "device_maximiser": split["maximise"],
                         "other": el - split["fit"] - split["maximise"]},
             "final_hv": float(res.hypervolume_convergence[-1]), "n_evaluations": int(len(res.ysample)),
-            "roofline": None, "cpu_baseline": reference_solve_c1(),
+            "roofline": None, "cpu_baseline": reference_solve_c1() if args.full else None, "full": args.full,
         }))
 
 
@@ -280,8 +303,10 @@ def run_thompson(args, cfg, world_size, rank, device, backend):
         elapsed = float(t.item())
     step_ms = elapsed / args.steps * 1e3
     fl = thompson_flops(n, N, B)
+    if rank == 0 and args.dump_outputs:      # rank 0's trust region: the draws and the indices selected from them
+        dump_outputs(args.dump_outputs, {"draws": Yd.cpu().numpy(), "selected": idx.cpu().numpy()})
     cpu = None
-    if rank == 0 and world_size == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world_size == 1 and not args.no_cpu_baseline:
         cpu = cpu_thompson(X, yagg, ls, var, Xc_host, B, args.cpu_seconds)
     if rank == 0:
         out = {
@@ -300,7 +325,7 @@ def run_thompson(args, cfg, world_size, rank, device, backend):
                          "kernel": "whole step (covariance GEMMs + blocked Cholesky + draws + select); "
                                    "algorithmic flops per step = n^2 N + n N (N+1) + N^3/3 + B N^2",
                          "ms_per_launch": step_ms},
-            "cpu_baseline": cpu, "jitter": jit[0],
+            "cpu_baseline": cpu, "jitter": jit[0], "full": args.full,
         }
         print(json.dumps(out))
     if world_size > 1:
@@ -434,8 +459,22 @@ def launch_check(world_size, rank, backend):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default 50; config 1: its budget of 100 BO iterations)")
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the oracle's "
+                         "CPU baseline (--cpu-seconds, --no-cpu-baseline), the reference's recorded CPU figures, the "
+                         "posterior's event-timed roofline inside the timed steps (--timing-stride, --stage-timing), "
+                         "the stand-alone K-block roofline (--no-kblock) and the model-state install time; a plain "
+                         "run reports them as null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy in float64 (rank 0's shard; at most 64 MB in all, a larger array as a fixed "
+                         "seeded sample).  fused and sobol chains: best (the {value, index} pair) and acq_values, the "
+                         "acquisition over the same candidates that the arg-max ran over, from one omb_eval call after "
+                         "the timed steps; separate chain: mu, var, acq, best; config 6: draws, selected; config 1: "
+                         "Xsample, ysample, hypervolume_convergence")
     ap.add_argument("--config", type=int, default=3, choices=sorted(CONFIGS), help="BASELINE.json config")
     ap.add_argument("--log2-cand", type=int, default=None, help="candidates per GPU = 2^this (default: config)")
     ap.add_argument("--mode", default="reference", choices=["reference", "textbook"])
@@ -475,6 +514,10 @@ def main():
                          "0: s01 = -0.028, reference-mode EHVI <= 0 everywhere (degenerate arg-max)")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
+    if args.steps is None:
+        args.steps = cfg.get("budget", 50)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))          # no launcher: this process starts the ranks
 
@@ -554,7 +597,9 @@ def main():
     acq = torch.empty(N, dtype=torch.float64, device=device)
     raised = torch.empty(N, dtype=torch.int32, device=device)
     pair = torch.empty(2, dtype=torch.float64, device=device)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    # --full, separate chain: the posterior launch of every timed step between two events
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+          for _ in range(args.steps if args.full and args.chain == "separate" else 0)]
     if acq_kind == "ehvi2d":
         s00, s01 = pareto.cache_stats(cache)
         pf_dev = torch.as_tensor(pareto.stripes_2d(pf), device=device)
@@ -616,20 +661,22 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        if i == 1 and args.chain != "separate":
+        if args.full and i == 1 and args.chain != "separate":
             # HIP events on the chain's stream: around the posterior (level 1) or every stage (2).  Switched on
             # after step 0 is queued: step 0 follows the synchronize on an idle GPU and is not a steady-state
             # launch, so the average covers steps 1, 1 + stride, ...
             ctx.debug_set("timing_stride", stride)
             ctx.timing(2 if args.stage_timing else 1)
-        best = step(i if i >= 1 else None)
+        best = step(i if args.full and i >= 1 else None)
     torch.cuda.synchronize()
     if world_size > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     stage_ms = None
     chains = args.steps
-    if args.chain != "separate" and args.steps > 1:
+    if not args.full:
+        pass                                  # a plain run: no events in the timed steps, nothing to read
+    elif args.chain != "separate" and args.steps > 1:
         stage_sum, chains = ctx.timing_read()
         ctx.timing(0)
         stage_ms = {k: v / chains for k, v in stage_sum.items() if args.stage_timing or k == "posterior"}
@@ -639,16 +686,29 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    if stage_ms is not None:
+    if not args.full:
+        post_ms = None
+    elif stage_ms is not None:
         post_ms = stage_ms["posterior"] if chains else float("nan")
     else:
         post_ms = float(np.mean([a.elapsed_time(b) for a, b in ev[1:]])) if args.steps > 1 else float("nan")
         chains = max(args.steps - 1, 0)
     best = best.cpu().numpy()
 
+    if rank == 0 and args.dump_outputs:
+        # what the last timed step left with its caller; before --full's state install replaces the model states
+        outs = {"best": best}
+        if args.chain == "separate":
+            outs.update(mu=mu.cpu().numpy(), var=var.cpu().numpy(), acq=acq.cpu().numpy())
+        else:
+            # the fused chains return the pair alone: the values their arg-max ran over, by the same plan
+            # (the sobol chain's device candidates are the points of Xc)
+            outs["acq_values"] = ctx.eval(Xc).cpu().numpy()
+        dump_outputs(args.dump_outputs, outs)
+
     # standalone K(X, X*) block: the HBM-bound kernel of the north star
     kblock = None
-    if not args.no_kblock:
+    if args.full and not args.no_kblock:
         K = torch.empty((n, N), dtype=torch.float64, device=device)
         ctx.kernel_block(0, Xc, out=K)
         torch.cuda.synchronize()
@@ -680,38 +740,42 @@ def main():
 
     # per-iteration model-state install, outside `value`: what a BO iteration does before its
     # batch — factorise Ky on the device and install (α, L⁻¹) for every objective (omb_gp_fit_state)
-    from optimobo_amd.gp import DeviceGPState
-    dev_states = [DeviceGPState(st.X, st.y, st.lengthscale, st.variance) for st in states]
-    for o, st in enumerate(dev_states):
-        ctx.set_gp_state(o, st)
-    torch.cuda.synchronize()
-    t_up = time.perf_counter()
-    reps_up = 5
-    for _ in range(reps_up):
+    state_ms = None
+    if args.full:
+        from optimobo_amd.gp import DeviceGPState
+        dev_states = [DeviceGPState(st.X, st.y, st.lengthscale, st.variance) for st in states]
         for o, st in enumerate(dev_states):
             ctx.set_gp_state(o, st)
-    torch.cuda.synchronize()
-    state_ms = (time.perf_counter() - t_up) / reps_up * 1e3
+        torch.cuda.synchronize()
+        t_up = time.perf_counter()
+        reps_up = 5
+        for _ in range(reps_up):
+            for o, st in enumerate(dev_states):
+                ctx.set_gp_state(o, st)
+        torch.cuda.synchronize()
+        state_ms = (time.perf_counter() - t_up) / reps_up * 1e3
 
-    flops = n_obj * posterior_flops_per_candidate(n, d) * N
-    achieved = flops / (post_ms * 1e-3) / 1e12
     step_ms = elapsed / args.steps * 1e3
-    # the posterior is one launch inside every step, so its event-timed average cannot exceed the step
-    check = bool(post_ms <= step_ms)
-    roofline = {"bound": "mfma", "achieved": achieved, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": achieved / FP64_MFMA_PEAK_TFLOPS, "traffic": load_traffic(n, N),
-                "kernel": f"posterior_kernel (omb_posterior, {n_obj} objective(s), n_train={n}, n_var={d})",
-                "ms_per_launch": post_ms,
-                "launches_timed": int(chains),
-                "pipe": load_pipe(args.config, "posterior_kernel"),
-                "timing_stride": stride,
-                "check": check,
-                "timing": "HIP events on the chain's stream around the posterior launch"
-                          + (f" of every {stride}th timed step from step 1" if args.chain != "separate"
-                             and stride > 1 else " of every timed step but the first")}
+    roofline, check = None, True
+    if args.full:
+        flops = n_obj * posterior_flops_per_candidate(n, d) * N
+        achieved = flops / (post_ms * 1e-3) / 1e12
+        # the posterior is one launch inside every step, so its event-timed average cannot exceed the step
+        check = bool(post_ms <= step_ms)
+        roofline = {"bound": "mfma", "achieved": achieved, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                    "frac": achieved / FP64_MFMA_PEAK_TFLOPS, "traffic": load_traffic(n, N),
+                    "kernel": f"posterior_kernel (omb_posterior, {n_obj} objective(s), n_train={n}, n_var={d})",
+                    "ms_per_launch": post_ms,
+                    "launches_timed": int(chains),
+                    "pipe": load_pipe(args.config, "posterior_kernel"),
+                    "timing_stride": stride,
+                    "check": check,
+                    "timing": "HIP events on the chain's stream around the posterior launch"
+                              + (f" of every {stride}th timed step from step 1" if args.chain != "separate"
+                                 and stride > 1 else " of every timed step but the first")}
 
     cpu = None
-    if rank == 0 and world_size == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world_size == 1 and not args.no_cpu_baseline:
         from oracle import acquisition as oacq
         if acq_kind == "ehvi2d":
             cpu = cpu_baseline(X, Y, ls, variances, Xc_host,
@@ -758,7 +822,8 @@ def main():
             "roofline": roofline,
             "roofline_kblock": kblock,
             "cpu_baseline": cpu,
-            "reference_cpu_per_candidate": reference_cpu(args.config),
+            "reference_cpu_per_candidate": reference_cpu(args.config) if args.full else None,
+            "full": args.full,
             "chain": args.chain,
             "stage_ms": stage_ms,
             "state_install_ms": state_ms,

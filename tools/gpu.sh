@@ -5,7 +5,8 @@
 #   bash tools/gpu.sh OUT STEP [STEP ...]
 #
 # OUT is a directory under gpurun_out/.  Each STEP is one quoted word list:
-#   "bench NAME ARGS..."   python bench.py ARGS > OUT/NAME.json (stderr OUT/NAME.err)
+#   "bench NAME ARGS..."   python bench.py ARGS > OUT/NAME.json (stderr OUT/NAME.err); pass --full among ARGS for the
+#                          CPU baseline, the rooflines and the state-install time
 #   "prof NAME ARGS..."    rocprofv3 --kernel-trace --stats of bench.py ARGS (OUT/NAME/…, line in OUT/NAME.json)
 #   "pmc NAME ARGS..."     PMC passes (tools/pmc_run.sh) of bench.py ARGS into OUT/NAME
 #   "test NAME PYTEST..."  python -m pytest -m gpu PYTEST > OUT/NAME.txt
@@ -32,7 +33,7 @@ for step in "$@"; do
     prof)
       name=$1; shift
       timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$OUT/$name" -o run \
-        --output-format csv -- python3 bench.py --no-cpu-baseline "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" ;;
+        --output-format csv -- python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" ;;
     pmc)
       name=$1; shift
       PMC_BENCH_ARGS="$*" bash tools/pmc_run.sh "$OUT/$name" ;;

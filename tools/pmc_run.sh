@@ -6,7 +6,7 @@ set -e
 OUT=${1:-gpurun_out/pmc}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-ARGS="bench.py --steps 3 --warmup 1 --no-cpu-baseline ${PMC_BENCH_ARGS:-}"
+ARGS="bench.py --full --steps 3 --warmup 1 --no-cpu-baseline ${PMC_BENCH_ARGS:-}"
 i=0
 # PMC_GROUPS: ';'-separated counter groups (one rocprofv3 pass each) in place of the default four;
 # PMC_GROUPS=pipe: the six passes behind profiles/r05_*_pmc_pipe.json (tools/pmc_pipe.py)
