@@ -118,7 +118,10 @@ const char* omb_last_error(const omb_ctx* ctx);
  * (default 0: the picks in parallel rounds to their fixed point; the same picks).
  * omb_debug_set(ctx, OMB_DEBUG_SYRK_GLDS, 0) builds the posterior covariance's SYRK with the register-staged two-slab
  * pipeline instead of the three-stage direct-to-LDS one (default 1 where n_train % 16 = 0 and N is even; the same
- * matrix bit for bit). */
+ * matrix bit for bit).
+ * omb_debug_set(ctx, OMB_DEBUG_BOXES_KD, 1) runs omb_ehvi_boxes_k / an omb_plan_ehvi_boxes_k plan with one wavefront
+ * per candidate (omb_ehvi_boxes' kernel, instantiated for every k) where 9·k·C ≤ 8192, instead of the
+ * candidate-blocked kernel (default 0; the same per-box products, another order of the sum: equal to rounding). */
 enum {
   OMB_DEBUG_SPIN_LIMIT = 1,
   OMB_DEBUG_COV_TABLE = 2,
@@ -128,7 +131,8 @@ enum {
   OMB_DEBUG_TIMING_STRIDE = 6,
   OMB_DEBUG_COV_FUSED = 8,
   OMB_DEBUG_SELECT_SEQ = 9,
-  OMB_DEBUG_SYRK_GLDS = 10
+  OMB_DEBUG_SYRK_GLDS = 10,
+  OMB_DEBUG_BOXES_KD = 11
 };
 int omb_debug_set(omb_ctx* ctx, int what, int64_t value);
 
@@ -191,6 +195,18 @@ int omb_ehvi_mc(omb_ctx* ctx, int k, const double* mu_dev, const double* var_dev
 int omb_ehvi_boxes(omb_ctx* ctx, int k, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
                    const double* coords_dev, int C, const uint16_t* boxes_dev, int B, double* out_dev);
 
+/* The same exact EHVI for any 2 ≤ k ≤ OMB_MAX_OBJ objectives and box lists of up to 2^24 boxes (the k ≥ 4
+ * decompositions of optimobo_amd.pareto.box_decomposition hold 10^3..10^5): arguments as omb_ehvi_boxes, boxes_dev
+ * 4-byte aligned.  One workgroup per 8 (4, 2, 1: as the LDS budget allows) candidates tabulates their Φ/φ at the
+ * k·C grid coordinates; each lane then reads a box's indices once from global memory and accumulates every
+ * candidate's product; fixed-order reduction, so a candidate's value does not depend on N or on its place in the
+ * batch.  Per box the product is omb_ehvi_boxes' term for term; the order of the sum over boxes differs.
+ *   OMB_EINVAL  k outside [2, OMB_MAX_OBJ], B < 1, null or misaligned pointers
+ *   OMB_EUNSUP  C < 2 or 3·k·C + 2·k + 4 > 8192 (one candidate's tables in 64 KiB of LDS), B > 2^24
+ * Indices are not checked here (the list is on the device): omb_plan_ehvi_boxes_k checks them. */
+int omb_ehvi_boxes_k(omb_ctx* ctx, int k, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
+                     const double* coords_dev, int C, const uint16_t* boxes_dev, int B, double* out_dev);
+
 /* Hypervolume-based PoI of EMO (emo.py:176-228): cells_dev (C, 2, 2) [upper, lower]. */
 int omb_hvpoi(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
               const double* cells_dev, int C, double* out_dev);
@@ -245,6 +261,10 @@ int omb_plan_ehvi3d_mc(omb_ctx* ctx, const double* cache_host, int M, const doub
 int omb_plan_ehvi_mc(omb_ctx* ctx, int k, const double* cache_host, int M, const double* r_host, double hv_pf);
 /* Exact EHVI (k = 2, 3): as omb_ehvi_boxes, coords_host (k, C), boxes_host (B, 2k). */
 int omb_plan_ehvi_boxes(omb_ctx* ctx, int k, const double* coords_host, int C, const uint16_t* boxes_host, int B);
+/* Exact EHVI (2 ≤ k ≤ OMB_MAX_OBJ): as omb_ehvi_boxes_k, coords_host (k, C), boxes_host (B, 2k).  The list is on
+ * the host here, so every box is checked: a grid index ≥ C, or a lower index ≥ its upper index, is OMB_EINVAL
+ * (and leaves no plan). */
+int omb_plan_ehvi_boxes_k(omb_ctx* ctx, int k, const double* coords_host, int C, const uint16_t* boxes_host, int B);
 /* EMO hypervolume-based PoI (k = 2): as omb_hvpoi, cells_host (C, 2, 2). */
 int omb_plan_hvpoi(omb_ctx* ctx, const double* cells_host, int C);
 /* expected_decomposition (k objectives): as omb_expdec, cache_host (M, k). */

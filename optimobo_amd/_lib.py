@@ -29,6 +29,7 @@ DEBUG_TIMING_STRIDE = 6
 DEBUG_COV_FUSED = 8
 DEBUG_SELECT_SEQ = 9
 DEBUG_SYRK_GLDS = 10
+DEBUG_BOXES_KD = 11
 MAX_OBJ, MAX_DIM, MAX_TRAIN, MAX_TRAIN_DENSE = 8, 256, 1024, 16384
 
 _p = ctypes.c_void_p
@@ -54,6 +55,7 @@ SIGNATURES = {
     "omb_ehvi3d_mc": (_i, [_p, _p, _p, _i64, _i64, _p, _i, _dp, _d, _p, _p]),
     "omb_ehvi_mc": (_i, [_p, _i, _p, _p, _i64, _i64, _p, _i, _dp, _d, _p, _p]),
     "omb_ehvi_boxes": (_i, [_p, _i, _p, _p, _i64, _i64, _p, _i, _p, _i, _p]),
+    "omb_ehvi_boxes_k": (_i, [_p, _i, _p, _p, _i64, _i64, _p, _i, _p, _i, _p]),
     "omb_hvpoi": (_i, [_p, _p, _p, _i64, _i64, _p, _i, _p]),
     "omb_expdec": (_i, [_p, _i, _p, _p, _i64, _i64, _p, _i, _i, _dp, _dp, _dp, _dp, _d, _p]),
     "omb_ei": (_i, [_p, _p, _p, _i64, _d, _d, _p]),
@@ -65,6 +67,7 @@ SIGNATURES = {
     "omb_plan_ehvi3d_mc": (_i, [_p, _p, _i, _dp, _d]),
     "omb_plan_ehvi_mc": (_i, [_p, _i, _p, _i, _dp, _d]),
     "omb_plan_ehvi_boxes": (_i, [_p, _i, _p, _i, _p, _i]),
+    "omb_plan_ehvi_boxes_k": (_i, [_p, _i, _p, _i, _p, _i]),
     "omb_plan_hvpoi": (_i, [_p, _p, _i]),
     "omb_plan_expdec": (_i, [_p, _i, _p, _i, _i, _dp, _dp, _dp, _dp, _d]),
     "omb_plan_ei": (_i, [_p, _d, _d]),

@@ -67,10 +67,11 @@ class AcquisitionEngine:
         sig = self._dev(np.asarray(sigma, np.float64).reshape(2, -1))
         return self.ctx.ehvi2d(mu, sig, pareto.stripes_2d(PF), np.asarray(r, np.float64), 1.0, 1.0, mode="sigma")
 
-    def ehvi_exact(self, Xc, max_point, PF):
-        """Exact EHVI (2 or 3 objectives) over the box decomposition — "textbook" mode."""
+    def ehvi_exact(self, Xc, max_point, PF, max_boxes=1 << 20):
+        """Exact EHVI (2 to 8 objectives) over the box decomposition — "textbook" mode.  ValueError when the
+        decomposition (k ≥ 4) needs more than max_boxes boxes."""
         mu, var = self.posterior(Xc)
-        coords, _, boxes = pareto.box_decomposition(PF, max_point)
+        coords, _, boxes = pareto.box_decomposition(PF, max_point, max_boxes=max_boxes)
         return self.ctx.ehvi_boxes(mu, var, coords, boxes)
 
     def ehvi3d(self, Xc, max_point, PF, cache):
@@ -112,8 +113,8 @@ class AcquisitionEngine:
         s00, s01 = pareto.cache_stats(np.asarray(cache, np.float64))
         self.ctx.plan_ehvi2d(pareto.stripes_2d(PF), np.asarray(max_point, np.float64), s00, s01, mode=mode)
 
-    def plan_ehvi_exact(self, max_point, PF):
-        coords, _, boxes = pareto.box_decomposition(PF, max_point)
+    def plan_ehvi_exact(self, max_point, PF, max_boxes=1 << 20):
+        coords, _, boxes = pareto.box_decomposition(PF, max_point, max_boxes=max_boxes)
         self.ctx.plan_ehvi_boxes(coords, boxes)
 
     def plan_ehvi3d(self, max_point, PF, cache):

@@ -4,18 +4,32 @@
 sample_exponent, acquisition_func)`` and ``MonoSurrogateOptimiser(...).solve(aggregation_func,
 budget, n_init_samples)`` keep the reference signatures and return ``Res``.  Extra keyword
 arguments select the device maximiser: ``mode`` ("reference" = bug-compatible acquisition
-values, "textbook" = exact EHVI), ``n_candidates`` (Sobol batch per iteration), ``refine_rounds``,
-``seed`` and ``device``.
+values, "textbook" = exact EHVI for every ``n_obj`` from 2 to 8), ``n_candidates`` (Sobol batch per
+iteration), ``refine_rounds``, ``seed`` and ``device``.
+
+The exact EHVI at ``n_obj`` ≥ 4 sums over a box decomposition of the non-dominated region whose size grows
+steeply with the front (pareto.box_decomposition).  ``MultiSurrogateOptimiser.exact_max_boxes`` bounds it: an
+iteration whose front needs more boxes, or a grid larger than the kernel holds, uses the reference's
+Monte-Carlo estimate instead and says so in one ``RuntimeWarning`` per optimiser.
 """
+import warnings
+
 import numpy as np
 
 from .. import pareto
 from ..refdirs import get_reference_directions
+from .._lib import OMB_EUNSUP, OMBError
 from ._base import BODriver
 
 
 class MultiSurrogateOptimiser(BODriver):
-    """One GP per objective; EHVI (2-D / 3-D) or expected decomposition as the acquisition."""
+    """One GP per objective; EHVI (2-D, or k-D for n_obj ≥ 3) or expected decomposition as the acquisition.
+
+    mode "textbook": the exact EHVI for 2 ≤ n_obj ≤ 8; at n_obj ≥ 4 while the front's box decomposition
+    stays within ``exact_max_boxes`` (else the Monte-Carlo estimate, with one RuntimeWarning).
+    """
+
+    exact_max_boxes = 1 << 17       # boxes of one iteration's exact EHVI at n_obj ≥ 4
 
     def _get_cached_samples(self, dimensions, sample_exponent):
         """optimisers.py:121-141 — scrambled Sobol mapped through the normal ppf."""
@@ -28,12 +42,32 @@ class MultiSurrogateOptimiser(BODriver):
         mc = function == "EHVI_3D" or self.n_obj >= 3          # optimisers.py:245-248: EHVI_3D for n_obj != 2
         if mc and self.mode == "textbook" and self.n_obj <= 3:
             eng.plan_ehvi_exact(max_point, pf)          # exact EHVI in place of the MC estimate (k = 2, 3)
+        elif mc and self.mode == "textbook":
+            self._plan_exact_kd(eng, max_point, pf, cache)   # exact for 4 ≤ k ≤ 8 while the box budget allows
         elif mc:
             eng.plan_ehvi3d(max_point, pf, cache)       # the reference's Monte-Carlo form, any k ≥ 3
         else:
             eng.plan_ehvi(max_point, pf, cache, mode=self.mode)
         x, v = self._maximise(models, None)
         return x, -v
+
+    def _plan_exact_kd(self, eng, max_point, pf, cache):
+        """Plans the exact EHVI at n_obj ≥ 4; when the box budget or the kernel's grid limit rules it out, the
+        Monte-Carlo plan stands in, after one RuntimeWarning per optimiser."""
+        try:
+            eng.plan_ehvi_exact(max_point, pf, max_boxes=self.exact_max_boxes)
+            return
+        except ValueError as e:                          # box_decomposition: over the box budget
+            reason = str(e)
+        except OMBError as e:                            # omb_plan_ehvi_boxes_k: grid or box count past the kernel's
+            if e.code != OMB_EUNSUP:
+                raise
+            reason = str(e)
+        if not getattr(self, "_warned_exact_fallback", False):
+            self._warned_exact_fallback = True
+            warnings.warn(f"exact EHVI unavailable at n_obj={self.n_obj} ({reason}); using the Monte-Carlo "
+                          "estimate of the reference", RuntimeWarning, stacklevel=3)
+        eng.plan_ehvi3d(max_point, pf, cache)
 
     def _get_proposed_scalarisation(self, function, models, min_val, scalar_func, ref_dir, cache):
         """optimisers.py:62-88 on the device: returns (x, −value, ref_dir)."""

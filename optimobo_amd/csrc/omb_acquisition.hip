@@ -331,6 +331,182 @@ hipError_t launch_ehvi_boxes(hipStream_t stream, int k, const double* mu, const 
   return hipGetLastError();
 }
 
+// The one-wavefront-per-candidate kernel above for any 2 ≤ k ≤ OMB_MAX_OBJ (omb_ehvi_boxes_k with
+// OMB_DEBUG_BOXES_KD = 1): the baseline the candidate-blocked kernel below is measured against.  9·k·C ≤ 8192.
+hipError_t launch_ehvi_boxes_wave(hipStream_t stream, int k, const double* mu, const double* var, int64_t ld,
+                                  int64_t N, const double* coords, int C, const uint16_t* boxes, int B, double* out) {
+  const size_t table = sizeof(double) * (size_t)k * C * (1 + 2 * kBoxWaves);
+  const size_t box_bytes = sizeof(uint16_t) * 2 * (size_t)k * B;
+  const bool in_lds = table + box_bytes <= 64 * 1024;
+  const size_t shm = table + (in_lds ? box_bytes : 0);
+  int64_t nb = (N + kBoxWaves - 1) / kBoxWaves;
+  const unsigned grid = (unsigned)(nb > 16384 ? 16384 : (nb < 1 ? 1 : nb));
+  dim3 g(grid), b(64 * kBoxWaves);
+  switch (k) {
+#define OMB_BW(KV)                                                                                                      \
+  case KV:                                                                                                              \
+    if (in_lds) hipLaunchKernelGGL((ehvi_boxes_kernel<KV, true>), g, b, shm, stream, mu, var, ld, N, coords, C, boxes, B, out); \
+    else hipLaunchKernelGGL((ehvi_boxes_kernel<KV, false>), g, b, shm, stream, mu, var, ld, N, coords, C, boxes, B, out);       \
+    break;
+    OMB_BW(2) OMB_BW(3) OMB_BW(4) OMB_BW(5) OMB_BW(6) OMB_BW(7) OMB_BW(8)
+#undef OMB_BW
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------ exact EHVI over boxes, k-D
+// The same sum for 2 ≤ k ≤ OMB_MAX_OBJ and box lists of 10^3..10^5 boxes (pareto.box_decomposition, k ≥ 4), where
+// one wavefront per candidate re-reads every box's indices and six table entries per objective from LDS.  Here
+// one workgroup owns CT candidates:
+//   1. all threads tabulate (Φ, φ) — interleaved, one 16-byte LDS read fetches both — at the K·C grid coordinates
+//      for each of the CT candidates;
+//   2. lane t takes boxes t, t + 256, …: the box's 2K uint16 indices come once, straight from global memory (K
+//      32-bit words per lane, neighbouring lanes neighbouring boxes), its 2K grid values once from LDS; then for
+//      each of the CT candidates only the two table entries per objective are read (the candidates' (μ, σ) stay
+//      in registers across the box loop: 4·K·CT VGPRs, which is what bounds CT at larger K);
+//   3. the CT partial sums are reduced in a fixed order: xor shuffles in the wave, then the four waves' sums from
+//      LDS in wave order.  No atomics: a candidate's value depends on B alone, not on N, its position in the
+//      batch, CT or the launch grid.
+// The per-box product is that of ehvi_boxes_kernel term for term; only the order of the sum over boxes differs.
+// LDS doubles: 2·CT·K·C (tables) + 2·CT·K (μ, σ) + K·C (grid) + 4·CT (reduction); CT = 8, 4, 2 or 1, the largest
+// within kd_max_ct(K) that fits 64 KiB (ehvi_boxes_kd_ct), so 3·K·C + 2·K + 4 ≤ 8192 bounds C (check_boxes_k).
+// Two workgroups per CU at least (≤ 256 VGPRs; no scratch at any K: the compiler's resource report).
+constexpr int kKdThreads = 256;
+
+struct alignas(16) Pair64 {
+  double x, y;
+};
+
+template <int K, int CT>
+__global__ __launch_bounds__(kKdThreads, 2) void ehvi_boxes_kd_kernel(const double* __restrict__ mu,
+                                                                   const double* __restrict__ var, int64_t ld,
+                                                                   int64_t N, const double* __restrict__ coords, int C,
+                                                                   const uint32_t* __restrict__ boxes, int B,
+                                                                   double* __restrict__ out) {
+  extern __shared__ Pair64 sm2[];
+  const int KC = K * C;
+  Pair64* tab = sm2;                                         // CT × K·C (Φ, φ)
+  Pair64* ms = tab + CT * KC;                                // CT × K (μ, σ)
+  double* grid = reinterpret_cast<double*>(ms + CT * K);     // K·C coordinates (−∞ → −1e300)
+  double* red = grid + KC;                                   // waves × CT
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int i = tid; i < KC; i += kKdThreads) grid[i] = fmax(coords[i], -1e300);
+  for (int64_t base = (int64_t)blockIdx.x * CT; base < N; base += (int64_t)gridDim.x * CT) {
+    __syncthreads();                                         // grid staged; the previous block's reads done
+    if (tid < CT * K) {
+      const int c = tid / K, j = tid - c * K;
+      const int64_t cc = base + c < N ? base + c : N - 1;   // the tail block computes its last candidate again
+      ms[tid] = Pair64{mu[j * ld + cc], sqrt(var[j * ld + cc])};
+    }
+    __syncthreads();
+    for (int i = tid; i < CT * KC; i += kKdThreads) {
+      const int c = i / KC, r = i - c * KC;
+      const Pair64 m = ms[c * K + r / C];
+      const double t = (grid[r] - m.x) / m.y;
+      tab[i] = Pair64{ndtr(t), npdf(t)};
+    }
+    __syncthreads();
+    double acc[CT], cm[CT][K], cs[CT][K];                 // (μ, σ): 4·K·CT VGPRs (kd_max_ct)
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+      acc[c] = 0.0;
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        cm[c][j] = ms[c * K + j].x;
+        cs[c][j] = ms[c * K + j].y;
+      }
+    }
+    for (int b = tid; b < B; b += kKdThreads) {
+      int il[K], ih[K];
+      double ul[K], u[K];
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        const uint32_t w = boxes[(size_t)b * K + j];         // lo | hi << 16
+        il[j] = j * C + (int)(w & 0xffffu);
+        ih[j] = j * C + (int)(w >> 16);
+        u[j] = grid[ih[j]];
+        ul[j] = u[j] - grid[il[j]];
+      }
+#pragma unroll
+      for (int c = 0; c < CT; ++c) {
+        const Pair64* t = tab + c * KC;
+        double prod = 1.0;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+          const Pair64 l = t[il[j]], h = t[ih[j]];
+          prod *= ul[j] * l.x + (u[j] - cm[c][j]) * (h.x - l.x) + cs[c][j] * (h.y - l.y);
+        }
+        acc[c] += prod;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+      double v = acc[c];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+      if (lane == 0) red[wave * CT + c] = v;
+    }
+    __syncthreads();
+    if (tid < CT && base + tid < N)
+      out[base + tid] = ((red[tid] + red[CT + tid]) + red[2 * CT + tid]) + red[3 * CT + tid];
+  }
+}
+
+static size_t ehvi_boxes_kd_lds(int k, int C, int ct) {
+  return sizeof(double) * ((size_t)2 * ct * k * C + (size_t)2 * ct * k + (size_t)k * C + (kKdThreads / 64) * (size_t)ct);
+}
+
+// candidates per workgroup: the largest of 8, 4, 2, 1 that keeps the kernel free of scratch (kd_max_ct: the
+// candidates' (μ, σ) and the loads in flight within 256 VGPRs — the compiler's resource report, gfx950) and whose
+// tables fit 64 KiB of LDS (0: not even one)
+constexpr int kd_max_ct(int k) { return k <= 3 ? 8 : (k <= 5 ? 4 : 2); }
+
+int ehvi_boxes_kd_ct(int k, int C) {
+  for (int ct = kd_max_ct(k); ct >= 1; ct >>= 1)
+    if (ehvi_boxes_kd_lds(k, C, ct) <= 64 * 1024) return ct;
+  return 0;
+}
+
+template <int K>
+static void launch_kd_k(int ct, dim3 g, size_t shm, hipStream_t stream, const double* mu, const double* var, int64_t ld,
+                        int64_t N, const double* coords, int C, const uint32_t* boxes, int B, double* out) {
+  const dim3 b(kKdThreads);
+  if constexpr (kd_max_ct(K) >= 8)
+    if (ct == 8) {
+      hipLaunchKernelGGL((ehvi_boxes_kd_kernel<K, 8>), g, b, shm, stream, mu, var, ld, N, coords, C, boxes, B, out);
+      return;
+    }
+  if constexpr (kd_max_ct(K) >= 4)
+    if (ct == 4) {
+      hipLaunchKernelGGL((ehvi_boxes_kd_kernel<K, 4>), g, b, shm, stream, mu, var, ld, N, coords, C, boxes, B, out);
+      return;
+    }
+  if (ct == 2) {
+      hipLaunchKernelGGL((ehvi_boxes_kd_kernel<K, 2>), g, b, shm, stream, mu, var, ld, N, coords, C, boxes, B, out);
+      return;
+    }
+  hipLaunchKernelGGL((ehvi_boxes_kd_kernel<K, 1>), g, b, shm, stream, mu, var, ld, N, coords, C, boxes, B, out);
+}
+
+hipError_t launch_ehvi_boxes_kd(hipStream_t stream, int k, const double* mu, const double* var, int64_t ld, int64_t N,
+                                const double* coords, int C, const uint16_t* boxes, int B, double* out) {
+  const int ct = ehvi_boxes_kd_ct(k, C);
+  if (ct == 0 || (reinterpret_cast<uintptr_t>(boxes) & 3)) return hipErrorInvalidValue;
+  const size_t shm = ehvi_boxes_kd_lds(k, C, ct);
+  const int64_t nb = (N + ct - 1) / ct;
+  const dim3 g((unsigned)(nb > 65536 ? 65536 : (nb < 1 ? 1 : nb)));
+  const uint32_t* bw = reinterpret_cast<const uint32_t*>(boxes);
+  switch (k) {
+#define OMB_KD(KV) \
+  case KV: launch_kd_k<KV>(ct, g, shm, stream, mu, var, ld, N, coords, C, bw, B, out); break;
+    OMB_KD(2) OMB_KD(3) OMB_KD(4) OMB_KD(5) OMB_KD(6) OMB_KD(7) OMB_KD(8)
+#undef OMB_KD
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------ HV-PoI
 // emo.py:192-228 with vol5 (:176-189):  s = sqrt(σ² + 1e-5);
 //   PoI = Σ_c Π_k [Φ((u_k−μ_k)/s_k) − Φ((l_k−μ_k)/s_k)],  I = Σ_c [u > μ]·Π_k(u_k − max(l_k, μ_k)).

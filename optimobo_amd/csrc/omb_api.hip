@@ -36,6 +36,7 @@ struct Plan {
   ScalParams sp{};
   const double* geo = nullptr;  // pf / cache / coords / cells on the device
   const uint16_t* boxes = nullptr;
+  bool boxes_kd = false;        // PLAN_EHVI_BOXES set by omb_plan_ehvi_boxes_k: the k-D kernel
 };
 
 struct omb_ctx {
@@ -99,6 +100,7 @@ struct omb_ctx {
   int chol_acq_rel = 0;          // OMB_DEBUG_CHOL_MODE (value & 4): release / acquire hand-offs
   int chol_single = 0;           // OMB_DEBUG_CHOL_MODE (value & 8): every trailing update its own task
   bool select_seq = false;       // OMB_DEBUG_SELECT_SEQ: the sequential greedy walk for B ≤ 64 too
+  bool boxes_kd_wave = false;    // OMB_DEBUG_BOXES_KD: omb_ehvi_boxes_k by one wavefront per candidate where that fits
 };
 
 namespace {
@@ -214,6 +216,14 @@ int plan_begin(omb_ctx* ctx, size_t bytes, void** host) {
 // Posterior of objectives 0..n_obj-1 (their state in args.gp, dense L⁻¹ in Ld[o]): the fused kernel
 // when every n_train fits it, else per objective and candidate chunk K block → V = L⁻¹K* (GEMM) →
 // column reduction.
+// omb_ehvi_boxes_k's kernel: candidate-blocked, or (OMB_DEBUG_BOXES_KD = 1, where its tables fit) the baseline
+hipError_t launch_boxes_k(omb_ctx* ctx, int k, const double* mu, const double* var, int64_t ld, int64_t N,
+                          const double* coords, int C, const uint16_t* boxes, int B, double* out) {
+  if (ctx->boxes_kd_wave && 9 * (int64_t)k * C <= kMaxLdsDoubles)
+    return launch_ehvi_boxes_wave(ctx->stream, k, mu, var, ld, N, coords, C, boxes, B, out);
+  return launch_ehvi_boxes_kd(ctx->stream, k, mu, var, ld, N, coords, C, boxes, B, out);
+}
+
 hipError_t posterior_any(omb_ctx* ctx, const GPArgs& args, const double* const* Ld, int n_obj, int max_R,
                          const double* Xc, int64_t N, double* mu, double* var) {
   // the fused kernel keeps the candidates' B fragments in registers: n_var ≤ 64 (kMaxFusedDP)
@@ -326,7 +336,8 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
         e = launch_ehvi_mc(ctx->stream, k, mu, var, N, N, pl.geo, pl.M, pl.r, pl.hv, vals, raised);
         break;
       case PLAN_EHVI_BOXES:
-        e = launch_ehvi_boxes(ctx->stream, k, mu, var, N, N, pl.geo, pl.C, pl.boxes, pl.B, vals);
+        e = pl.boxes_kd ? launch_boxes_k(ctx, k, mu, var, N, N, pl.geo, pl.C, pl.boxes, pl.B, vals)
+                        : launch_ehvi_boxes(ctx->stream, k, mu, var, N, N, pl.geo, pl.C, pl.boxes, pl.B, vals);
         break;
       case PLAN_HVPOI:
         e = launch_hvpoi(ctx->stream, mu, var, N, N, pl.geo, pl.C, vals);
@@ -468,6 +479,10 @@ int omb_debug_set(omb_ctx* ctx, int what, int64_t value) {
   }
   if (what == OMB_DEBUG_SELECT_SEQ) {
     ctx->select_seq = value != 0;
+    return OMB_OK;
+  }
+  if (what == OMB_DEBUG_BOXES_KD) {
+    ctx->boxes_kd_wave = value != 0;
     return OMB_OK;
   }
   if (what == OMB_DEBUG_CHOL_MODE) {
@@ -626,6 +641,20 @@ int omb_ehvi_boxes(omb_ctx* ctx, int k, const double* mu_dev, const double* var_
   return OMB_OK;
 }
 
+int omb_ehvi_boxes_k(omb_ctx* ctx, int k, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
+                     const double* coords_dev, int C, const uint16_t* boxes_dev, int B, double* out_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if ((rc = check_boxes_k(E(ctx), k, C, B))) return rc;
+  if ((rc = check_moments(E(ctx), mu_dev, var_dev, ld, N, k, out_dev))) return rc;
+  if (!coords_dev || !boxes_dev) return fail(ctx, OMB_EINVAL, "null grid/box list");
+  if (reinterpret_cast<uintptr_t>(boxes_dev) & 3) return fail(ctx, OMB_EINVAL, "box list not 4-byte aligned");
+  if (N == 0) return OMB_OK;
+  hipError_t e = launch_boxes_k(ctx, k, mu_dev, var_dev, ld, N, coords_dev, C, boxes_dev, B, out_dev);
+  if (e != hipSuccess) return hip_fail(ctx, e, "ehvi_boxes_k");
+  return OMB_OK;
+}
+
 int omb_hvpoi(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
               const double* cells_dev, int C, double* out_dev) {
   int rc = enter(ctx);
@@ -760,6 +789,32 @@ int omb_plan_ehvi_boxes(omb_ctx* ctx, int k, const double* coords_host, int C, c
   if ((rc = stage_to_geo(ctx, cbytes + bbytes))) return rc;
   Plan pl;
   pl.kind = PLAN_EHVI_BOXES;
+  pl.k = k;
+  pl.C = C;
+  pl.B = B;
+  pl.geo = static_cast<const double*>(ctx->geo);
+  pl.boxes = reinterpret_cast<const uint16_t*>(static_cast<const char*>(ctx->geo) + cbytes);
+  ctx->plan = pl;
+  return OMB_OK;
+}
+
+int omb_plan_ehvi_boxes_k(omb_ctx* ctx, int k, const double* coords_host, int C, const uint16_t* boxes_host, int B) {
+  void* h = nullptr;
+  int rc = enter(ctx);
+  if (rc) return rc;
+  ctx->plan = Plan();
+  if ((rc = check_boxes_k(E(ctx), k, C, B))) return rc;
+  if (!coords_host || !boxes_host) return fail(ctx, OMB_EINVAL, "null grid/box list");
+  if ((rc = check_box_list(E(ctx), k, C, boxes_host, B))) return rc;
+  const size_t cbytes = sizeof(double) * (size_t)k * C;     // a multiple of 8: the box list stays 4-byte aligned
+  const size_t bbytes = sizeof(uint16_t) * 2 * (size_t)k * B;
+  if ((rc = plan_begin(ctx, cbytes + bbytes, &h))) return rc;
+  memcpy(h, coords_host, cbytes);
+  memcpy(static_cast<char*>(h) + cbytes, boxes_host, bbytes);
+  if ((rc = stage_to_geo(ctx, cbytes + bbytes))) return rc;
+  Plan pl;
+  pl.kind = PLAN_EHVI_BOXES;
+  pl.boxes_kd = true;
   pl.k = k;
   pl.C = C;
   pl.B = B;

@@ -64,6 +64,29 @@ int check_boxes(std::string* err, int k, int C, int B) {
   return OMB_OK;
 }
 
+int check_boxes_k(std::string* err, int k, int C, int64_t B) {
+  if (k < 2 || k > OMB_MAX_OBJ)
+    return errf(err, OMB_EINVAL, "exact EHVI needs 2 <= k <= %d objectives (k=%d)", OMB_MAX_OBJ, k);
+  // one candidate's (Φ, φ) tables, its (μ, σ), the grid and the reduction words must fit the 64 KiB of dynamic LDS
+  const int64_t c_max = (kMaxLdsDoubles - 2 * k - 4) / (3 * (int64_t)k);
+  if (C < 2 || 3 * (int64_t)k * C + 2 * k + 4 > kMaxLdsDoubles)
+    return errf(err, OMB_EUNSUP, "grid size C=%d outside [2, %lld] for k=%d", C, (long long)c_max, k);
+  if (B < 1) return errf(err, OMB_EINVAL, "empty box list");
+  if (B > kMaxBoxesK) return errf(err, OMB_EUNSUP, "box count B=%lld above %d", (long long)B, kMaxBoxesK);
+  return OMB_OK;
+}
+
+int check_box_list(std::string* err, int k, int C, const uint16_t* boxes, int64_t B) {
+  for (int64_t b = 0; b < B; ++b)
+    for (int j = 0; j < k; ++j) {
+      const int lo = boxes[2 * k * b + 2 * j], hi = boxes[2 * k * b + 2 * j + 1];
+      if (hi >= C || lo >= hi)
+        return errf(err, OMB_EINVAL, "box %lld, objective %d: grid indices [%d, %d) not increasing inside [0, %d)",
+                    (long long)b, j, lo, hi, C);
+    }
+  return OMB_OK;
+}
+
 int check_ei(std::string* err, int kind, int k, double var_eps, double pof_eps) {
   const bool ok = (kind == OMB_EI_PLAIN && k == 1) || (kind == OMB_EI_PARETO && k == 2) ||
                   (kind == OMB_EI_CONSTRAINED && k >= 2 && k <= OMB_MAX_OBJ);

@@ -42,6 +42,11 @@ int check_moments(std::string* err, const void* mu, const void* var, int64_t ld,
 int check_ehvi2d(std::string* err, int P, const double* r, int mode);
 int check_ehvi_mc(std::string* err, int k, int M, const double* r);
 int check_boxes(std::string* err, int k, int C, int B);
+// omb_ehvi_boxes_k / omb_plan_ehvi_boxes_k: 2 ≤ k ≤ OMB_MAX_OBJ, 3·k·C + 2·k + 4 ≤ kMaxLdsDoubles, 1 ≤ B ≤ kMaxBoxesK.
+constexpr int kMaxBoxesK = 1 << 24;
+int check_boxes_k(std::string* err, int k, int C, int64_t B);
+// Every box of a host box list (B, 2k): lo index < hi index < C (an index past the grid would be read from LDS).
+int check_box_list(std::string* err, int k, int C, const uint16_t* boxes, int64_t B);
 int check_ei(std::string* err, int kind, int k, double var_eps, double pof_eps);
 int check_hvpoi(std::string* err, int C);
 // Validates an expected_decomposition request and fills its ScalParams.

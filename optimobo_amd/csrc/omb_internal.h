@@ -83,6 +83,14 @@ hipError_t launch_ehvi_mc(hipStream_t stream, int k, const double* mu, const dou
 hipError_t launch_ehvi_boxes(hipStream_t stream, int k, const double* mu, const double* var, int64_t ld, int64_t N,
                              const double* coords, int C, const uint16_t* boxes, int B, double* out);
 
+// Exact EHVI for 2 ≤ k ≤ OMB_MAX_OBJ (omb_ehvi_boxes_k): the candidate-blocked kernel (boxes 4-byte aligned;
+// check_boxes_k holds C to its LDS budget), and the one-wavefront-per-candidate kernel of launch_ehvi_boxes
+// instantiated for every k (9·k·C ≤ kMaxLdsDoubles), the baseline it is measured against.
+hipError_t launch_ehvi_boxes_kd(hipStream_t stream, int k, const double* mu, const double* var, int64_t ld, int64_t N,
+                                const double* coords, int C, const uint16_t* boxes, int B, double* out);
+hipError_t launch_ehvi_boxes_wave(hipStream_t stream, int k, const double* mu, const double* var, int64_t ld,
+                                  int64_t N, const double* coords, int C, const uint16_t* boxes, int B, double* out);
+
 hipError_t launch_hvpoi(hipStream_t stream, const double* mu, const double* var, int64_t ld, int64_t N,
                         const double* cells, int C, double* out);
 

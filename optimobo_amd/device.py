@@ -75,12 +75,14 @@ class AcqContext:
         launch / as two; ("chol_mode", 0/1/2 [+ 4]) factors auto / by per-step launches / in one persistent launch
         [with release-acquire hand-offs];
         ("timing_stride", s) records the timing events on every s-th chain only; ("select_seq", 0/1) picks the
-        Thompson selection's parallel rounds (default) / its sequential walk for B <= 64."""
+        Thompson selection's parallel rounds (default) / its sequential walk for B <= 64; ("boxes_kd", 0/1) runs
+        omb_ehvi_boxes_k candidate-blocked (default) / one wavefront per candidate where its tables fit."""
         code = {"spin_limit": _lib.DEBUG_SPIN_LIMIT, "cov_table": _lib.DEBUG_COV_TABLE,
                 "fused_chain": _lib.DEBUG_FUSED_CHAIN, "argmax_passes": _lib.DEBUG_ARGMAX_PASSES,
                 "chol_mode": _lib.DEBUG_CHOL_MODE, "timing_stride": _lib.DEBUG_TIMING_STRIDE,
                 "cov_fused": _lib.DEBUG_COV_FUSED,
-                "select_seq": _lib.DEBUG_SELECT_SEQ, "syrk_glds": _lib.DEBUG_SYRK_GLDS}[what]
+                "select_seq": _lib.DEBUG_SELECT_SEQ, "syrk_glds": _lib.DEBUG_SYRK_GLDS,
+                "boxes_kd": _lib.DEBUG_BOXES_KD}[what]
         self._check(self.lib.omb_debug_set(self._h, code, int(value)), "omb_debug_set")
 
     # ------------------------------------------------------------------ GP state
@@ -177,8 +179,9 @@ class AcqContext:
                                            _lib.darr(r), float(hv_pf), _ptr(out), _ptr(raised)), "omb_ehvi3d_mc")
         return out, raised
 
-    def ehvi_boxes(self, mu, var, coords, boxes, out=None):
-        """Exact EHVI over a box decomposition (optimobo_amd.pareto.box_decomposition)."""
+    def ehvi_boxes(self, mu, var, coords, boxes, out=None, kd=None):
+        """Exact EHVI over a box decomposition (optimobo_amd.pareto.box_decomposition).  kd: None picks the
+        entry by k; True / False force omb_ehvi_boxes_k (any 2 ≤ k ≤ 8) / omb_ehvi_boxes (k ≤ 3)."""
         k, N = mu.shape
         coords = _dev_f64(coords, self.device)
         if not isinstance(boxes, torch.Tensor):
@@ -187,9 +190,10 @@ class AcqContext:
             boxes = torch.as_tensor(b.view(np.int16), device=self.device)
         out = out if out is not None else torch.empty(N, dtype=torch.float64, device=self.device)
         self._stream()
-        self._check(self.lib.omb_ehvi_boxes(self._h, k, _ptr(mu), _ptr(var), mu.stride(0), N, _ptr(coords),
-                                            coords.shape[1], _ptr(boxes), boxes.shape[0], _ptr(out)),
-                    "omb_ehvi_boxes")
+        # k = 2, 3: one wavefront per candidate; k >= 4: the candidate-blocked k-D kernel (omb_ehvi_boxes_k)
+        fn = "omb_ehvi_boxes_k" if (k > 3 if kd is None else kd) else "omb_ehvi_boxes"
+        self._check(getattr(self.lib, fn)(self._h, k, _ptr(mu), _ptr(var), mu.stride(0), N, _ptr(coords),
+                                          coords.shape[1], _ptr(boxes), boxes.shape[0], _ptr(out)), fn)
         return out
 
     def hvpoi(self, mu, var, cells, out=None):
@@ -268,7 +272,8 @@ class AcqContext:
     def plan_ehvi_boxes(self, coords, boxes):
         c = np.ascontiguousarray(coords, dtype=np.float64)
         b = np.ascontiguousarray(boxes, dtype=np.uint16)
-        self._plan("omb_plan_ehvi_boxes", c.shape[0], _lib.host_ptr(c), c.shape[1], _lib.host_ptr(b), b.shape[0])
+        fn = "omb_plan_ehvi_boxes" if c.shape[0] <= 3 else "omb_plan_ehvi_boxes_k"
+        self._plan(fn, c.shape[0], _lib.host_ptr(c), c.shape[1], _lib.host_ptr(b), b.shape[0])
 
     def plan_hvpoi(self, cells):
         c = np.ascontiguousarray(cells, dtype=np.float64).reshape(-1, 2, 2)

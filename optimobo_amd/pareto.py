@@ -17,6 +17,8 @@ row 3), so they are host numpy; the per-candidate work they feed runs on the GPU
 import numpy as np
 from scipy.stats import norm, qmc
 
+MAX_OBJ = 8          # OMB_MAX_OBJ (include/optimobo_hip.h)
+
 
 def nondominated_mask(Y, block=2048):
     """mask[i] = no row of Y Pareto-dominates row i (minimisation)."""
@@ -90,19 +92,130 @@ def hypervolume(points, ref):
     return float(total)
 
 
-def box_decomposition(pf, ref):
-    """Disjoint boxes covering the part of (−∞, ref] the front does not dominate (k = 2, 3).
+class _BoxBudget(Exception):
+    pass
 
-    Input of omb_ehvi_boxes (the exact "textbook" EHVI): HVI(y) = Σ_b Π_j (hi_bj − max(y_j, lo_bj))⁺.
+
+def _front_ranks(F):
+    """Distinct non-dominated rows of an integer point set, in np.unique's (canonical) row order."""
+    F = np.unique(F, axis=0)
+    if len(F) < 2:
+        return F
+    le = np.all(F[:, None, :] <= F[None, :, :], axis=2)
+    np.fill_diagonal(le, False)                       # rows are distinct: a ≤ b with a ≠ b is dominance
+    return F[~le.any(axis=0)]
+
+
+def _boxes_3d_ranks(F, top, budget):
+    """box_decomposition's 3-D slab sweep on grid ranks: F (n, 3) distinct non-dominated rows."""
+    order = np.argsort(F[:, 2], kind="stable")
+    pts = F[order].tolist()
+    t0, t1, t2 = top
+    rows = []
+    stair = []                                        # 2-D front of the points below the slab, x ascending
+    i, n = 0, len(pts)
+    z = 0
+    while True:
+        z_next = pts[i][2] if i < n else t2
+        x_lo, y_hi = 0, t1
+        for x, y in stair:
+            rows.append((x_lo, x, 0, y_hi, z, z_next))
+            x_lo, y_hi = x, y
+        rows.append((x_lo, t0, 0, y_hi, z, z_next))
+        if len(rows) > budget:
+            raise _BoxBudget
+        if i >= n:
+            break
+        z = z_next
+        while i < n and pts[i][2] == z:               # the level's points enter the staircase
+            x, y = pts[i][0], pts[i][1]
+            i += 1
+            if any(a <= x and b <= y for a, b in stair):
+                continue
+            stair = [(a, b) for a, b in stair if not (x <= a and y <= b)]
+            stair.append((x, y))
+            stair.sort()
+    return np.asarray(rows, np.uint16)
+
+
+def _boxes_ranks(F, top, budget, memo):
+    """Boxes (B, 2d) of grid ranks covering what the front F (n, d) leaves non-dominated in [0, top].
+
+    Recursion over the last objective: between two consecutive levels of it the region is the (d−1)-D region
+    of the points at or below the lower level (their projected front), times the level interval.  F holds
+    distinct non-dominated rows, so the projected front changes at every level and no two slabs merge.
+    Sub-fronts recur across slabs; memo keeps their boxes.  budget: boxes this call may return.
+    """
+    d = F.shape[1]
+    key = (d, F.tobytes())
+    hit = memo.get(key)
+    if hit is not None:
+        if len(hit) > budget:
+            raise _BoxBudget
+        return hit
+    if d == 3:
+        out = _boxes_3d_ranks(F, top[:3], budget)
+        memo[key] = out
+        return out
+    if len(F) == 0:
+        return np.array([[0, t] for t in top[:d]], np.uint16).reshape(1, 2 * d)
+    levels = np.unique(F[:, -1])
+    parts = [np.array([[0, t] for t in top[:d - 1]] + [[0, levels[0]]], np.uint16).reshape(1, 2 * d)]
+    count = 1
+    front = np.zeros((0, d - 1), F.dtype)
+    for a, z in enumerate(levels):
+        front = _front_ranks(np.vstack((front, F[F[:, -1] == z, :-1])))
+        sub = _boxes_ranks(front, top, budget - count, memo)
+        count += len(sub)
+        if count > budget:
+            raise _BoxBudget
+        zz = np.empty((len(sub), 2), np.uint16)
+        zz[:, 0] = z
+        zz[:, 1] = levels[a + 1] if a + 1 < len(levels) else top[d - 1]
+        parts.append(np.hstack((sub, zz)))
+    out = np.concatenate(parts)
+    memo[key] = out
+    return out
+
+
+def _box_decomposition_kd(pf, ref, max_boxes):
+    k = ref.size
+    pts = pf[np.all(pf < ref, axis=1)] if pf.size else np.zeros((0, k))
+    pts = calc_pf(pts) if len(pts) > 1 else pts
+    grids = [np.concatenate(([-np.inf], np.unique(pts[:, j]), [ref[j]])) for j in range(k)]
+    C = max(len(g) for g in grids)
+    if C > 65535:
+        raise ValueError("box_decomposition: front too large for 16-bit grid indices")
+    top = [len(g) - 1 for g in grids]
+    ranks = np.stack([np.searchsorted(grids[j], pts[:, j]) for j in range(k)], axis=1).astype(np.int32)
+    ranks = _front_ranks(ranks.reshape(-1, k))
+    try:
+        boxes = _boxes_ranks(ranks, top, int(max_boxes), {})
+    except _BoxBudget:
+        raise ValueError(f"box_decomposition: a front of {len(ranks)} points in k={k} objectives needs more than "
+                         f"max_boxes={int(max_boxes)} boxes") from None
+    coords = np.stack([np.concatenate((g, np.full(C - len(g), g[-1]))) for g in grids])
+    return (np.ascontiguousarray(coords), np.array([len(g) for g in grids], np.int32), np.ascontiguousarray(boxes))
+
+
+def box_decomposition(pf, ref, max_boxes=1 << 20):
+    """Disjoint boxes covering the part of (−∞, ref] the front does not dominate (2 ≤ k ≤ 8).
+
+    Input of omb_ehvi_boxes[_k] (the exact "textbook" EHVI): HVI(y) = Σ_b Π_j (hi_bj − max(y_j, lo_bj))⁺.
     Returns (coords (k, C) f64 — per objective the sorted grid [−∞, front values…, ref_j] padded
     with ref_j —, ncoord (k,) int32, boxes (B, 2k) uint16 = [lo_idx_0, hi_idx_0, lo_idx_1, …]).
     3-D: one slab per distinct f3 level; inside a slab the 2-D staircase of the points below it.
+    k ≥ 4: the same sweep by recursion over the last objective (_boxes_ranks), on grid ranks, so the
+    boxes are exact; their number grows like P^(k/2)…P^(k−1), and a ValueError is raised
+    as soon as the count passes max_boxes (k ≥ 4 only; the k ≤ 3 lists are at most P² boxes).
     """
     pf = np.asarray(pf, np.float64)
     ref = np.asarray(ref, np.float64)
     k = ref.size
+    if 4 <= k <= MAX_OBJ:
+        return _box_decomposition_kd(pf.reshape(-1, k), ref, max_boxes)
     if k not in (2, 3):
-        raise NotImplementedError("box_decomposition: 2 or 3 objectives")
+        raise NotImplementedError(f"box_decomposition: 2 to {MAX_OBJ} objectives")
     pts = pf[np.all(pf < ref, axis=1)] if pf.size else np.zeros((0, k))
     pts = calc_pf(pts) if len(pts) > 1 else pts
     grids = [np.concatenate(([-np.inf], np.unique(pts[:, j]), [ref[j]])) for j in range(k)]

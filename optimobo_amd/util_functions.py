@@ -103,8 +103,9 @@ def EHVI_3D(X, models, max_point, PF, cache, mode="reference"):
     Any number of objectives k = len(models) ≥ 3, as the reference (which calls it for every n_obj != 2,
     optimisers.py:245-248): the per-sample volume is pygmo's k-D single-point hypervolume.
     mode "reference": the reference's Monte-Carlo form; batch → (values (N,), raised (N,) bool),
-    NaN where the reference would raise.  mode "textbook" (k = 3): the exact EHVI over a box
-    decomposition (no MC error, never raises); batch → (N,).
+    NaN where the reference would raise.  mode "textbook" (3 ≤ k ≤ 8): the exact EHVI over a box
+    decomposition (no MC error, never raises; ValueError when a k ≥ 4 front needs more than 2^20 boxes);
+    batch → (N,).
     """
     Xb, single = _batch(X)
     if mode == "textbook":
