@@ -295,6 +295,29 @@ int omb_eval_argmax(omb_ctx* ctx, const double* Xc_dev, int64_t N, int64_t offse
  * result_dev is the Sobol index (offset = start). */
 int omb_eval_argmax_sobol(omb_ctx* ctx, int64_t start, int64_t N, double* result_dev);
 
+/* ---------------------------------------------------------------------------------------
+ * Gradients with respect to a candidate (closed forms; no finite differences).  With k_i = k(x, X_i) and
+ * s_ij = (x_j − X_ij)/ℓ_j²:  ∂k_i/∂x_j = g_i·s_ij,  g_i = −(5/3)σ_f²(1 + √5 r_i)e^{−√5 r_i} (Matern-5/2; finite at
+ * r = 0) or −k_i (RBF);  ∂μ/∂x_j = Σ_i α_i g_i s_ij;  ∂σ²/∂x_j = −2 Σ_i w_i g_i s_ij,  w = L⁻ᵀ(L⁻¹k) (two products
+ * with the dense L⁻¹, no explicit K⁻¹).  σ² is not clamped, so the gradient is that of the unclamped expression.
+ * n_train ≤ OMB_MAX_TRAIN_DENSE, n_var ≤ OMB_MAX_DIM, both kernels, N ≥ 0 (N = 0 is OMB_OK and touches nothing).
+ * The workspace (K*, V, w: (n_obj + 2)·n_train doubles per candidate, in passes of at most 512 MiB) is grown on
+ * demand; a grow synchronises the stream first.  Fixed-order sums: a candidate's gradient does not depend on N or
+ * on its place in the batch.  Asynchronous.
+ * ------------------------------------------------------------------------------------- */
+/* μ, σ² as omb_posterior, plus ∂μ_o/∂x and ∂σ²_o/∂x at every candidate:
+ * dmu_dev, dvar_dev (n_obj, N, d) row-major.  mu_dev / var_dev (n_obj, N) may not be NULL. */
+int omb_posterior_grad(omb_ctx* ctx, int n_obj, const double* Xc_dev, int64_t N, double* mu_dev, double* var_dev,
+                       double* dmu_dev, double* dvar_dev);
+/* Plan's acquisition value and its gradient w.r.t. the candidate: vals_dev (N), grad_dev (N, d).
+ * vals_dev is bitwise omb_eval's.  Plans with a gradient: omb_plan_ei, omb_plan_ei_ext (every kind),
+ * omb_plan_ehvi2d (OMB_EHVI_REFERENCE: σA = σ²0·s00, σB = σ²0·s01, last stripe omitted — differentiated as it is;
+ * OMB_EHVI_TEXTBOOK), omb_plan_ehvi_boxes, omb_plan_ehvi_boxes_k.  The Monte-Carlo EHVI, expected-decomposition
+ * and HV-PoI plans (piecewise in the candidate) and EHVI-2D's OMB_EHVI_SIGMA mode return OMB_EUNSUP, write
+ * nothing and leave the plan set; no plan is OMB_ESTATE, as for omb_eval.  Where the value is NaN, every gradient
+ * entry of that candidate is NaN; no other candidate is affected. */
+int omb_eval_grad(omb_ctx* ctx, const double* Xc_dev, int64_t N, double* vals_dev, double* grad_dev);
+
 /* Device timing of the fused chain (HIP events on the context's stream), up to 4096 chains.
  * omb_timing(ctx, level): 0 off; 1 the posterior stage only (2 events per chain); 2 every
  * stage (5 events; each record costs a few µs of GPU time).  omb_timing_read synchronises

@@ -77,6 +77,9 @@ SIGNATURES = {
     "omb_eval": (_i, [_p, _p, _i64, _p]),
     "omb_eval_argmax": (_i, [_p, _p, _i64, _i64, _p]),
     "omb_eval_argmax_sobol": (_i, [_p, _i64, _i64, _p]),
+    # gradients with respect to a candidate
+    "omb_posterior_grad": (_i, [_p, _i, _p, _i64, _p, _p, _p, _p]),
+    "omb_eval_grad": (_i, [_p, _p, _i64, _p, _p]),
     "omb_timing": (_i, [_p, _i]),
     "omb_timing_read": (_i, [_p, _dp, ctypes.POINTER(_i64)]),
     # Thompson sampling (TuRBO)

@@ -184,6 +184,74 @@ class AcquisitionEngine:
         v1 = float(self.score(acq_fn, x1[None, :])[0])
         return (x1, v1) if v1 > v0 else (np.asarray(x0, np.float64), float(v0))
 
+    def has_gradient(self):
+        """True when the current plan is one the device differentiates (omb_eval_grad): the EI family, EHVI-2D
+        in reference or textbook mode, exact EHVI over boxes."""
+        return self.ctx.plan_has_gradient()
+
+    def value_and_grad(self, X):
+        """The plan's acquisition and its gradient at host points X (m, d) → numpy (v (m,), g (m, d)): one
+        omb_eval_grad.  v is bitwise ``score``'s value before its NaN → −inf mapping."""
+        v, g = self.ctx.eval_grad(self._dev(np.atleast_2d(X)))
+        return v.cpu().numpy().astype(np.float64), g.cpu().numpy().astype(np.float64)
+
+    def polish_batch(self, starts, lower, upper, maxiter=100):
+        """``polish`` for several starts at once on the analytic gradient: one bounded L-BFGS-B run per start
+        (scipy's routine in reverse communication, gp._LbfgsbRun), advanced in lockstep — every round is ONE
+        omb_eval_grad on the points of the runs still active, instead of a (2d+1)-point stencil per run and step.
+        ``starts``: points (m, d), or (x, v) pairs as ``_starts`` returns them (the value is taken again at x).
+        The objective of run s is −a(x)/|a(x0_s)|, ``polish``'s scaling.  Returns [(x, v)] in the order of the
+        starts; each keeps its x0 unless the polished point scores strictly higher."""
+        from .gp import _LbfgsbRun, _lockstep_ok
+        lower = np.asarray(lower, np.float64)
+        upper = np.asarray(upper, np.float64)
+        d = lower.size
+        if len(starts) and isinstance(starts[0], tuple):
+            starts = [s[0] for s in starts]
+        X0 = np.clip(np.asarray(starts, np.float64).reshape(-1, d), lower, upper)
+        m = X0.shape[0]
+        if m == 0:
+            return []
+        v0, g0 = self.value_and_grad(X0)
+        ok = np.isfinite(v0)
+        scale = np.where(ok & (v0 != 0.0), 1.0 / np.where(ok & (v0 != 0.0), np.abs(v0), 1.0), 1.0)
+
+        def fg(s, v, g):
+            if not np.isfinite(v):
+                return np.inf, np.zeros(d)
+            return -v * scale[s], -np.where(np.isfinite(g), g, 0.0) * scale[s]
+
+        X1 = X0.copy()
+        if _lockstep_ok():
+            runs = {s: _LbfgsbRun(X0[s], *fg(s, v0[s], g0[s]), 15000, int(maxiter), bounds=(lower, upper))
+                    for s in range(m) if ok[s]}
+            while runs:
+                ask = {}
+                for s in sorted(runs):
+                    x = runs[s].advance()
+                    if x is None:
+                        X1[s] = runs.pop(s).x
+                    else:
+                        ask[s] = x
+                if not ask:
+                    break
+                order = sorted(ask)
+                v, g = self.value_and_grad(np.stack([ask[s] for s in order]))
+                for i, s in enumerate(order):
+                    runs[s].supply(ask[s], *fg(s, v[i], g[i]))
+        else:   # another scipy layout: the same runs one after another
+            from scipy.optimize import minimize
+            for s in np.flatnonzero(ok):
+                def one(x, s=s):
+                    v, g = self.value_and_grad(np.clip(x, lower, upper)[None, :])
+                    return fg(s, v[0], g[0])
+                X1[s] = minimize(one, X0[s], jac=True, method="L-BFGS-B", bounds=list(zip(lower, upper)),
+                                 options={"maxiter": int(maxiter)}).x
+        X1 = np.clip(X1, lower, upper)
+        v1 = self.score(None, X1)
+        v0s = np.where(np.isnan(v0), -np.inf, v0)
+        return [(X1[s], float(v1[s])) if v1[s] > v0s[s] else (X0[s], float(v0s[s])) for s in range(m)]
+
     def _starts(self, acq_fn, lower, upper, n_candidates, seed, k, pool=64, sep=0.1):
         """Round 0 of a multi-start search: the ``n_candidates`` Sobol points scored on the device, every rank's
         ``pool`` best (value, global index) pairs gathered, then up to ``k`` starts picked greedily in
@@ -240,12 +308,24 @@ class AcquisitionEngine:
         round 0's best well-separated points (_starts) — round 0's arg-max alone stopped 1.2% short of
         scipy's DE on a 6-D expected decomposition (tests/test_gpu_config1.py); the first start is the
         single-start search's, so the result is never worse.
+        ``polish="analytic"`` finishes all starts together, after their refinement rounds, with ``polish_batch``
+        (L-BFGS-B on the device gradient, one omb_eval_grad per round for all starts); it needs the plan
+        (``acq_fn`` None) and a plan with a gradient (``has_gradient``), ValueError otherwise.  ``polish="auto"``
+        is "analytic" where that applies and the stencil polish (True) elsewhere.
         Returns (x_best (d,), value).
         """
         lower = np.asarray(lower, np.float64)
         upper = np.asarray(upper, np.float64)
         d = lower.size
         W, rank = world()
+        if isinstance(polish, str):
+            if polish not in ("analytic", "auto"):
+                raise ValueError(f"polish must be True, False, 'analytic' or 'auto', not {polish!r}")
+            can = acq_fn is None and self.has_gradient()
+            if polish == "analytic" and not can:
+                raise ValueError("polish='analytic' needs the planned acquisition (acq_fn=None) and a plan with a "
+                                 "device gradient (EI family, EHVI-2D reference / textbook, exact EHVI over boxes)")
+            polish = "analytic" if can else True
         k = (1 if d <= 2 else 4) if starts is None else int(starts)
         if k > 1:
             cands = self._starts(acq_fn, lower, upper, n_candidates, seed, k)
@@ -277,7 +357,7 @@ class AcquisitionEngine:
                 if g[1] >= 0 and g[0] > best_v:
                     best_x = self.ctx.sobol(int(g[1]), 1).cpu().numpy()[0]   # the winner, regenerated
                     best_v = float(g[0])
-            if polish:
+            if polish and polish != "analytic":
                 if W == 1:
                     best_x, best_v = self.polish(acq_fn, best_x, best_v, lower, upper)
                 else:
@@ -287,6 +367,15 @@ class AcquisitionEngine:
                     torch.distributed.broadcast_object_list(box, src=0)
                     best_x, best_v = np.asarray(box[0][0], np.float64), float(box[0][1])
             results.append((best_x, best_v))
+        if polish == "analytic":
+            if W == 1:
+                results = self.polish_batch(results, lower, upper)
+            else:
+                box = [None]
+                if rank == 0:
+                    box[0] = self.polish_batch(results, lower, upper)
+                torch.distributed.broadcast_object_list(box, src=0)
+                results = [(np.asarray(x, np.float64), float(v)) for x, v in box[0]]
         # the best start; ties to the earliest (the single-start search's when it ties)
         return max(results, key=lambda r: r[1])
 

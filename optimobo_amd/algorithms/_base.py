@@ -18,7 +18,7 @@ from ..result import Res
 
 class BODriver:
     def __init__(self, test_problem, ideal_point=None, max_point=None, mode="reference", n_candidates=1 << 14,
-                 refine_rounds=2, seed=None, device=None):
+                 refine_rounds=2, seed=None, device=None, polish=True, starts=None):
         self.test_problem = test_problem
         self.max_point = max_point
         self.ideal_point = ideal_point
@@ -37,6 +37,10 @@ class BODriver:
         # several ranks (torch.distributed initialised): one seed and one numpy state for all of them
         self.seed = agree_host_rng(seed)
         self.device = device
+        # AcquisitionEngine.maximise's finish (True: the stencil L-BFGS-B; "analytic" / "auto": the batched one on
+        # the device gradient) and its number of starts (None: maximise's default)
+        self.polish = polish
+        self.starts = starts
         self._iteration = 0
 
     def _objective_function(self, problem, x):
@@ -87,7 +91,7 @@ class BODriver:
         seed = (self.seed if self.seed is not None else np.random.randint(0, 2 ** 31 - 1)) + 7919 * self._iteration
         self._iteration += 1
         return eng.maximise(acq_fn, self.test_problem.xl, self.test_problem.xu, n_candidates=self.n_candidates,
-                            seed=seed, refine_rounds=self.refine_rounds)
+                            seed=seed, refine_rounds=self.refine_rounds, polish=self.polish, starts=self.starts)
 
     def _result(self, ysample, Xsample, hypervolume_convergence, n_init_samples):
         pf_approx = util_functions.calc_pf(ysample)

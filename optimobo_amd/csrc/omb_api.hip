@@ -82,6 +82,9 @@ struct omb_ctx {
   // dense posterior path (n_train > OMB_MAX_TRAIN): K* | V chunk workspace
   void* dws = nullptr;
   size_t dws_cap = 0;
+  // gradient chain (omb_posterior_grad / omb_eval_grad): ∂a/∂μ | ∂a/∂σ² | K* | V | w per objective
+  void* gws = nullptr;
+  size_t gws_cap = 0;
   // device fault word (pinned, mapped host memory): kernels mark it, enter() reports it
   int* fault_host = nullptr;
   int* fault_dev = nullptr;
@@ -416,6 +419,7 @@ int omb_destroy(omb_ctx* ctx) {
   if (ctx->ews) (void)hipFree(ctx->ews);
   if (ctx->fws) (void)hipFree(ctx->fws);
   if (ctx->dws) (void)hipFree(ctx->dws);
+  if (ctx->gws) (void)hipFree(ctx->gws);
   if (ctx->fault_host) (void)hipHostFree(ctx->fault_host);
   if (ctx->fit_host) (void)hipHostFree(ctx->fit_host);
   for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
@@ -929,6 +933,118 @@ int omb_eval_argmax(omb_ctx* ctx, const double* Xc_dev, int64_t N, int64_t offse
 int omb_eval_argmax_sobol(omb_ctx* ctx, int64_t start, int64_t N, double* result_dev) {
   if (ctx && !result_dev) return fail(ctx, OMB_EINVAL, "null result");
   return run_chain(ctx, nullptr, true, start, N, start, nullptr, result_dev);
+}
+
+// ---------------------------------------------------------------------------------------
+// Gradients with respect to a candidate (omb_grad.hip).  Per pass of up to grad_chunk candidates and per objective:
+// K* (omb_kernel_block's launch) → V = L⁻¹K* → w = L⁻ᵀV (two GEMMs with the dense L⁻¹); then one contraction launch
+// for all objectives.  aux: doubles in front of the chunk buffers (omb_eval_grad's ∂a/∂μ, ∂a/∂σ²).
+static int grad_ws(omb_ctx* ctx, const GPArgs& args, int n_obj, int64_t N, size_t aux, int64_t* Nc, int* n_max) {
+  *n_max = 0;
+  for (int o = 0; o < n_obj; ++o)
+    if (args.gp[o].n > *n_max) *n_max = args.gp[o].n;
+  *Nc = grad_chunk(n_obj, *n_max, N);
+  const size_t doubles = aux + (size_t)(n_obj + 2) * (size_t)*n_max * (size_t)*Nc;
+  return grow_dev(ctx, &ctx->gws, &ctx->gws_cap, doubles * sizeof(double), "gradient workspace");
+}
+
+static int grad_chain(omb_ctx* ctx, const GPArgs& args, int n_obj, int n_max, int64_t Nc, size_t aux,
+                      const double* Xc, int64_t N, double* dmu, double* dvar, const double* dadm, const double* dadv,
+                      const double* vals, double* grad) {
+  double* Kst = static_cast<double*>(ctx->gws) + aux;
+  double* V = Kst + (size_t)n_max * Nc;
+  double* W = V + (size_t)n_max * Nc;
+  GradArgs ga;
+  memset(&ga, 0, sizeof(ga));
+  ga.n_obj = n_obj;
+  ga.d = args.d;
+  ga.DP = args.DP;
+  ga.JW = 1;
+  while (ga.JW < args.d) ga.JW <<= 1;
+  for (int64_t c0 = 0; c0 < N; c0 += Nc) {
+    const int64_t nc = (N - c0) < Nc ? (N - c0) : Nc;
+    const double* X0 = Xc + c0 * args.d;
+    for (int o = 0; o < n_obj; ++o) {
+      const GPDev& g = args.gp[o];
+      double* Wo = W + (size_t)o * n_max * Nc;
+      hipError_t e = launch_kernel_block(ctx->stream, args, o, X0, nc, Kst);
+      if (e == hipSuccess) e = launch_gemm_ltri_nn(ctx->stream, g.n, nc, 1.0, ctx->obj[o].Ld, g.n, Kst, nc, 0.0, V, nc);
+      if (e == hipSuccess) e = launch_gemm_tn(ctx->stream, g.n, nc, g.n, 1.0, ctx->obj[o].Ld, g.n, V, nc, 0.0, Wo, nc);
+      if (e != hipSuccess) return hip_fail(ctx, e, "gradient chain (w = L^-T L^-1 k)");
+      ga.o[o] = GradObj{g.Xs, g.alpha, g.ls, Wo, g.variance, g.n, 0};
+    }
+    hipError_t e = launch_grad_contract(ctx->stream, ga, args.gp[0].kind, X0, nc, c0, N, dmu, dvar, dadm, dadv, vals,
+                                        grad);
+    if (e != hipSuccess) return hip_fail(ctx, e, "gradient contraction");
+  }
+  return OMB_OK;
+}
+
+int omb_posterior_grad(omb_ctx* ctx, int n_obj, const double* Xc_dev, int64_t N, double* mu_dev, double* var_dev,
+                       double* dmu_dev, double* dvar_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if ((rc = check_posterior_grad(E(ctx), n_obj, Xc_dev, N, mu_dev, var_dev, dmu_dev, dvar_dev))) return rc;
+  GPArgs args;
+  int max_R = 0;
+  if ((rc = gather_gp(ctx, n_obj, &args, &max_R))) return rc;
+  if (N == 0) return OMB_OK;
+  if ((N + 31) / 32 > 0x7fffffffLL) return fail(ctx, OMB_EUNSUP, "N=%lld too large", (long long)N);
+  int64_t Nc = 0;
+  int n_max = 0;
+  if ((rc = grad_ws(ctx, args, n_obj, N, 0, &Nc, &n_max))) return rc;
+  const double* Ld[OMB_MAX_OBJ];
+  gather_Ld(ctx, n_obj, Ld);
+  hipError_t e = posterior_any(ctx, args, Ld, n_obj, max_R, Xc_dev, N, mu_dev, var_dev);
+  if (e != hipSuccess) return hip_fail(ctx, e, "posterior");
+  return grad_chain(ctx, args, n_obj, n_max, Nc, 0, Xc_dev, N, dmu_dev, dvar_dev, nullptr, nullptr, nullptr, nullptr);
+}
+
+int omb_eval_grad(omb_ctx* ctx, const double* Xc_dev, int64_t N, double* vals_dev, double* grad_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if ((rc = check_eval_grad(E(ctx), Xc_dev, N, vals_dev, grad_dev))) return rc;
+  const Plan pl = ctx->plan;
+  if (pl.kind == PLAN_NONE) return fail(ctx, OMB_ESTATE, "no acquisition plan (call an omb_plan_* function)");
+  const char* unsup = nullptr;
+  if (pl.kind == PLAN_EHVI_MC) unsup = "Monte-Carlo EHVI";
+  if (pl.kind == PLAN_EXPDEC) unsup = "expected decomposition";
+  if (pl.kind == PLAN_HVPOI) unsup = "HV-PoI";
+  if (pl.kind == PLAN_EHVI2D && pl.mode == OMB_EHVI_SIGMA) unsup = "EHVI-2D in OMB_EHVI_SIGMA mode";
+  if (unsup) return fail(ctx, OMB_EUNSUP, "the %s plan has no analytic gradient", unsup);
+  GPArgs args;
+  int max_R = 0;
+  if ((rc = gather_gp(ctx, pl.k, &args, &max_R))) return rc;
+  if (N == 0) return OMB_OK;
+  if ((N + 31) / 32 > 0x7fffffffLL) return fail(ctx, OMB_EUNSUP, "N=%lld too large", (long long)N);
+  const int k = pl.k;
+  const size_t aux = 2 * (size_t)k * (size_t)N;
+  int64_t Nc = 0;
+  int n_max = 0;
+  if ((rc = grad_ws(ctx, args, k, N, aux, &Nc, &n_max))) return rc;
+  // the value: omb_eval's own chain, so vals_dev is bitwise omb_eval's; it leaves μ | σ² (k, N) in ctx->work
+  if ((rc = run_chain(ctx, Xc_dev, false, 0, N, 0, vals_dev, nullptr))) return rc;
+  const double* mu = static_cast<const double*>(ctx->work);
+  const double* var = mu + (size_t)k * (size_t)N;
+  double* dadm = static_cast<double*>(ctx->gws);
+  double* dadv = dadm + (size_t)k * (size_t)N;
+  hipError_t e;
+  switch (pl.kind) {
+    case PLAN_EHVI2D:
+      e = launch_ehvi2d_grad(ctx->stream, mu, var, N, N, pl.geo, pl.P, pl.r[0], pl.r[1], pl.s00, pl.s01, pl.mode, dadm,
+                             dadv);
+      break;
+    case PLAN_EHVI_BOXES:
+      e = launch_ehvi_boxes_grad(ctx->stream, k, mu, var, N, N, pl.geo, pl.C, pl.boxes, pl.B, dadm, dadv);
+      break;
+    case PLAN_EI:
+      e = launch_ei_grad(ctx->stream, pl.ei_kind, k, mu, var, N, N, pl.best, pl.var_eps, pl.pof_eps, dadm, dadv);
+      break;
+    default:
+      return fail(ctx, OMB_ESTATE, "corrupt plan");
+  }
+  if (e != hipSuccess) return hip_fail(ctx, e, "acquisition gradient");
+  return grad_chain(ctx, args, k, n_max, Nc, aux, Xc_dev, N, nullptr, nullptr, dadm, dadv, vals_dev, grad_dev);
 }
 
 int omb_timing(omb_ctx* ctx, int enable) {

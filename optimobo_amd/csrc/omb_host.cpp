@@ -101,6 +101,31 @@ int check_hvpoi(std::string* err, int C) {
   return OMB_OK;
 }
 
+int check_posterior_grad(std::string* err, int n_obj, const void* Xc, int64_t N, const void* mu, const void* var,
+                         const void* dmu, const void* dvar) {
+  if (n_obj < 1 || n_obj > OMB_MAX_OBJ) return errf(err, OMB_EINVAL, "n_obj=%d outside [1, %d]", n_obj, OMB_MAX_OBJ);
+  if (N < 0) return errf(err, OMB_EINVAL, "N=%lld < 0", (long long)N);
+  if (N > 0 && !Xc) return errf(err, OMB_EINVAL, "null candidate pointer");
+  if (N > 0 && (!mu || !var)) return errf(err, OMB_EINVAL, "null moment output (mu_dev / var_dev may not be NULL)");
+  if (N > 0 && (!dmu || !dvar)) return errf(err, OMB_EINVAL, "null gradient output");
+  return OMB_OK;
+}
+
+int check_eval_grad(std::string* err, const void* Xc, int64_t N, const void* vals, const void* grad) {
+  if (N < 0) return errf(err, OMB_EINVAL, "N=%lld < 0", (long long)N);
+  if (N > 0 && !Xc) return errf(err, OMB_EINVAL, "null candidate pointer");
+  if (N > 0 && (!vals || !grad)) return errf(err, OMB_EINVAL, "null output");
+  return OMB_OK;
+}
+
+int64_t grad_chunk(int n_obj, int n_train, int64_t N) {
+  if (N <= 0 || n_obj < 1 || n_obj > OMB_MAX_OBJ || n_train < 1 || n_train > OMB_MAX_TRAIN_DENSE) return 0;
+  const int64_t per = (int64_t)(n_obj + 2) * n_train * (int64_t)sizeof(double);
+  int64_t nc = ((int64_t)512 << 20) / per;
+  nc = nc < 64 ? 64 : (nc > (1 << 20) ? (1 << 20) : nc);
+  return nc < N ? nc : N;
+}
+
 int build_scal(std::string* err, int k, int M, int scal_id, const double* params_host, const double* weights_host,
                const double* ideal_host, const double* max_host, double agg_min, ScalParams* out) {
   if (k < 1 || k > OMB_MAX_OBJ) return errf(err, OMB_EINVAL, "k=%d outside [1, %d]", k, OMB_MAX_OBJ);

@@ -49,6 +49,14 @@ int check_boxes_k(std::string* err, int k, int C, int64_t B);
 int check_box_list(std::string* err, int k, int C, const uint16_t* boxes, int64_t B);
 int check_ei(std::string* err, int kind, int k, double var_eps, double pof_eps);
 int check_hvpoi(std::string* err, int C);
+// omb_posterior_grad: 1 ≤ n_obj ≤ OMB_MAX_OBJ, N ≥ 0, and with N > 0 no null candidate / output pointer.
+int check_posterior_grad(std::string* err, int n_obj, const void* Xc, int64_t N, const void* mu, const void* var,
+                         const void* dmu, const void* dvar);
+// omb_eval_grad: N ≥ 0, and with N > 0 no null candidate / output pointer.
+int check_eval_grad(std::string* err, const void* Xc, int64_t N, const void* vals, const void* grad);
+// Candidates per pass of the gradient chain: its workspace holds (n_obj + 2)·n_train doubles per candidate (K*, V
+// and one w per objective) and is kept to 512 MiB; at least 64, at most 2^20 and N (0 for an empty or out-of-range request).
+int64_t grad_chunk(int n_obj, int n_train, int64_t N);
 // Validates an expected_decomposition request and fills its ScalParams.
 int build_scal(std::string* err, int k, int M, int scal_id, const double* params_host, const double* weights_host,
                const double* ideal_host, const double* max_host, double agg_min, ScalParams* out);

@@ -262,6 +262,38 @@ hipError_t launch_gp_grad_partials_wide(hipStream_t stream, int kind, int DP, co
                                         const double* ls, double variance, const double* alpha, const double* Kinv,
                                         int64_t ldk, double* partials);
 
+// ---------------------------------------------------------------------------------------
+// Gradients with respect to a candidate (omb_grad.hip): omb_posterior_grad, omb_eval_grad.
+struct GradObj {
+  const double* Xs;     // GPDev::Xs (n_pad, DP)
+  const double* alpha;  // GPDev::alpha
+  const double* ls;     // GPDev::ls
+  const double* W;      // (n, nc) row-major: w = L⁻ᵀ(L⁻¹k) of the chunk's candidates
+  double variance;
+  int n;
+  int pad_;
+};
+struct GradArgs {
+  GradObj o[OMB_MAX_OBJ];
+  int n_obj, d, DP;
+  int JW;   // the power of two ≥ d (≤ 256): threads per training row in the contraction
+};
+// ∂μ_o/∂x, ∂σ²_o/∂x of the nc candidates Xc (nc, d) — candidates c0 .. c0 + nc − 1 of a batch of N — into dmu / dvar
+// (n_obj, N, d) when dmu is non-null, and, when grad is non-null, grad (N, d) = Σ_o dadm[o]·∂μ_o/∂x + dadv[o]·∂σ²_o/∂x
+// (dadm, dadv (n_obj, N); an all-NaN row where vals[c] is NaN).  One workgroup per candidate.
+hipError_t launch_grad_contract(hipStream_t stream, const GradArgs& ga, int kind, const double* Xc, int64_t nc,
+                                int64_t c0, int64_t N, double* dmu, double* dvar, const double* dadm,
+                                const double* dadv, const double* vals, double* grad);
+// ∂a/∂μ_o, ∂a/∂σ²_o of the acquisitions (rows o of dadm / dadv, pitch N), arguments as the value launchers'
+hipError_t launch_ei_grad(hipStream_t stream, int kind, int k, const double* mu, const double* var, int64_t ld,
+                          int64_t N, double best, double var_eps, double pof_eps, double* dadm, double* dadv);
+hipError_t launch_ehvi2d_grad(hipStream_t stream, const double* mu, const double* var, int64_t ld, int64_t N,
+                              const double* pf, int P, double r0, double r1, double s00, double s01, int mode,
+                              double* dadm, double* dadv);
+hipError_t launch_ehvi_boxes_grad(hipStream_t stream, int k, const double* mu, const double* var, int64_t ld,
+                                  int64_t N, const double* coords, int C, const uint16_t* boxes, int B, double* dadm,
+                                  double* dadv);
+
 // Packed-L^-1 size in doubles for R row tiles: Σ_{r<R} 4(r+1)·64 = 128·R·(R+1).
 inline int64_t packed_L_size(int R) { return 128ll * R * (R + 1); }
 // k-step pairs of the training-row A fragments [x/ℓ, ‖x/ℓ‖², 1]: ⌈⌈(DP+2)/4⌉/2⌉

@@ -40,6 +40,7 @@ class AcqContext:
         self._h = h
         self._gp_keep = {}     # device tensors referenced by the packed GP state
         self.gp_info = {}
+        self.plan_kind = None  # (omb_plan_* name, mode) of the plan last set through this object
 
     # ------------------------------------------------------------------ plumbing
     def _check(self, rc, what):
@@ -249,14 +250,26 @@ class AcqContext:
         return v.value, i.value
 
     # ------------------------------------------------------------------ fused chain (plans)
-    def _plan(self, fn, *args):
+    def _plan(self, fn, *args, mode=None):
         self._stream()
+        self.plan_kind = None          # a failed plan call leaves no plan
         self._check(getattr(self.lib, fn)(self._h, *args), fn)
+        self.plan_kind = (fn, mode)
+
+    # plans omb_eval_grad differentiates (include/optimobo_hip.h); EHVI-2D in "sigma" mode is not one
+    _GRAD_PLANS = ("omb_plan_ei", "omb_plan_ei_ext", "omb_plan_ehvi2d", "omb_plan_ehvi_boxes", "omb_plan_ehvi_boxes_k")
+
+    def plan_has_gradient(self):
+        """True when the plan last set through this context is one omb_eval_grad differentiates."""
+        if self.plan_kind is None:
+            return False
+        fn, mode = self.plan_kind
+        return fn in self._GRAD_PLANS and mode != "sigma"
 
     def plan_ehvi2d(self, pf_sorted, r, s00, s01, mode="reference"):
         pf = np.ascontiguousarray(pf_sorted, dtype=np.float64).reshape(-1, 2)
         m = {"reference": _lib.EHVI_REFERENCE, "textbook": _lib.EHVI_TEXTBOOK, "sigma": _lib.EHVI_SIGMA}[mode]
-        self._plan("omb_plan_ehvi2d", _lib.host_ptr(pf), pf.shape[0], _lib.darr(r), float(s00), float(s01), m)
+        self._plan("omb_plan_ehvi2d", _lib.host_ptr(pf), pf.shape[0], _lib.darr(r), float(s00), float(s01), m, mode=mode)
 
     def plan_ehvi_mc(self, cache, r, hv_pf):
         """EHVI_3D's Monte-Carlo form for k = cache.shape[1] objectives (cache (M, k), r (k,))."""
@@ -316,6 +329,34 @@ class AcqContext:
         self._stream()
         self._check(self.lib.omb_eval(self._h, _ptr(Xc), N, _ptr(out)), "omb_eval")
         return out
+
+    def posterior_grad(self, Xc, n_obj=None):
+        """omb_posterior_grad: (mu, var (n_obj, N), dmu, dvar (n_obj, N, d)) — the posterior moments of objectives
+        0..n_obj-1 at Xc (N, d), bitwise ``posterior``'s, and their gradients with respect to each candidate."""
+        Xc = _dev_f64(Xc, self.device)
+        self._check_width(Xc)
+        n_obj = n_obj if n_obj is not None else len(self.gp_info)
+        N, d = Xc.shape
+        mu = torch.empty((n_obj, N), dtype=torch.float64, device=self.device)
+        var = torch.empty_like(mu)
+        dmu = torch.empty((n_obj, N, d), dtype=torch.float64, device=self.device)
+        dvar = torch.empty_like(dmu)
+        self._stream()
+        self._check(self.lib.omb_posterior_grad(self._h, int(n_obj), _ptr(Xc), N, _ptr(mu), _ptr(var), _ptr(dmu),
+                                                _ptr(dvar)), "omb_posterior_grad")
+        return mu, var, dmu, dvar
+
+    def eval_grad(self, Xc):
+        """omb_eval_grad: (vals (N,), grad (N, d)) — the plan's acquisition at Xc (N, d), bitwise ``eval``'s, and
+        its gradient with respect to each candidate.  OMBError (OMB_EUNSUP) for a plan without a gradient."""
+        Xc = _dev_f64(Xc, self.device)
+        self._check_width(Xc)
+        N, d = Xc.shape
+        vals = torch.empty(N, dtype=torch.float64, device=self.device)
+        grad = torch.empty((N, d), dtype=torch.float64, device=self.device)
+        self._stream()
+        self._check(self.lib.omb_eval_grad(self._h, _ptr(Xc), N, _ptr(vals), _ptr(grad)), "omb_eval_grad")
+        return vals, grad
 
     def eval_argmax(self, Xc, offset=0, out=None):
         Xc = _dev_f64(Xc, self.device)

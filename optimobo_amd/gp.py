@@ -218,12 +218,15 @@ def _lockstep_ok():
 
 
 class _LbfgsbRun:
-    """scipy.optimize._lbfgsb_py._minimize_lbfgsb without bounds, driven from outside: ``advance``
+    """scipy.optimize._lbfgsb_py._minimize_lbfgsb, driven from outside: ``advance``
     runs the routine until it needs f and g at a point not evaluated last (returned) or it stops (None);
     ScalarFunction's rule (re-use the last evaluation when x is unchanged) and its evaluation count
-    (the initial point counts once) are kept."""
+    (the initial point counts once) are kept.  ``bounds`` = (lower, upper), both finite, makes it scipy's
+    bounded run (nbd = 2 for every variable; x0 — and so (f0, g0) — is the start clipped into the box, as
+    scipy clips it); None is the unbounded run."""
 
-    def __init__(self, x0, f0, g0, maxfun, maxiter, m=10, ftol=2.2204460492503131e-09, gtol=1e-5, maxls=20):
+    def __init__(self, x0, f0, g0, maxfun, maxiter, m=10, ftol=2.2204460492503131e-09, gtol=1e-5, maxls=20,
+                 bounds=None):
         self.setulb = _lbfgsb_routine()
         self.m, self.maxls = m, maxls
         self.pgtol, self.factr = gtol, ftol / np.finfo(float).eps
@@ -235,6 +238,11 @@ class _LbfgsbRun:
         self.nbd = np.zeros(n, np.int32)
         self.low = np.zeros(n, np.float64)
         self.up = np.zeros(n, np.float64)
+        if bounds is not None:
+            self.low[:] = np.asarray(bounds[0], np.float64)
+            self.up[:] = np.asarray(bounds[1], np.float64)
+            self.nbd[:] = 2
+            self.x = np.clip(self.x, self.low, self.up)
         self.wa = np.zeros(2 * m * n + 5 * n + 11 * m * m + 8 * m, np.float64)
         self.iwa = np.zeros(3 * n, dtype=np.int32)
         self.task = np.zeros(2, dtype=np.int32)
