@@ -121,7 +121,13 @@ const char* omb_last_error(const omb_ctx* ctx);
  * matrix bit for bit).
  * omb_debug_set(ctx, OMB_DEBUG_BOXES_KD, 1) runs omb_ehvi_boxes_k / an omb_plan_ehvi_boxes_k plan with one wavefront
  * per candidate (omb_ehvi_boxes' kernel, instantiated for every k) where 9·k·C ≤ 8192, instead of the
- * candidate-blocked kernel (default 0; the same per-box products, another order of the sum: equal to rounding). */
+ * candidate-blocked kernel (default 0; the same per-box products, another order of the sum: equal to rounding).
+ * omb_debug_set(ctx, OMB_DEBUG_POSTERIOR_ALL_VAR, 1) makes the fused chain (omb_eval, omb_eval_argmax[_sobol]) compute
+ * σ² of every objective of the plan.  By default (0) the chain's posterior computes σ² only of the objectives whose
+ * variance the planned acquisition loads — objective 0 alone for reference-mode EHVI-2D, Monte-Carlo EHVI, expected
+ * decomposition and the plain / Pareto EI, whose reference uses σ²₀ for every objective; all of them for the other
+ * plans — and μ of the rest without the triangular product V = L⁻¹K*.  Values and arg-max pairs are bit-identical
+ * either way; omb_posterior and omb_eval_grad always compute every σ². */
 enum {
   OMB_DEBUG_SPIN_LIMIT = 1,
   OMB_DEBUG_COV_TABLE = 2,
@@ -132,7 +138,8 @@ enum {
   OMB_DEBUG_COV_FUSED = 8,
   OMB_DEBUG_SELECT_SEQ = 9,
   OMB_DEBUG_SYRK_GLDS = 10,
-  OMB_DEBUG_BOXES_KD = 11
+  OMB_DEBUG_BOXES_KD = 11,
+  OMB_DEBUG_POSTERIOR_ALL_VAR = 12
 };
 int omb_debug_set(omb_ctx* ctx, int what, int64_t value);
 

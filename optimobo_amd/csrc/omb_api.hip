@@ -29,6 +29,7 @@ enum PlanKind { PLAN_NONE = 0, PLAN_EHVI2D, PLAN_EHVI_MC, PLAN_EHVI_BOXES, PLAN_
 struct Plan {
   int kind = PLAN_NONE;
   int k = 0;                    // objectives the acquisition reads (posterior of 0..k-1)
+  unsigned var_mask = 0;        // bit o: the plan's kernel loads σ² of objective o (the others' is never computed)
   int P = 0, M = 0, C = 0, B = 0, mode = 0;
   double r[OMB_MAX_OBJ] = {};
   double s00 = 0, s01 = 0, hv = 0, best = 0, var_eps = 0, pof_eps = 0;
@@ -104,6 +105,7 @@ struct omb_ctx {
   int chol_single = 0;           // OMB_DEBUG_CHOL_MODE (value & 8): every trailing update its own task
   bool select_seq = false;       // OMB_DEBUG_SELECT_SEQ: the sequential greedy walk for B ≤ 64 too
   bool boxes_kd_wave = false;    // OMB_DEBUG_BOXES_KD: omb_ehvi_boxes_k by one wavefront per candidate where that fits
+  bool posterior_all_var = false;  // OMB_DEBUG_POSTERIOR_ALL_VAR: the chain computes σ² of every objective
 };
 
 namespace {
@@ -232,6 +234,7 @@ hipError_t posterior_any(omb_ctx* ctx, const GPArgs& args, const double* const* 
   // the fused kernel keeps the candidates' B fragments in registers: n_var ≤ 64 (kMaxFusedDP)
   if (16 * max_R <= OMB_MAX_TRAIN && args.DP <= kMaxFusedDP)
     return launch_posterior(ctx->stream, args, n_obj, max_R, Xc, N, mu, var);
+  // the dense path ignores args.var_skip: it computes σ² of every objective
   for (int o = 0; o < n_obj; ++o) {
     const int64_t n = args.gp[o].n;
     int64_t Nc = (int64_t)(((size_t)256 << 20) / (16 * (size_t)n));   // K* and V chunks of 128 MiB each
@@ -258,9 +261,14 @@ void gather_Ld(omb_ctx* ctx, int n_obj, const double** Ld) {
   for (int o = 0; o < n_obj; ++o) Ld[o] = ctx->obj[o].Ld;
 }
 
-// The fused chain: [Sobol →] posterior(0..k-1) → planned acquisition → [arg-max].
+// bits 0..k-1
+unsigned all_objectives(int k) { return k >= 32 ? ~0u : (1u << k) - 1u; }
+
+// The fused chain: [Sobol →] posterior(0..k-1) → planned acquisition → [arg-max].  The posterior computes σ² of the
+// objectives in the plan's var_mask only (the others' slots of the workspace keep whatever they held); all_var (the
+// gradient chain, which reads every σ² afterwards, and OMB_DEBUG_POSTERIOR_ALL_VAR) computes all of them.
 int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t N, int64_t offset, double* vals_out,
-              double* result_dev) {
+              double* result_dev, bool all_var = false) {
   int rc = enter(ctx);
   if (rc) return rc;
   const Plan& pl = ctx->plan;
@@ -269,6 +277,7 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
   GPArgs args;
   int max_R = 0;
   if ((rc = gather_gp(ctx, pl.k, &args, &max_R))) return rc;
+  if (!all_var && !ctx->posterior_all_var) args.var_skip = all_objectives(pl.k) & ~pl.var_mask;
   if (sobol) {
     if (ctx->sob_d == 0) return fail(ctx, OMB_ESTATE, "no Sobol state (call omb_set_sobol)");
     if (ctx->sob_d != args.d) return fail(ctx, OMB_EINVAL, "Sobol dimension %d != n_var %d", ctx->sob_d, args.d);
@@ -487,6 +496,10 @@ int omb_debug_set(omb_ctx* ctx, int what, int64_t value) {
   }
   if (what == OMB_DEBUG_BOXES_KD) {
     ctx->boxes_kd_wave = value != 0;
+    return OMB_OK;
+  }
+  if (what == OMB_DEBUG_POSTERIOR_ALL_VAR) {
+    ctx->posterior_all_var = value != 0;
     return OMB_OK;
   }
   if (what == OMB_DEBUG_CHOL_MODE) {
@@ -741,6 +754,8 @@ int omb_plan_ehvi2d(omb_ctx* ctx, const double* pf_sorted_host, int P, const dou
   Plan pl;
   pl.kind = PLAN_EHVI2D;
   pl.k = 2;
+  // ehvi2d_kernel / ehvi2d_argmax_kernel: reference mode passes 0 for σ²₁ (σ²₀ serves both objectives)
+  pl.var_mask = mode == OMB_EHVI_REFERENCE ? 1u : 3u;
   pl.P = P;
   pl.mode = mode;
   pl.r[0] = r_host[0];
@@ -766,6 +781,7 @@ int omb_plan_ehvi_mc(omb_ctx* ctx, int k, const double* cache_host, int M, const
   Plan pl;
   pl.kind = PLAN_EHVI_MC;
   pl.k = k;
+  pl.var_mask = 1u;   // ehvi_mc_kernel: σ²₀ for every objective
   pl.M = M;
   for (int j = 0; j < k; ++j) pl.r[j] = r_host[j];
   pl.hv = hv_pf;
@@ -794,6 +810,7 @@ int omb_plan_ehvi_boxes(omb_ctx* ctx, int k, const double* coords_host, int C, c
   Plan pl;
   pl.kind = PLAN_EHVI_BOXES;
   pl.k = k;
+  pl.var_mask = all_objectives(k);
   pl.C = C;
   pl.B = B;
   pl.geo = static_cast<const double*>(ctx->geo);
@@ -820,6 +837,7 @@ int omb_plan_ehvi_boxes_k(omb_ctx* ctx, int k, const double* coords_host, int C,
   pl.kind = PLAN_EHVI_BOXES;
   pl.boxes_kd = true;
   pl.k = k;
+  pl.var_mask = all_objectives(k);
   pl.C = C;
   pl.B = B;
   pl.geo = static_cast<const double*>(ctx->geo);
@@ -842,6 +860,7 @@ int omb_plan_hvpoi(omb_ctx* ctx, const double* cells_host, int C) {
   Plan pl;
   pl.kind = PLAN_HVPOI;
   pl.k = 2;
+  pl.var_mask = 3u;
   pl.C = C;
   pl.geo = static_cast<const double*>(ctx->geo);
   ctx->plan = pl;
@@ -864,6 +883,7 @@ int omb_plan_expdec(omb_ctx* ctx, int k, const double* cache_host, int M, int sc
   Plan pl;
   pl.kind = PLAN_EXPDEC;
   pl.k = k;
+  pl.var_mask = 1u;   // expdec_kernel: σ²₀ for every objective
   pl.M = M;
   pl.sp = sp;
   pl.geo = static_cast<const double*>(ctx->geo);
@@ -884,6 +904,8 @@ int omb_plan_ei_ext(omb_ctx* ctx, int kind, int k, double best, double var_eps, 
   pl.kind = PLAN_EI;
   pl.ei_kind = kind;
   pl.k = k;
+  // ei_kernel: EI of objective 0; the Pareto kind multiplies by μ₁, the constrained kind reads every σ²
+  pl.var_mask = kind == OMB_EI_CONSTRAINED ? all_objectives(k) : 1u;
   pl.best = best;
   pl.var_eps = var_eps;
   pl.pof_eps = pof_eps;
@@ -1023,7 +1045,8 @@ int omb_eval_grad(omb_ctx* ctx, const double* Xc_dev, int64_t N, double* vals_de
   int n_max = 0;
   if ((rc = grad_ws(ctx, args, k, N, aux, &Nc, &n_max))) return rc;
   // the value: omb_eval's own chain, so vals_dev is bitwise omb_eval's; it leaves μ | σ² (k, N) in ctx->work
-  if ((rc = run_chain(ctx, Xc_dev, false, 0, N, 0, vals_dev, nullptr))) return rc;
+  // (every σ²: the gradient kernels below read them all)
+  if ((rc = run_chain(ctx, Xc_dev, false, 0, N, 0, vals_dev, nullptr, true))) return rc;
   const double* mu = static_cast<const double*>(ctx->work);
   const double* var = mu + (size_t)k * (size_t)N;
   double* dadm = static_cast<double*>(ctx->gws);

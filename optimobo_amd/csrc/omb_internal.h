@@ -38,6 +38,10 @@ struct GPArgs {
   ExpCoef ec;      // exp_nonpos coefficients as kernel arguments (set by launch_posterior)
   int* fault;      // context fault word (pinned host memory): bit 0 = an LDS-counter wait ran out
   int spin_limit;  // polls per LDS-counter wait before the fault word is marked
+  // bit o set: nothing reads σ² of objective o, so its workgroups take the fused kernels' mean-only path (K*
+  // generation and μ as always, no V = L⁻¹K*, var_out untouched).  The complement of the plan's var_mask, so that
+  // zeroed arguments compute everything.
+  unsigned var_skip;
 };
 
 constexpr int kFaultSpin = 1;          // fault word bit: posterior counter-ring wait exhausted

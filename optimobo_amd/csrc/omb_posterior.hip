@@ -21,7 +21,11 @@
 //     of quad q, quads split between the two waves of a pair in Gray-code order.
 //   * μ accumulates in VALU during generation; σ² is a wave reduction of the squared MFMA
 //     accumulators followed by a fixed-order cross-wave LDS reduction (deterministic).
+//   * Objectives whose σ² nothing reads (GPArgs::var_skip, set by the fused chain from its plan) take a mean-only
+//     path in every kernel below: the same K* generation folded into μ in the same order (the same bits), no
+//     V = L⁻¹K*, no store to var_out.
 #include <algorithm>
+#include <type_traits>
 
 #include "omb_internal.h"
 #include "omb_math.h"
@@ -790,7 +794,9 @@ __global__ __launch_bounds__(64 * NW, WPE) void posterior_kernel(GPArgs args, co
       __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(g.xsq), (short)0, 8 * g.n, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_al =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(g.alpha), (short)0, 8 * g.n, 0x00020000);
-  auto generate_mfma = [&](int kc, double* buf) {
+  // keep (std::true_type / std::false_type): whether K* goes to the ring; the mean-only path generates and folds it
+  // into μ in the same order, and stores nothing
+  auto generate_mfma = [&](int kc, double* buf, auto keep) {
     if constexpr (kMfmaGen) {
       if (NW > TPC && (wave / TPC) != kc % (NW / TPC)) return;   // other waves take this chunk
 #pragma unroll
@@ -837,15 +843,17 @@ __global__ __launch_bounds__(64 * NW, WPE) void posterior_kernel(GPArgs args, co
           }
           mu_part = fma(row_val(rsrc_al, g.alpha, k0, rowbase + 4 * e), v0, mu_part);
           mu_part = fma(row_val(rsrc_al, g.alpha, k1, rowbase + 4 * e + 4), v1, mu_part);
-          buf[((4 * t + e) * CT + mg_ct) * 64 + lane] = v0;
-          buf[((4 * t + e + 1) * CT + mg_ct) * 64 + lane] = v1;
+          if constexpr (decltype(keep)::value) {
+            buf[((4 * t + e) * CT + mg_ct) * 64 + lane] = v0;
+            buf[((4 * t + e + 1) * CT + mg_ct) * 64 + lane] = v1;
+          }
         }
       }
     }
   };
   auto generate = [&](int kc, double* buf) {
     if constexpr (kMfmaGen) {
-      generate_mfma(kc, buf);
+      generate_mfma(kc, buf, std::true_type{});
       return;
     }
     if (kPairs && (kc + 1) * kChunkRows <= g.n) {
@@ -940,6 +948,31 @@ __global__ __launch_bounds__(64 * NW, WPE) void posterior_kernel(GPArgs args, co
       }
     }
   };
+
+  // ---- mean-only path (GPArgs::var_skip): nothing reads σ² of this objective, so the workgroup (obj = blockIdx.y:
+  // uniform) generates every K* chunk by the same code and the same tile deal, folds it into μ in the same order,
+  // and ends with the μ half of the epilogue below: no ring, no counters, no V = L⁻¹K*, var_out untouched.  μ keeps
+  // its bits.  (The VALU generation of the ablations has no such path and computes everything.)  Marked unlikely
+  // only for the register allocator: the full path's loop keeps its budget (with an even weight the 6-wave
+  // instantiation at n_var 8 spilled one more dword than before the path existed).
+  if constexpr (kMfmaGen) {
+    if (__builtin_expect((args.var_skip >> obj) & 1, 0)) {
+      for (int kc = 0; kc < Q; ++kc) generate_mfma(kc, nullptr, std::false_type{});
+      double s = mu_part;
+      s += __shfl_xor(s, 16);
+      s += __shfl_xor(s, 32);
+      double* redmu = kbuf + NW * BN;
+      if (lane < 16) redmu[wave * 16 + lane] = s;
+      __syncthreads();
+      if (tid < BN) {
+        double m = 0.0;
+        for (int w = tid >> 4; w < NW; w += CT) m += redmu[w * 16 + (tid & 15)];
+        const int64_t c = c0 + tid;
+        if (c < N) mu_out[(int64_t)obj * N + c] = m;
+      }
+      return;
+    }
+  }
 
   if constexpr (kCounters) {
     // Three-buffer ring with per-chunk LDS counters instead of a block barrier per chunk:
@@ -1141,39 +1174,63 @@ __global__ __launch_bounds__(512, 2) void posterior_tile_kernel(GPArgs args, con
   OMB_POST_TRACE(1);
 
   double mu_part = 0.0;
+  // keep (std::true_type / std::false_type): whether K* goes to LDS (false: the mean-only path below)
+  auto generate = [&](auto keep) {
 #pragma unroll
-  for (int i = 0; i < GT; ++i) {
-    const int T = wave / CT + (NW / CT) * i;
-    if (T < g.R) {
-      const d2* xa = reinterpret_cast<const d2*>(g.Xf + (int64_t)T * (KSDP * 128) + 2 * lane);
-      d2 a[(KSD + 1) / 2];
+    for (int i = 0; i < GT; ++i) {
+      const int T = wave / CT + (NW / CT) * i;
+      if (T < g.R) {
+        const d2* xa = reinterpret_cast<const d2*>(g.Xf + (int64_t)T * (KSDP * 128) + 2 * lane);
+        d2 a[(KSD + 1) / 2];
 #pragma unroll
-      for (int p = 0; p < (KSD + 1) / 2; ++p) a[p] = xa[64 * p];
-      d4 cr = d4{0.0, 0.0, 0.0, 0.0};
+        for (int p = 0; p < (KSD + 1) / 2; ++p) a[p] = xa[64 * p];
+        d4 cr = d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-      for (int s = 0; s < KSD; ++s)
-        cr = __builtin_amdgcn_mfma_f64_16x16x4f64((s & 1) ? a[s >> 1].y : a[s >> 1].x, bfr[s], cr, 0, 0, 0);
+        for (int s = 0; s < KSD; ++s)
+          cr = __builtin_amdgcn_mfma_f64_16x16x4f64((s & 1) ? a[s >> 1].y : a[s >> 1].x, bfr[s], cr, 0, 0, 0);
 #pragma unroll
-      for (int e = 0; e < 4; e += 2) {
-        const int k0 = 16 * T + 4 * e + (lane >> 4), k1 = k0 + 4;
-        const double r2a = kAug ? cr[e] : fma(-2.0, cr[e], g.xsq[k0] + csq);
-        const double r2b = kAug ? cr[e + 1] : fma(-2.0, cr[e + 1], g.xsq[k1] + csq);
-        double v0, v1;
-        if constexpr (kTab256)
-          matern_r2_tab256_x2(r2a, r2b, pm, args.ec, etab, v0, v1);
-        else
-          kernel_of_r2_tab_x2<KIND>(r2a, r2b, pm, args.ec, etab, v0, v1);
-        if constexpr (!kAug) {
-          v0 = (k0 < g.n) ? v0 : 0.0;
-          v1 = (k1 < g.n) ? v1 : 0.0;
+        for (int e = 0; e < 4; e += 2) {
+          const int k0 = 16 * T + 4 * e + (lane >> 4), k1 = k0 + 4;
+          const double r2a = kAug ? cr[e] : fma(-2.0, cr[e], g.xsq[k0] + csq);
+          const double r2b = kAug ? cr[e + 1] : fma(-2.0, cr[e + 1], g.xsq[k1] + csq);
+          double v0, v1;
+          if constexpr (kTab256)
+            matern_r2_tab256_x2(r2a, r2b, pm, args.ec, etab, v0, v1);
+          else
+            kernel_of_r2_tab_x2<KIND>(r2a, r2b, pm, args.ec, etab, v0, v1);
+          if constexpr (!kAug) {
+            v0 = (k0 < g.n) ? v0 : 0.0;
+            v1 = (k1 < g.n) ? v1 : 0.0;
+          }
+          mu_part = fma(g.alpha[k0], v0, mu_part);
+          mu_part = fma(g.alpha[k1], v1, mu_part);
+          if constexpr (decltype(keep)::value) {
+            kbuf[((4 * T + e) * CT + ct_g) * 64 + lane] = v0;
+            kbuf[((4 * T + e + 1) * CT + ct_g) * 64 + lane] = v1;
+          }
         }
-        mu_part = fma(g.alpha[k0], v0, mu_part);
-        mu_part = fma(g.alpha[k1], v1, mu_part);
-        kbuf[((4 * T + e) * CT + ct_g) * 64 + lane] = v0;
-        kbuf[((4 * T + e + 1) * CT + ct_g) * 64 + lane] = v1;
       }
     }
+  };
+  // ---- mean-only path (GPArgs::var_skip; obj = blockIdx.y: uniform): the same generation folded into μ in the same
+  // order, nothing stored to LDS, then the μ half of the epilogue below — no V = L⁻¹K*, var_out untouched
+  if ((args.var_skip >> obj) & 1) {
+    generate(std::false_type{});
+    double mp = mu_part;
+    mp += __shfl_xor(mp, 16);
+    mp += __shfl_xor(mp, 32);
+    double* redmu = kbuf + 4 * BN;
+    if (lane < 16) redmu[wave * 16 + lane] = mp;
+    __syncthreads();
+    if (tid < BN) {
+      double m = 0.0;
+      for (int w = tid >> 4; w < NW; w += CT) m += redmu[w * 16 + (tid & 15)];
+      const int64_t c = c0 + tid;
+      if (c < N) mu_out[(int64_t)obj * N + c] = m;
+    }
+    return;
   }
+  generate(std::true_type{});
   OMB_POST_TRACE(2);
   __syncthreads();
   OMB_POST_TRACE(3);
@@ -1399,12 +1456,11 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : NW / 4) void posterior_reg_k
 
   const double pm[3] = {g.variance, kSqrt5 * g.variance, kFiveThirds * g.variance};
   const d2* xf = XL ? reinterpret_cast<const d2*>(lds_X) + lane : reinterpret_cast<const d2*>(g.Xf) + lane;
-  for (; t < ntiles; t += stride) {
-    const int64_t c = 16 * t + (lane & 15);
+  // B fragment [−2·x*/ℓ, 1, ‖x*/ℓ‖²] of tile t: lane l needs dims 4s + (l>>4) only; ‖x*/ℓ‖² from the four
+  // lane groups by two shuffles
+  auto cand_fragment = [&](double (&bfr)[KSD]) {
     if constexpr ((ABL & 64) == 0)
       if (t != first) load_raw(t, raw);
-    // B fragment [−2·x*/ℓ, 1, ‖x*/ℓ‖²]: lane l needs dims 4s + (l>>4) only; ‖x*/ℓ‖² from the four
-    // lane groups by two shuffles
     double xs[KSD], csq = 0.0;
 #pragma unroll
     for (int q = 0; q < KSD; ++q) {
@@ -1419,39 +1475,71 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : NW / 4) void posterior_reg_k
       if (t + stride < ntiles) load_raw(t + stride, raw);
     csq += __shfl_xor(csq, 16);
     csq += __shfl_xor(csq, 32);
-    double bfr[KSD];
 #pragma unroll
     for (int s = 0; s < KSD; ++s) {
       const int j = 4 * s + (lane >> 4);
       bfr[s] = (j < d) ? -2.0 * xs[s] : (j == d ? 1.0 : (j == d + 1 ? csq : 0.0));
     }
+  };
+  // K* of training-row tile T against the tile's 16 candidates (kv: the B fragments of k-steps 4T .. 4T + 3),
+  // folded into μ
+  auto kstar_tile = [&](int T, const double (&bfr)[KSD], double (&kv)[4], double& mu_part) {
+    const int Tl = XL ? T : min(T, R - 1);        // T ≥ R: finite stand-in rows (zero L⁻¹ / α)
+    d2 a[KSDP];
+#pragma unroll
+    for (int p = 0; p < KSDP; ++p) a[p] = xf[64 * (KSDP * Tl + p)];
+    d4 cr = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < KSD; ++q)
+      cr = __builtin_amdgcn_mfma_f64_16x16x4f64((q & 1) ? a[q >> 1].y : a[q >> 1].x, bfr[q], cr, 0, 0, 0);
+#pragma unroll
+    for (int e = 0; e < 4; e += 2) {
+      if constexpr ((ABL & 8) != 0) {
+        kv[e] = cr[e];
+        kv[e + 1] = cr[e + 1];
+      } else if constexpr (kTab256) {
+        matern_r2_tab256_x2<(ABL & 16) != 0, (ABL & 32) != 0>(cr[e], cr[e + 1], pm, args.ec, etab, kv[e], kv[e + 1]);
+      } else {
+        kernel_of_r2_tab_x2<KIND>(cr[e], cr[e + 1], pm, args.ec, etab, kv[e], kv[e + 1]);
+      }
+      mu_part = fma(lds_alpha[16 * T + 4 * e + (lane >> 4)], kv[e], mu_part);
+      mu_part = fma(lds_alpha[16 * T + 4 * e + 4 + (lane >> 4)], kv[e + 1], mu_part);
+    }
+  };
+
+  // ---- mean-only path (GPArgs::var_skip; obj = blockIdx.y: uniform): the same K* values folded into μ in the same
+  // order; no product with the staged L⁻¹, no σ², var_out untouched
+  if ((args.var_skip >> obj) & 1) {
+    for (; t < ntiles; t += stride) {
+      const int64_t c = 16 * t + (lane & 15);
+      double bfr[KSD];
+      cand_fragment(bfr);
+      double mu_part = 0.0;
+      // two row tiles per trip: enough independent transform chains, and few enough registers that the full path
+      // below keeps its budget
+#pragma unroll 2
+      for (int T = 0; T < RMAX; ++T) {
+        double kv[4];
+        kstar_tile(T, bfr, kv, mu_part);
+      }
+      mu_part += __shfl_xor(mu_part, 16);
+      mu_part += __shfl_xor(mu_part, 32);
+      if (lane < 16 && c < N) mu_out[(int64_t)obj * N + c] = mu_part;
+    }
+    return;
+  }
+
+  for (; t < ntiles; t += stride) {
+    const int64_t c = 16 * t + (lane & 15);
+    double bfr[KSD];
+    cand_fragment(bfr);
 
     d4 acc[RMAX];
     double mu_part = 0.0, s = 0.0;
 #pragma unroll
     for (int T = 0; T < RMAX; ++T) {
-      const int Tl = XL ? T : min(T, R - 1);        // T ≥ R: finite stand-in rows (zero L⁻¹ / α)
-      d2 a[KSDP];
-#pragma unroll
-      for (int p = 0; p < KSDP; ++p) a[p] = xf[64 * (KSDP * Tl + p)];
-      d4 cr = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int q = 0; q < KSD; ++q)
-        cr = __builtin_amdgcn_mfma_f64_16x16x4f64((q & 1) ? a[q >> 1].y : a[q >> 1].x, bfr[q], cr, 0, 0, 0);
       double kv[4];
-#pragma unroll
-      for (int e = 0; e < 4; e += 2) {
-        if constexpr ((ABL & 8) != 0) {
-          kv[e] = cr[e];
-          kv[e + 1] = cr[e + 1];
-        } else if constexpr (kTab256) {
-          matern_r2_tab256_x2<(ABL & 16) != 0, (ABL & 32) != 0>(cr[e], cr[e + 1], pm, args.ec, etab, kv[e], kv[e + 1]);
-        } else {
-          kernel_of_r2_tab_x2<KIND>(cr[e], cr[e + 1], pm, args.ec, etab, kv[e], kv[e + 1]);
-        }
-        mu_part = fma(lds_alpha[16 * T + 4 * e + (lane >> 4)], kv[e], mu_part);
-        mu_part = fma(lds_alpha[16 * T + 4 * e + 4 + (lane >> 4)], kv[e + 1], mu_part);
-      }
+      kstar_tile(T, bfr, kv, mu_part);
       if constexpr (!(ABL & 2)) {
 #pragma unroll
         for (int r = T; r < RMAX; ++r) {
