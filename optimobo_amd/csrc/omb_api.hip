@@ -100,7 +100,7 @@ struct omb_ctx {
   int fused_chain = 0;  // OMB_DEBUG_FUSED_CHAIN: 0 EHVI-2D then the arg-max's passes, 1 one ticketed launch, 2 EHVI
                         // with the per-workgroup pairs, then the arg-max's second pass
   bool argmax_one_pass = false;  // OMB_DEBUG_ARGMAX_PASSES: 1 (one launch) or 2 (default: measured level)
-  int chol_mode = kCholAuto;     // OMB_DEBUG_CHOL_MODE (value & 3)
+  int chol_mode = kCholPersistent;   // OMB_DEBUG_CHOL_MODE (value & 3): 1 per-step launches, else persistent
   int chol_acq_rel = 0;          // OMB_DEBUG_CHOL_MODE (value & 4): release / acquire hand-offs
   int chol_single = 0;           // OMB_DEBUG_CHOL_MODE (value & 8): every trailing update its own task
   bool select_seq = false;       // OMB_DEBUG_SELECT_SEQ: the sequential greedy walk for B ≤ 64 too
@@ -507,8 +507,7 @@ int omb_debug_set(omb_ctx* ctx, int what, int64_t value) {
       return fail(ctx, OMB_EINVAL, "Cholesky mode %lld (0 auto, 1 per-step launches, 2 one persistent launch; + 4: "
                   "release / acquire hand-offs; + 8: the persistent launch's trailing updates one task per step)",
                   (long long)value);
-    const int modes[3] = {kCholAuto, kCholBlocked, kCholPersistOnly};
-    ctx->chol_mode = modes[value & 3];
+    ctx->chol_mode = (value & 3) == 1 ? kCholSteps : kCholPersistent;   // 0 (auto) and 2 are the same schedule
     ctx->chol_acq_rel = (value & 4) ? 1 : 0;
     ctx->chol_single = (value & 8) ? 1 : 0;
     return OMB_OK;
@@ -1183,15 +1182,16 @@ static int chol_workspace(omb_ctx* ctx, int64_t N, int** dinfo, double** ws) {
   return OMB_OK;
 }
 
-// sync_zeroed: the persistent launch's sync words and info were zeroed by the covariance SYRK (cov_build)
-static int chol_enqueue(omb_ctx* ctx, double* A, int64_t N, int64_t lda, double jitter, bool sync_zeroed = false) {
+// zeroed / n_zeroed: the ints that the covariance SYRK (cov_build) set to 0 together with the status, or none
+static int chol_enqueue(omb_ctx* ctx, double* A, int64_t N, int64_t lda, double jitter, const int* zeroed = nullptr,
+                        int n_zeroed = 0) {
   int* dinfo = nullptr;
   double* ws = nullptr;
   int rc = chol_workspace(ctx, N, &dinfo, &ws);
   if (rc) return rc;
   OMB_HIP(ctx, launch_add_diag(ctx->stream, A, N, lda, jitter));
   OMB_HIP(ctx, launch_cholesky_mode(ctx->stream, A, N, lda, dinfo, ws, ctx->chol_mode, ctx->spin_limit,
-                                    ctx->chol_acq_rel, ctx->chol_single, sync_zeroed));
+                                    ctx->chol_acq_rel, ctx->chol_single, zeroed, n_zeroed));
   OMB_HIP(ctx, hipMemcpyAsync(ctx->info_host, dinfo, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   return OMB_OK;
 }
@@ -1290,7 +1290,7 @@ int omb_posterior_samples(omb_ctx* ctx, int obj, const double* Xc_dev, int64_t N
     if ((e = cov_build(ctx, s, Xc_dev, N, V, S, N, cws, jit, prescale && t == 0, sync_ints, n_sync, dinfo, &zeroed)) !=
         hipSuccess)   // Σ + jit·I
       return hip_fail(ctx, e, "posterior_samples (cov)");
-    if ((rc = chol_enqueue(ctx, S, N, N, 0.0, zeroed))) return rc;
+    if ((rc = chol_enqueue(ctx, S, N, N, 0.0, zeroed ? sync_ints : nullptr, zeroed ? n_sync : 0))) return rc;
     // the draws are queued before the status is read (no idle GPU between the factor and them); a failed factor's
     // draws are overwritten by the next try's
     if ((e = launch_chol_samples(ctx->stream, S, N, N, mu, Zt_dev, B, Y_dev, cws)) != hipSuccess)

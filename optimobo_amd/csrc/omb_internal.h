@@ -157,34 +157,27 @@ hipError_t launch_cov_syrk(hipStream_t s, int64_t N, int64_t K, const double* V,
 hipError_t launch_mirror_lower(hipStream_t stream, double* S, int64_t N, int64_t lds);
 hipError_t launch_add_diag(hipStream_t stream, double* S, int64_t N, int64_t lds, double v);
 // in-place lower Cholesky; info (device int, zeroed by the first kernel) = first bad column (1-based);
-// ws: chol_ws_doubles(N) device doubles of workspace (the inverse of the current diagonal block, as MFMA
-// fragments for the panel product, then one int flag per step).  info = kCholSpinFault: a workgroup's
+// ws: chol_ws_doubles(N) device doubles of workspace (the inverses of the diagonal blocks, as MFMA fragments for the
+// panel product, then the schedule's flags).  info = kCholSpinFault: a workgroup's
 // wait for the diagonal block ran out after spin_limit polls (the factor is invalid; reported as OMB_EHIP).
 constexpr int kCholWsDoubles = 64 * 64;
 constexpr int kCholSpinFault = -2147483647;
-// kCholBlocked (round 4): the diagonal blocks by tiles of 16 (chol64_blocked); kCholBlockedAcqRel: the same with
-// the fused step's flag as an agent-scope release / acquire (tools/ablate/ablate_chol)
-// kCholPersistent (round 4): the whole factorisation in one launch (chol_persist_kernel; kCholBlocked when A is too
-// large for its 32-bit buffer offsets)
-// kCholPersistent: the last min(t, 32) of the t 64-column steps in one persistent launch, the steps before it as
-// per-step launches (their trailing updates are faster while the trailing matrix is large; omb_linalg.hip
-// chol_hybrid_k0).  kCholAuto (launch_cholesky) = kCholPersistent where A fits its 32-bit buffer offsets, else
-// kCholBlocked.
-// kCholPersistOnly: the whole factorisation in one persistent launch (k0 = 0; kCholBlocked when A is too large).
-enum { kCholTwoLaunch = 0, kCholFused = 1, kCholBlocked = 2, kCholBlockedAcqRel = 3, kCholPersistent = 4, kCholAuto = 5,
-       kCholPersistOnly = 6 };
+// Two schedules.  kCholPersistent, the default: the whole factorisation in one persistent launch (chol_persist_kernel:
+// one workgroup walks the diagonal, the others draw panel and update tasks from a table), or kCholSteps where A is too
+// large for that launch's 32-bit buffer offsets.  kCholSteps: one launch per 64-column step (chol_update_kernel, with
+// the next diagonal block and panel inside).
+enum { kCholPersistent = 0, kCholSteps = 1 };
 int64_t chol_ws_doubles(int64_t N);
-hipError_t launch_cholesky(hipStream_t stream, double* A, int64_t N, int64_t lda, int* info, double* ws,
-                           int spin_limit = kDefaultSpinLimit);
 // acq_rel = 1: every cross-workgroup hand-off of the schedule as an agent-scope release / acquire pair (the HIP memory
 // model's form; the default relaxed / sc1 form is measured valid on gfx950 and checked bitwise against this one).
-// single_steps = 1: the persistent launch's workers take every trailing update as its own task (round 5's table; the
-// default batches far tiles' updates, bitwise the same factor — checked against this one)
-// sync_zeroed: the persistent launch's sync words (chol_persist_sync_words) and info are already zero (written by the
-// covariance SYRK of the Thompson chain), so the k0 = 0 persistent launch goes without its init kernel
+// single_steps = 1: the persistent launch's workers take every trailing update as its own task (the default batches
+// far tiles' updates, bitwise the same factor — checked against this one)
+// zeroed / n_zeroed: ints that an earlier launch on the stream has set to 0 together with info (the covariance SYRK of
+// the Thompson chain).  Where they are exactly the persistent launch's sync words (chol_persist_sync_words), it goes
+// without its init kernel; any other range, and the per-step schedule, ignore them.
 hipError_t launch_cholesky_mode(hipStream_t stream, double* A, int64_t N, int64_t lda, int* info, double* ws, int mode,
                                 int spin_limit = kDefaultSpinLimit, int acq_rel = 0, int single_steps = 0,
-                                bool sync_zeroed = false);
+                                const int* zeroed = nullptr, int n_zeroed = 0);
 int chol_persist_sync_words(double* ws, int64_t N, int** ints);
 // Y (B, N) = μ + Zt Lᵀ (L lower, N×N): row b of Y is the sample μ + L z_b.
 // ws: chol_samples_ws_doubles(N, B) device doubles (split-K partial products; 0 when unsplit).

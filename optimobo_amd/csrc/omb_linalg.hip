@@ -151,15 +151,6 @@ __global__ void add_diag_kernel(double* __restrict__ S, int64_t N, int64_t lds, 
 // ----------------------------------------------------------------------------- Cholesky
 constexpr int kNB = 64;
 
-// Phase timestamps of the diagonal-block factorisation for tools/ablate/ablate_chol (empty here).
-#ifndef OMB_CHOL_TRACE
-#define OMB_CHOL_TRACE(id, cond)
-#endif
-// per-column timestamps (wave w done with column j) for tools/ablate/ablate_chol (empty here)
-#ifndef OMB_CHOL_COL
-#define OMB_CHOL_COL(w, j, cond)
-#endif
-
 __device__ __forceinline__ double readlane_f64(double v, int l) {
   const long long b = __builtin_bit_cast(long long, v);
   const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(b & 0xffffffffll), l);
@@ -192,31 +183,18 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
-// ----------------------------------------------------------------------------- Cholesky, fused steps
-// The blocked factorisation per 64-column step k (launch_cholesky; round 3 folds the panel into the update
-// launch, see chol_update_kernel<FUSE>):
-//   chol_panel_kernel   the panel below the diagonal block, L21 = A21 · W_kkᵀ with W_kk = L_kk⁻¹, on
-//                       MFMA (16 rows per 2-wave workgroup; W_kk's B fragments read from the workspace);
-//   chol_update_kernel  the trailing update A22 −= L21 L21ᵀ (lower triangle, 64×64 MFMA tiles) whose
-//                       workgroup owning the next diagonal tile factors it right after its update
-//                       (chol64_factor), inverts the factor and writes L_{k+1,k+1} and the fragments of
-//                       W_{k+1,k+1} for the next panel (chol64_factor, chol64_inverse);
-//   chol_diag_kernel    step 0's diagonal block (nothing precedes it).
-// The serial chain of a step is the diagonal workgroup's factor + inverse.  Round 2's panel solved
-// x · L_kkᵀ = b by substitution, a 64-step dependent chain per row with an LDS broadcast read at every
-// step (29.5 µs per step at N = 3000, profiles/r02_v20_c6_top_kernels.txt), and the factor broadcast each
-// column through LDS (29.9 µs for the update kernel's diagonal workgroup).  Solving with the explicit
-// inverse of the 64×64 diagonal block is the usual GPU TRSM; its error grows with cond(L_kk), which
-// the jitter of omb_posterior_samples bounds.
-
-// LDS of the diagonal-block factorisation (diagonal workgroups of chol_update_kernel, chol_diag_kernel):
-//   Lb    4 sub-blocks × 64 rows × kLbP doubles: Lb[(b·64 + r)·kLbP + q] = L[r][16b + q]; the 144-B row
-//         pitch keeps 16 lanes reading 16 different rows conflict-free;
-//   aux   cbuf (2 × 64: the current column, double buffered) | dinv (64: 1/L_jj);
-//   prog  8 ints: columns of sub-block b published to Lb so far (0..3); W_bb in Lb (4..7).
-constexpr int kLbP = 18;
-constexpr int kLbDoubles = 4 * kNB * kLbP;
-constexpr int kCholAux = 2 * kNB + kNB;
+// ----------------------------------------------------------------------------- Cholesky, per-step launches
+// The blocked factorisation per 64-column step k (launch_cholesky_blocked):
+//   chol_diag_blk_kernel  step 0's diagonal block (nothing precedes it);
+//   chol_panel_kernel     step 0's panel below the diagonal block, L21 = A21 · W_kkᵀ with W_kk = L_kk⁻¹, on MFMA
+//                         (16 rows per 2-wave workgroup; W_kk's B fragments read from the workspace);
+//   chol_update_kernel    the trailing update A22 −= L21 L21ᵀ (lower triangle, 64×64 MFMA tiles), whose workgroup
+//                         owning the next diagonal tile factors and inverts it (chol64_blocked) and whose workgroups
+//                         below it form the next step's panel rows, so every step after the first is one launch.
+// The serial chain of a step is the diagonal workgroup's factor + inverse.  Solving with the explicit inverse of the
+// 64×64 diagonal block is the usual GPU TRSM (substitution was a 64-step dependent chain per row with an LDS
+// broadcast read at every step: 29.5 µs per step at N = 3000, profiles/r02_v20_c6_top_kernels.txt); its error grows
+// with cond(L_kk), which the jitter of omb_posterior_samples bounds.
 
 // The W fragments are stored and (by the fused step's waiting workgroups) read as agent-scope relaxed
 // atomics: coherent across the XCDs' L2s without the L2 write-back / invalidate that an agent-scope
@@ -230,209 +208,12 @@ __device__ __forceinline__ double wf_load(const double* p) {
                                                       __HIP_MEMORY_SCOPE_AGENT));
 }
 
-// The off-diagonal blocks of W = L⁻¹ into Wf, the MFMA B fragments of chol_panel_kernel:
+// The W fragment layout: W = L_kk⁻¹ (64×64, lower) as the MFMA B fragments of the panel product, kCholWsDoubles
+// doubles per step,
 //   Wf[(jb·16 + s)·64 + l] = W[16jb + (l & 15)][m(s, l >> 4)],   m(s, g) = 16(s >> 2) + 4g + (s & 3)
-// (k-step s of the panel's output column block jb; only s < 4(jb + 1) is read — the rest of that row
-// block of W is zero — so the panel skips W's upper triangle in whole k-steps).
-// Wave j forms its column block, W_ij = −W_ii Σ_{k=j}^{i−1} L_ik W_kj for i = j+1..3, on MFMA: a product's
-// accumulator layout (lane l: rows 4e + (l >> 4), column l & 15) is the next product's B operand
-// layout, so the W_kj (k > j) stay in registers and only L and the W_ii are read from LDS.
-// Round 3: each wave runs this right after its own sub-block's tail, while the later waves still factor.
-// The sums Σ L_ik W_kj need only L (complete for row block i once sub-blocks < i are factored) and the
-// wave's own earlier blocks; only the final product waits for W_ii (wdone[i], set by wave i after its
-// tail).  After the last sub-block only the three products with W_33 remain (the whole inverse used to
-// follow a barrier after the factor: ≈ 4.8k cycles on the step's chain, profiles/r03_v37_chol_trace_paired_consumer.txt).
-__device__ __forceinline__ void chol64_inverse(int w, int r, const double* Lb, int* wdone, double* __restrict__ Wf) {
-  const int c = r & 15, g = r >> 4;
-  d4 Wc[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) Wc[i] = d4{0.0, 0.0, 0.0, 0.0};
-  static_for<1, 4>([&](auto ic) {
-    constexpr int i = decltype(ic)::value;
-    if (i > w) {
-      d4 T = d4{0.0, 0.0, 0.0, 0.0};
-      static_for<0, i>([&](auto kc) {
-        constexpr int k = decltype(kc)::value;
-        if (k >= w) {
-          static_for<0, 4>([&](auto sc) {
-            constexpr int s = decltype(sc)::value;
-            const double av = Lb[(k * 64 + 16 * i + c) * kLbP + 4 * s + g];   // L[16i + c][16k + 4s + g]
-            // B operand W_kj[4s + g][c]: W_ww from LDS, the others from registers
-            const double bv = (k == w) ? Lb[(k * 64 + 16 * k + 4 * s + g) * kLbP + c] : Wc[k][s];
-            T = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, T, 0, 0, 0);
-          });
-        }
-      });
-      // W_ii in Lb (published by wave i after its tail)
-      while (__hip_atomic_load(&wdone[i], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0)
-        __builtin_amdgcn_s_sleep(1);
-      d4 R = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-        R = __builtin_amdgcn_mfma_f64_16x16x4f64(Lb[(i * 64 + 16 * i + c) * kLbP + 4 * s + g], T[s], R, 0, 0, 0);
-      Wc[i] = -R;
-      // W[16i + 4e + g][16w + c]: jb = i, s = 4w + (c & 3), lane 4e + g + 16 (c >> 2)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) wf_store(&Wf[(i * 16 + 4 * w + (c & 3)) * 64 + 4 * e + g + 16 * (c >> 2)], Wc[i][e]);
-    }
-  });
-  OMB_CHOL_TRACE(16, w == 0 && r == 0);
-}
-
-// Factor a 64×64 SPD block with the 4 waves of a 256-thread workgroup: thread (wave w, lane r) holds
-// a[q] = A[r][16w + q] (only 16w + q ≤ r is meaningful; rows past the block are identity rows).
-// Wave b factors sub-block b (columns 16b..16b+15).  Before its turn it applies every earlier
-// sub-block's columns to its own 16 columns as they are published (a progress counter per sub-block
-// in LDS; L[r][j]·L[16w+q][j] from Lb), so when the previous wave finishes, the next one starts at once
-// — round 2's bulk update after every 16 columns took ≈ 2 µs each (profiles/r02_v24_ablate_chol.txt).
-// Column j of the own sub-block:
-//   * the serial chain runs on wave-uniform values: d_{j+1} = A'_{j+1,j+1} − (a_{j+1,j}·inv_j)², where
-//     A' and a_{j+1,j} were read (v_readlane) before inv_j is known — 9 dependent FP64 ops per column
-//     (rsq, two Newton steps, one mul, one fma);
-//   * the next two rows' entries of column j are applied at once (uniform scalars a_{j+k,j}·inv_j), the
-//     rest one column later from an LDS broadcast of the column (software pipeline);
-//   * the column goes to Lb for the later waves, then the progress counter moves (release order).
-// Entries above the diagonal are not kept at zero (a[jj] is scaled on every row, no selects); they
-// only ever feed entries above the diagonal of the same row, which nothing reads.
-// When its sub-block is done, the wave stores its 16 columns of L into A (rows < nb), then inverts its
-// 16×16 diagonal block by substitution (x[m] = (δ_mc − Σ_{p<m} L_ww[m][p] x[p]) / L_ww[m][m], lane l →
-// column l & 15, rows of L_ww as LDS broadcasts), leaves W_ww in place of L_ww in Lb and writes W_ww's
-// fragments to Wf (see chol64_inverse) — while the later waves are still factoring.
-// bad_lds[0] = 1-based first non-positive pivot column or 0 (valid after the caller's barrier).
-__device__ __forceinline__ void chol64_factor(double (&a)[16], int w, int r, int nb, double* Lb, double* aux,
-                                              int* prog, int* bad_lds, double* __restrict__ A, int64_t lda,
-                                              int64_t c0, double* __restrict__ Wf) {
-  double* dinv = aux + 2 * kNB;
-  // ---- earlier sub-blocks' columns, as they appear
-#pragma unroll 1
-  for (int b = 0; b < w; ++b) {
-    // two published columns per step: row q's entries of columns jj, jj+1 are adjacent in Lb (one b128
-    // read), so a step is 17 b128 reads and 32 fmas (in column order: bitwise the one-column loop); one
-    // column per step took ≈ 530 cycles against the owner's ≈ 470 and fell ≈ 1,300 cycles behind per
-    // sub-block (profiles/r03_v27_chol_column_trace.txt)
-#pragma unroll 1   // rolled: unrolled, the column reads were merged and hoisted (512 VGPRs + spills)
-    for (int jj = 0; jj < 16; jj += 2) {
-      while (__hip_atomic_load(&prog[b], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <= jj + 1)
-        __builtin_amdgcn_s_sleep(1);
-      const double2 lr = *reinterpret_cast<const double2*>(Lb + (b * 64 + r) * kLbP + jj);
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const double2 v = *reinterpret_cast<const double2*>(Lb + (b * 64 + 16 * w + q) * kLbP + jj);
-        a[q] = fma(-lr.x, v.x, a[q]);
-        a[q] = fma(-lr.y, v.y, a[q]);
-      }
-      OMB_CHOL_COL(w, 16 * b + jj + 1, r == 0);
-    }
-  }
-  // ---- own sub-block
-  static_for<0, 4>([&](auto bc) {
-    constexpr int b = decltype(bc)::value;
-    if (w != b) return;
-    OMB_CHOL_TRACE(2 + 2 * b, r == 0);
-    int bad = 0;
-    double dj = readlane_f64(a[0], 16 * b);          // first pivot (every earlier column applied)
-    double pl = 0.0;   // the previous column's entry of this row
-    double pv[16];     // the previous column's entries L[16b+q][j−1] (q ≥ jj+2), from LDS
-    // order within column j: chain (pre-read entries, inv, next pivot), scale + the next two rows,
-    // publish (Lb, progress), then column j−1's deferred updates, then column j's broadcast loads —
-    // the loads' LDS latency hides behind the next column's chain
-    static_for<0, 16>([&](auto jc) {
-      constexpr int jj = decltype(jc)::value;
-      constexpr int j = 16 * b + jj;
-      // entries for the chain and the next two rows (column j−1's deferred updates never touch them)
-      double a1 = 0.0, a2 = 0.0, ap = 0.0;
-      if constexpr (jj < 15) {
-        a1 = readlane_f64(a[jj], j + 1);
-        ap = readlane_f64(a[jj + 1], j + 1);
-      }
-      if constexpr (jj < 14) a2 = readlane_f64(a[jj], j + 2);
-      if (!(dj > 0.0)) {
-        if (bad == 0) bad = j + 1;
-        dj = 1.0;                                      // continue without NaNs; flagged
-      }
-      const double y0 = __builtin_amdgcn_rsq(dj);
-      const double hd = 0.5 * dj;
-      const double y1 = fma(y0, fma(-hd * y0, y0, 0.5), y0);
-      const double inv = fma(y1, fma(-hd * y1, y1, 0.5), y1);
-      double s1 = 0.0, s2 = 0.0;
-      if constexpr (jj < 15) {
-        s1 = a1 * inv;                                 // L[j+1][j]
-        dj = fma(-s1, s1, ap);                         // next pivot
-      }
-      if constexpr (jj < 14) s2 = a2 * inv;            // L[j+2][j]
-      const double lrj = a[jj] * inv;                  // row j: dj·inv = √dj
-      a[jj] = lrj;
-      if constexpr (jj < 15) a[jj + 1] = fma(-lrj, s1, a[jj + 1]);
-      if constexpr (jj < 14) a[jj + 2] = fma(-lrj, s2, a[jj + 2]);
-      // publish the column, then release it to the later waves (before any new LDS load is queued)
-      if (r == j) dinv[j] = inv;
-      Lb[(b * 64 + r) * kLbP + jj] = lrj;
-      if constexpr (b < 3) {
-        if (r == 0) __hip_atomic_store(&prog[b], jj + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-      }
-      // column j−1's remaining updates (q ≥ jj+2; loaded one column ago, their latency behind the chain)
-      if constexpr (jj >= 1) {
-#pragma unroll
-        for (int q = jj + 2; q < 16; ++q) a[q] = fma(-pl, pv[q], a[q]);
-      }
-      if constexpr (jj < 13) {
-        double* cb = aux + kNB * (jj & 1);
-        cb[r] = lrj;
-#pragma unroll
-        for (int q = jj + 3; q < 16; ++q) pv[q] = cb[16 * b + q];
-        pl = lrj;
-      }
-      OMB_CHOL_COL(w, j, r == 0);
-      __builtin_amdgcn_sched_barrier(0);
-    });
-    OMB_CHOL_TRACE(3 + 2 * b, r == 0);
-    if (r == 0 && bad) bad_lds[0] = bad;
-    // ---- this sub-block's 16 columns of L into A: lane → (row 4i + (r >> 4), column r & 15)
-    {
-      const int q = r & 15;
-      double lv[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) lv[i] = Lb[(b * 64 + 4 * i + (r >> 4)) * kLbP + q];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int row = 4 * i + (r >> 4);
-        if (row < nb && 16 * b + q <= row) A[(c0 + row) * lda + c0 + 16 * b + q] = lv[i];
-      }
-    }
-    // ---- W_bb = L_bb⁻¹, column c = r & 15 per lane
-    const int c = r & 15, g = r >> 4;
-    const double* Ld = Lb + (b * 64 + 16 * b) * kLbP;   // L_bb row m at Ld + m·kLbP
-    double x[16];
-    static_for<0, 16>([&](auto mc) {
-      constexpr int m = decltype(mc)::value;
-      // row m's offset passes through an empty asm that consumes x[m−2]: its reads issue one row
-      // ahead of their use, not all 120 at once (which took the kernel to 256 VGPRs)
-      int off = m * kLbP;
-      if constexpr (m >= 2) asm volatile("" : "+v"(off) : "v"(x[m - 2]));
-      double t0 = (m == c) ? 1.0 : 0.0, t1 = 0.0;
-#pragma unroll
-      for (int p = 0; p + 1 < m; p += 2) {
-        const double2 l = *reinterpret_cast<const double2*>(Ld + off + p);
-        t0 = fma(-l.x, x[p], t0);
-        t1 = fma(-l.y, x[p + 1], t1);
-      }
-      if constexpr (m & 1) t0 = fma(-Ld[off + m - 1], x[m - 1], t0);
-      x[m] = (t0 + t1) * dinv[16 * b + m];
-    });
-    // every lane's reads of L_bb precede the overwrite (LDS operations of a wave complete in order)
-    if (r < 16) {
-#pragma unroll
-      for (int m = 0; m < 16; ++m) Lb[(b * 64 + 16 * b + m) * kLbP + c] = x[m];
-    }
-    // W_bb's fragments: rows jb = b, k-steps s = 4b + u: W[16b + c][16b + 4g + u]
-#pragma unroll
-    for (int u = 0; u < 4; ++u) wf_store(&Wf[(b * 16 + 4 * b + u) * 64 + r], Lb[(b * 64 + 16 * b + c) * kLbP + 4 * g + u]);
-    // W_bb is in Lb: release it to the waves forming W's earlier column blocks (wdone = prog + 4)
-    if (r == 0) __hip_atomic_store(&prog[4 + b], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    OMB_CHOL_TRACE(10 + b, r == 0);
-  });
-  chol64_inverse(w, r, Lb, prog + 4, Wf);
-}
+// (k-step s of the panel's output column block jb; only s < 4(jb + 1) is read — the rest of that row block of W is
+// zero — so the panel skips W's upper triangle in whole k-steps).  chol64_blocked writes it, chol_panel_kernel, the
+// panel rows of chol_update_kernel and chol_persist_panel read it.
 
 // ----------------------------------------------------------------------------- Cholesky, blocked diagonal block
 // Round 4.  The 64×64 diagonal block is factored as 4 × 4 tiles of 16 (right-looking inside the block), with
@@ -442,7 +223,9 @@ __device__ __forceinline__ void chol64_factor(double (&a)[16], int w, int r, int
 //              U_b  D_wj −= L_wb L_jbᵀ for b < j ≤ w, 4 MFMAs each (L_jb of wave j after its flag; for j = w both
 //                   operands are the P_b accumulator);
 //   F_w        the tile (w, w): its Cholesky factor and inverse W_ww in registers (chol16_factor);
-// then, as chol64_inverse, W's column block w: W_iw = −W_ii Σ_{k=w}^{i−1} L_ik W_kw (i > w) on MFMA.
+// then W's column block w: W_iw = −W_ii Σ_{k=w}^{i−1} L_ik W_kw (i > w) on MFMA — a product's accumulator layout
+// (lane l: rows 4e + (l >> 4), column l & 15) is the next product's B operand layout, so the W_kw (k > w) stay in
+// registers; the sums need only L, only the final product waits for W_ii.
 // The block's serial chain is F_0 → P_0 U_0 (wave 1) → F_1 → … → F_3 → the three products with W_33: four
 // 16-column factors and three 8-MFMA hand-offs.  Round 3 ran one wave per 16-column strip of all 64 rows
 // (≈ 470 cycles per column on the owner, ≈ 40k cycles for the block, profiles/r03_v38_chol_trace_pipelined_inverse.txt).
@@ -550,7 +333,7 @@ __device__ __forceinline__ void load_row16(const double* __restrict__ p, bool ok
 }
 
 // The diagonal block at rows / columns r0 .. r0+63 of A (nb ≤ 64 real rows; the rest identity), factored in place
-// (lower triangle of rows < nb), with W = L⁻¹'s MFMA fragments to Wf (the layout of chol64_inverse).  kCholDOuter: A22_00
+// (lower triangle of rows < nb), with W = L⁻¹'s MFMA fragments to Wf (the W fragment layout above).  kCholDOuter: A22_00
 // minus the product of the panel rows A[r0 + ·][c0 .. c0+63].  Ds, Wl, fl: LDS (fl zeroed by the caller and a
 // barrier passed).  The caller reads fl[20] (block-relative 1-based first bad column, 0 = none) after a barrier.
 // MODE kCholDLoad (step 0 / chol_diag_blk_kernel): D = A_kk; kCholDOuter (chol_update_kernel): D = A22_00 − L21_0
@@ -737,7 +520,7 @@ __device__ __forceinline__ void chol64_blocked(double* __restrict__ A, int64_t l
   });
 }
 
-// Step 0's diagonal block (chol_diag_kernel's blocked form); zeroes info and the fused steps' flags.
+// Step 0's diagonal block; zeroes info and the fused steps' flags.
 __global__ __launch_bounds__(256) void chol_diag_blk_kernel(double* __restrict__ A, int64_t N, int64_t lda,
                                                             double* __restrict__ ws, int* __restrict__ info,
                                                             int* __restrict__ flags, int nflags) {
@@ -753,67 +536,14 @@ __global__ __launch_bounds__(256) void chol_diag_blk_kernel(double* __restrict__
   if (threadIdx.x == 0 && (fl[20] || fl[21])) atomicCAS(info, 0, fl[21] ? kCholSpinFault : fl[20]);
 }
 
-__global__ __launch_bounds__(256) void chol_diag_kernel(double* __restrict__ A, int64_t N, int64_t lda,
-                                                         double* __restrict__ ws, int* __restrict__ info,
-                                                         int* __restrict__ flags, int nflags) {
-  for (int i = threadIdx.x; i < nflags; i += blockDim.x) flags[i] = 0;
-  if (threadIdx.x == 0) *info = 0;
-  __shared__ __attribute__((aligned(16))) double Lb[kLbDoubles];
-  __shared__ double aux[kCholAux];
-  __shared__ int prog[8];   // column progress per sub-block | W_bb published
-  __shared__ int bad_lds[1];
-  const int nb = (int)(N < kNB ? N : kNB);
-  const int r = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  OMB_CHOL_TRACE(0, threadIdx.x == 0);
-  if (threadIdx.x == 0) bad_lds[0] = 0;
-  if (threadIdx.x < 8) prog[threadIdx.x] = 0;
-  double a[16];
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int c = 16 * w + q;
-    double v = (c == r) ? 1.0 : 0.0;
-    if (r < nb && c <= r) v = A[(int64_t)r * lda + c];
-    a[q] = v;
-  }
-  __syncthreads();
-  OMB_CHOL_TRACE(1, threadIdx.x == 0);
-  chol64_factor(a, w, r, nb, Lb, aux, prog, bad_lds, A, lda, 0, ws);   // with W = L⁻¹ (chol64_inverse)
-  __syncthreads();
-  OMB_CHOL_TRACE(15, threadIdx.x == 0);
-  if (threadIdx.x == 0 && bad_lds[0]) atomicCAS(info, 0, bad_lds[0]);
-}
-
-// Panel of step `step`: rows c0+64 .. N−1, L21 = A21 · Wᵀ (W = L_kk⁻¹ from the fragments of chol64_factor /
-// chol64_inverse).
+// Panel of step `step`: rows c0+64 .. N−1, L21 = A21 · Wᵀ (W = L_kk⁻¹ from the fragments chol64_blocked wrote).
 // Workgroup = 16 rows, 2 waves: wave 0 the output column blocks 0 and 3, wave 1 blocks 1 and 2 (20
 // MFMAs each).  The k index is permuted as m(s, g) = 16(s >> 2) + 4g + (s & 3) so a lane's A operands
 // are 4 contiguous doubles per 16-column group; the barrier separates both waves' reads of the rows
 // from the in-place writes.
-// The persistent launch's sync words for t steps after k0 per-step launches (chol_persist_kernel's layout: wflag[t] |
-// pflag[t·t] | cnt[t·t] | ticket | abort), word x.
-__device__ __forceinline__ int chol_persist_init_word(int x, int t, int k0) {
-  if (k0 > 0 && x >= t && x < t + t * t) {
-    const int i = (x - t) / t, k = (x - t) % t;
-    return (k == k0 && i > k0) ? 4 : 0;
-  }
-  if (k0 > 0 && x >= t + t * t && x < t + 2 * t * t) {
-    const int i = (x - t - t * t) / t, j = (x - t - t * t) % t;
-    return (j > k0 && j <= i) ? k0 : 0;
-  }
-  return 0;
-}
-
-// pinit (round 5, the hybrid schedule): step 0's panel launch also writes the later persistent launch's sync words
-// (chol_persist_init_kernel's job; the per-step launches never touch them), one launch fewer on the chain.
 template <bool VEC>
 __global__ __launch_bounds__(128) void chol_panel_kernel(double* __restrict__ A, int64_t N, int64_t lda, int step,
-                                                         const double* __restrict__ Wf, const int* __restrict__ info,
-                                                         int* __restrict__ pinit = nullptr, int pt = 0, int pk0 = 0) {
-  if (pinit) {
-    const int pn = pt + 2 * pt * pt + 2;
-    for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < pn; x += gridDim.x * blockDim.x)
-      pinit[x] = chol_persist_init_word(x, pt, pk0);
-  }
+                                                         const double* __restrict__ Wf, const int* __restrict__ info) {
   if (*info != 0) return;
   const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -869,13 +599,13 @@ __global__ __launch_bounds__(128) void chol_panel_kernel(double* __restrict__ A,
 // One workgroup per lower tile of A22 (t tiles a side, t(t+1)/2 workgroups): workgroup 0 is the diagonal
 // tile (0, 0), workgroups 1 .. t−1 the tiles (m, 0) below it — the next step's panel rows — and the rest
 // the tiles (m, n), 1 ≤ n ≤ m, in row order.
-// FUSE (round 3): the workgroups of the tiles (m, 0) keep their updated tile in LDS, wait for the
+// The workgroups of the tiles (m, 0) keep their updated tile in LDS, wait for the
 // diagonal workgroup to publish W_{k+1} = L_{k+1,k+1}⁻¹ (flags[step], set after the fragments are in the
 // workspace) and form the next step's panel rows L21 = A21 · Wᵀ themselves, so a step is one launch:
 // the panel's own launch (≈ 5 µs plus a launch gap per step at N = 3000) leaves the chain.  Workgroup 0
 // is dispatched first (in-order dispatch); the wait is bounded all the same (spin_limit polls, then
 // info = kCholSpinFault and the workgroup finishes), so a waiting workgroup can never hang the grid.
-// The fused step's hand-off of W_{k+1} (chol_update_kernel<FUSE>): the diagonal workgroup stores the fragments
+// The hand-off of W_{k+1}: the diagonal workgroup stores the fragments
 // with agent-scope relaxed atomics (wf_store: sc1, coherent across the XCDs' L2s), waits for all of them (vmcnt 0)
 // and sets the flag; a waiting workgroup polls the flag (relaxed), passes a barrier and reads the fragments with
 // wf_load.  The compiler fences (signal fences) keep the fragment accesses on their side of the flag; the
@@ -923,8 +653,10 @@ __device__ __forceinline__ void chol_tile_of(int b, int t, int& mt, int& nt) {
   nt = q - mp * (mp + 1) / 2 + 1;
 }
 
-// BLK: the diagonal workgroup runs chol64_blocked (round 4, the default) instead of round 3's strip factor
-template <bool FUSE, bool BLK>
+// LDS of a chol_update_kernel workgroup, in doubles: the GEMM's As and Bs, the diagonal workgroup's D (kNB × kDP) or
+// a panel workgroup's updated tile (each 4,224); 4,608 keeps the footprint the kernel was measured with
+constexpr int kUpdLdsDoubles = 4 * kNB * 18;
+
 __global__ __launch_bounds__(256, 3) void chol_update_kernel(double* __restrict__ A, int64_t N, int64_t lda, int step,
                                                           int t, double* __restrict__ ws, int* __restrict__ info,
                                                           int* __restrict__ flags, int spin_limit, int acq_rel,
@@ -940,108 +672,79 @@ __global__ __launch_bounds__(256, 3) void chol_update_kernel(double* __restrict_
   const int64_t r0 = c0 + kNB;                              // first row / column of A22
   const int64_t M = N - r0;
   const int64_t m0 = (int64_t)mt * kGT, n0 = (int64_t)nt * kGT;
-  // one array: the GEMM's As and Bs, then (the diagonal workgroup) the 64 × 65 staging tile D, then
-  // the factorisation's Lb
-  static_assert(2 * 2 * kGK * kGP <= kLbDoubles && kNB * (kNB + 1) <= kLbDoubles, "LDS carve-up");
-  __shared__ __attribute__((aligned(16))) double smem[kLbDoubles];
-  __shared__ double aux[kCholAux];
-  __shared__ int prog[8];   // column progress per sub-block | W_bb published
+  // one array: the GEMM's As and Bs, or (the diagonal workgroup) chol64_blocked's D
+  static_assert(2 * 2 * kGK * kGP <= kUpdLdsDoubles && kNB * kDP <= kUpdLdsDoubles, "LDS carve-up");
+  __shared__ __attribute__((aligned(16))) double smem[kUpdLdsDoubles];
   auto& As = *reinterpret_cast<double (*)[2][kGK][kGP]>(smem);                      // As[buf][k][m] = L21(m0 + m, k0 + k)
   auto& Bs = *reinterpret_cast<double (*)[2][kGK][kGP]>(smem + 2 * kGK * kGP);      // Bs[buf][k][n] = L21(n0 + n, k0 + k)
-  __shared__ int bad_lds[1];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const double* L21 = A + r0 * lda + c0;
-  if constexpr (BLK) {
-    // round 4: the next diagonal block factored by tiles of 16 (chol64_blocked), its product with the panel
-    // formed by the waves that own the tiles
-    if (mt == 0 && nt == 0) {
-      __shared__ __attribute__((aligned(16))) double Wl[4 * kWlP];
-      __shared__ int fl[kBlkFlags];
-      if (tid < kBlkFlags) fl[tid] = 0;
-      __syncthreads();
-      chol64_blocked<kCholDOuter>(A, lda, r0, (int)(M < kNB ? M : kNB), c0, ws, smem, Wl, fl);
-      __syncthreads();
-      if (tid == 0 && (fl[20] || fl[21])) atomicCAS(info, 0, fl[21] ? kCholSpinFault : (int)(r0 + fl[20]));
-      OMB_CHOL_STRACE(step, 1, tid == 0);
-      if constexpr (FUSE) chol_publish_w(flags + step, tid, acq_rel);
-      OMB_CHOL_STRACE(step, 2, tid == 0);
-      return;
-    }
-  }
-  // the next diagonal block (A22's first tile) belongs to workgroup (0, 0)
-  if (!(mt == 0 && nt == 0)) {
-    double ra[4], rb[4];
-    auto fetch = [&](int k0) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int idx = tid + 256 * e;
-        const int am = idx >> 4, ak = idx & 15;
-        ra[e] = (m0 + am < M) ? L21[(m0 + am) * lda + k0 + ak] : 0.0;
-        rb[e] = (n0 + am < M) ? L21[(n0 + am) * lda + k0 + ak] : 0.0;
-      }
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int idx = tid + 256 * e;
-        As[buf][idx & 15][idx >> 4] = ra[e];
-        Bs[buf][idx & 15][idx >> 4] = rb[e];
-      }
-    };
-    d4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
-    fetch(0);
-    stash(0);
+  // the next diagonal block (A22's first tile) belongs to workgroup (0, 0): factored by tiles of 16 (chol64_blocked),
+  // its product with the panel formed by the waves that own the tiles
+  if (mt == 0 && nt == 0) {
+    __shared__ __attribute__((aligned(16))) double Wl[4 * kWlP];
+    __shared__ int fl[kBlkFlags];
+    if (tid < kBlkFlags) fl[tid] = 0;
     __syncthreads();
-    int buf = 0;
+    chol64_blocked<kCholDOuter>(A, lda, r0, (int)(M < kNB ? M : kNB), c0, ws, smem, Wl, fl);
+    __syncthreads();
+    if (tid == 0 && (fl[20] || fl[21])) atomicCAS(info, 0, fl[21] ? kCholSpinFault : (int)(r0 + fl[20]));
+    OMB_CHOL_STRACE(step, 1, tid == 0);
+    chol_publish_w(flags + step, tid, acq_rel);
+    OMB_CHOL_STRACE(step, 2, tid == 0);
+    return;
+  }
+  double ra[4], rb[4];
+  auto fetch = [&](int k0) {
 #pragma unroll
-    for (int k0 = 0; k0 < kNB; k0 += kGK) {
-      const bool more = k0 + kGK < kNB;
-      if (more) fetch(k0 + kGK);
-#pragma unroll
-      for (int ks = 0; ks < kGK / 4; ++ks) {
-        const int kk = 4 * ks + (lane >> 4);
-        const double a0 = As[buf][kk][32 * wm + (lane & 15)];
-        const double a1 = As[buf][kk][32 * wm + 16 + (lane & 15)];
-        const double b0 = Bs[buf][kk][32 * wn + (lane & 15)];
-        const double b1 = Bs[buf][kk][32 * wn + 16 + (lane & 15)];
-        acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-      }
-      if (more) stash(buf ^ 1);
-      __syncthreads();
-      buf ^= 1;
+    for (int e = 0; e < 4; ++e) {
+      const int idx = tid + 256 * e;
+      const int am = idx >> 4, ak = idx & 15;
+      ra[e] = (m0 + am < M) ? L21[(m0 + am) * lda + k0 + ak] : 0.0;
+      rb[e] = (n0 + am < M) ? L21[(n0 + am) * lda + k0 + ak] : 0.0;
     }
-    // C/D map of v_mfma_f64_16x16x4f64: col = lane & 15, row = (lane >> 4) + 4·i
-    if (!FUSE || nt != 0) {
+  };
+  auto stash = [&](int buf) {
 #pragma unroll
-      for (int rb2 = 0; rb2 < 2; ++rb2)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int lr = 32 * wm + 16 * rb2 + (lane >> 4) + 4 * i;
-            const int lc = 32 * wn + 16 * cb + (lane & 15);
-            const int64_t row = m0 + lr, col_g = n0 + lc;
-            if (row < M && col_g < M && col_g <= row) {
-              double* p = A + (r0 + row) * lda + r0 + col_g;
-              *p = *p - acc[rb2][cb][i];
-            }
-          }
-      return;
+    for (int e = 0; e < 4; ++e) {
+      const int idx = tid + 256 * e;
+      As[buf][idx & 15][idx >> 4] = ra[e];
+      Bs[buf][idx & 15][idx >> 4] = rb[e];
     }
-    // FUSE, tile (m, 0): the updated tile (the next step's A21 rows) into LDS, D[lr·kPD + lc]; the
-    // GEMM loop ended on a barrier, so As/Bs are free
-    constexpr int kPD = kNB + 2;                              // 528-B rows: 16 lanes' b128 reads of 16 rows conflict-free
-    static_assert(kNB * kPD <= kLbDoubles, "LDS carve-up");
-    double* Dp = smem;
+  };
+  d4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
+  fetch(0);
+  stash(0);
+  __syncthreads();
+  int buf = 0;
+#pragma unroll
+  for (int k0 = 0; k0 < kNB; k0 += kGK) {
+    const bool more = k0 + kGK < kNB;
+    if (more) fetch(k0 + kGK);
+#pragma unroll
+    for (int ks = 0; ks < kGK / 4; ++ks) {
+      const int kk = 4 * ks + (lane >> 4);
+      const double a0 = As[buf][kk][32 * wm + (lane & 15)];
+      const double a1 = As[buf][kk][32 * wm + 16 + (lane & 15)];
+      const double b0 = Bs[buf][kk][32 * wn + (lane & 15)];
+      const double b1 = Bs[buf][kk][32 * wn + 16 + (lane & 15)];
+      acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+    }
+    if (more) stash(buf ^ 1);
+    __syncthreads();
+    buf ^= 1;
+  }
+  // C/D map of v_mfma_f64_16x16x4f64: col = lane & 15, row = (lane >> 4) + 4·i
+  if (nt != 0) {
 #pragma unroll
     for (int rb2 = 0; rb2 < 2; ++rb2)
 #pragma unroll
@@ -1050,117 +753,66 @@ __global__ __launch_bounds__(256, 3) void chol_update_kernel(double* __restrict_
         for (int i = 0; i < 4; ++i) {
           const int lr = 32 * wm + 16 * rb2 + (lane >> 4) + 4 * i;
           const int lc = 32 * wn + 16 * cb + (lane & 15);
-          const int64_t row = m0 + lr;
-          Dp[lr * kPD + lc] = (row < M) ? A[(r0 + row) * lda + r0 + lc] - acc[rb2][cb][i] : 0.0;
+          const int64_t row = m0 + lr, col_g = n0 + lc;
+          if (row < M && col_g < M && col_g <= row) {
+            double* p = A + (r0 + row) * lda + r0 + col_g;
+            *p = *p - acc[rb2][cb][i];
+          }
         }
-    __syncthreads();
-    // W_{k+1}'s fragments: wait for the diagonal workgroup's flag (bounded); relaxed polls and coherent
-    // fragment loads (wf_load), no cache-wide invalidate
-    OMB_CHOL_STRACE(step, 4, tid == 0 && mt == 1);
-    chol_wait_w(flags + step, tid, spin_limit, info, acq_rel);
-    OMB_CHOL_STRACE(step, 5, tid == 0 && mt == 1);
-    // the next step's panel rows, as chol_panel_kernel: wave w → rows 16w + (lane & 15) of the tile,
-    // all four output column blocks
-    {
-      const int c = lane & 15, g = lane >> 4;
-      double x[16];                                           // x[4sg + u] = D[16w + c][16sg + 4g + u]
-      const double* dr = Dp + (16 * wave + c) * kPD + 4 * g;
-#pragma unroll
-      for (int sg = 0; sg < 4; ++sg) {
-        const double2 v0 = reinterpret_cast<const double2*>(dr + 16 * sg)[0];
-        const double2 v1 = reinterpret_cast<const double2*>(dr + 16 * sg)[1];
-        x[4 * sg] = v0.x;
-        x[4 * sg + 1] = v0.y;
-        x[4 * sg + 2] = v1.x;
-        x[4 * sg + 3] = v1.y;
-      }
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb) {
-        const double* wf = ws + jb * 16 * 64 + lane;
-        d4 pa = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int s2 = 0; s2 < 16; ++s2)
-          if (s2 < 4 * (jb + 1)) pa = __builtin_amdgcn_mfma_f64_16x16x4f64(x[s2], wf_load(wf + s2 * 64), pa, 0, 0, 0);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int64_t orow = m0 + 16 * wave + 4 * e + g;
-          if (orow < M) A[(r0 + orow) * lda + r0 + 16 * jb + c] = pa[e];
-        }
-      }
-    }
-    OMB_CHOL_STRACE(step, 6, tid == 0 && mt == 1);
     return;
   }
-  // Diagonal workgroup: the tile's 64 L21 rows and its A22 values are loaded at once (one load latency
-  // instead of one per 16-column slab of the pipeline above), the product runs from one LDS copy
-  // (A and B are the same rows), and D = A22 − L21 L21ᵀ is formed in place for the factorisation.
-  double* D = smem;                                          // 64 × 65: first T[k·65 + m] = L21(m, k), then D
+  // tile (m, 0): the updated tile (the next step's A21 rows) into LDS, D[lr·kPD + lc]; the
+  // GEMM loop ended on a barrier, so As/Bs are free
+  constexpr int kPD = kNB + 2;                              // 528-B rows: 16 lanes' b128 reads of 16 rows conflict-free
+  static_assert(kNB * kPD <= kUpdLdsDoubles, "LDS carve-up");
+  double* Dp = smem;
+#pragma unroll
+  for (int rb2 = 0; rb2 < 2; ++rb2)
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int lr = 32 * wm + 16 * rb2 + (lane >> 4) + 4 * i;
+        const int lc = 32 * wn + 16 * cb + (lane & 15);
+        const int64_t row = m0 + lr;
+        Dp[lr * kPD + lc] = (row < M) ? A[(r0 + row) * lda + r0 + lc] - acc[rb2][cb][i] : 0.0;
+      }
+  __syncthreads();
+  // W_{k+1}'s fragments: wait for the diagonal workgroup's flag (bounded); relaxed polls and coherent
+  // fragment loads (wf_load), no cache-wide invalidate
+  OMB_CHOL_STRACE(step, 4, tid == 0 && mt == 1);
+  chol_wait_w(flags + step, tid, spin_limit, info, acq_rel);
+  OMB_CHOL_STRACE(step, 5, tid == 0 && mt == 1);
+  // the next step's panel rows, as chol_panel_kernel: wave w → rows 16w + (lane & 15) of the tile,
+  // all four output column blocks
   {
-    double lv[16], av[16];
+    const int c = lane & 15, g = lane >> 4;
+    double x[16];                                           // x[4sg + u] = D[16w + c][16sg + 4g + u]
+    const double* dr = Dp + (16 * wave + c) * kPD + 4 * g;
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int idx = tid + 256 * e, m = idx >> 6, k = idx & 63;
-      lv[e] = (m < M) ? L21[m * lda + k] : 0.0;
-      av[e] = (m < M && k <= m) ? A[(r0 + m) * lda + r0 + k] : 0.0;
+    for (int sg = 0; sg < 4; ++sg) {
+      const double2 v0 = reinterpret_cast<const double2*>(dr + 16 * sg)[0];
+      const double2 v1 = reinterpret_cast<const double2*>(dr + 16 * sg)[1];
+      x[4 * sg] = v0.x;
+      x[4 * sg + 1] = v0.y;
+      x[4 * sg + 2] = v1.x;
+      x[4 * sg + 3] = v1.y;
     }
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int idx = tid + 256 * e;
-      D[(idx & 63) * 65 + (idx >> 6)] = lv[e];
-    }
-    __syncthreads();
-    d4 acc[2][2];
+    for (int jb = 0; jb < 4; ++jb) {
+      const double* wf = ws + jb * 16 * 64 + lane;
+      d4 pa = d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+      for (int s2 = 0; s2 < 16; ++s2)
+        if (s2 < 4 * (jb + 1)) pa = __builtin_amdgcn_mfma_f64_16x16x4f64(x[s2], wf_load(wf + s2 * 64), pa, 0, 0, 0);
 #pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = d4{0.0, 0.0, 0.0, 0.0};
-    if (wm >= wn) {                                          // the upper-right quadrant is not needed
-#pragma unroll
-      for (int ks = 0; ks < kNB / 4; ++ks) {
-        const int kk = 4 * ks + (lane >> 4);
-        const double a0 = D[kk * 65 + 32 * wm + (lane & 15)];
-        const double a1 = D[kk * 65 + 32 * wm + 16 + (lane & 15)];
-        const double b0 = D[kk * 65 + 32 * wn + (lane & 15)];
-        const double b1 = D[kk * 65 + 32 * wn + 16 + (lane & 15)];
-        acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+      for (int e = 0; e < 4; ++e) {
+        const int64_t orow = m0 + 16 * wave + 4 * e + g;
+        if (orow < M) A[(r0 + orow) * lda + r0 + 16 * jb + c] = pa[e];
       }
     }
-    __syncthreads();                                         // T consumed
-    if (wm >= wn) {
-#pragma unroll
-      for (int rb2 = 0; rb2 < 2; ++rb2)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            D[(32 * wm + 16 * rb2 + (lane >> 4) + 4 * i) * 65 + 32 * wn + 16 * cb + (lane & 15)] = acc[rb2][cb][i];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int idx = tid + 256 * e, m = idx >> 6, k = idx & 63;
-      if (k <= m) D[m * 65 + k] = av[e] - D[m * 65 + k];
-    }
   }
-  __syncthreads();
-  const int nb = (int)(M < kNB ? M : kNB);
-  const int r = lane, w = wave;
-  double a[16];
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int c = 16 * w + q;
-    a[q] = (r < nb && c <= r) ? D[r * 65 + c] : (c == r ? 1.0 : 0.0);
-  }
-  if (tid == 0) bad_lds[0] = 0;
-  if (tid < 8) prog[tid] = 0;
-  __syncthreads();                                           // D consumed: smem becomes Lb
-  chol64_factor(a, w, r, nb, smem, aux, prog, bad_lds, A, lda, r0, ws);   // with W = L⁻¹ (chol64_inverse)
-  __syncthreads();
-  if (tid == 0 && bad_lds[0]) atomicCAS(info, 0, (int)(r0 + bad_lds[0]));
-  if constexpr (FUSE) chol_publish_w(flags + step, tid, acq_rel);
+  OMB_CHOL_STRACE(step, 6, tid == 0 && mt == 1);
 }
 
 // ----------------------------------------------------------------------------- Cholesky, one persistent launch
@@ -1232,8 +884,7 @@ struct CholSync {
   int* cnt;     // [t·t]    updates applied to tile (i, j)
   int* ticket;  // task counter of the worker workgroups
   int* abort;   // set by the first wait that runs out
-  const int* tab;   // the workers' tasks in order, (code, steps) pairs (chol_task_table), or null for the
-                    // step-major arithmetic order
+  const int* tab;   // the workers' tasks in order, (code, steps) pairs (chol_task_table)
 };
 
 // Wave 0 waits (every lane of it, on wave-uniform values) until *p ≥ v: relaxed polls; false after an abort or
@@ -1489,32 +1140,17 @@ __device__ __forceinline__ void chol_dma_tile(const double* __restrict__ src, in
   }
 }
 
-// bulk tasks of step k (see above): P(i, k) for i = k+2 .. t−1, then the update tiles by columns
-// k0 > 0 (chol_persist_kernel after k0 per-step launches): step k0's panel column is already in A, so step k0 has
-// only its update tasks
-__host__ __device__ __forceinline__ int chol_persist_np(int t, int k, int k0) {
-  return (k0 > 0 && k == k0) ? 0 : (t - k - 2 > 0 ? t - k - 2 : 0);
-}
-__host__ __device__ __forceinline__ int chol_persist_step_tasks(int t, int k, int k0 = 0) {
-  const int m = t - k - 1;
-  const int nu = m > 1 ? m * (m + 1) / 2 - 1 : 0;
-  return chol_persist_np(t, k, k0) + nu;
-}
-
-// The sync words of one persistent launch: all zero, except (k0 > 0) the state the per-step launches leave — step
-// k0's panel tiles published (pflag(i, k0) = 4) and every trailing tile updated through step k0 − 1 (cnt = k0).
-// One launch in place of a memset; k0 = 0 also zeroes info (the per-step path's first kernel does that otherwise).
-__global__ __launch_bounds__(256) void chol_persist_init_kernel(int* __restrict__ ints, int t, int k0,
-                                                                int* __restrict__ info) {
-  const int n = t + 2 * t * t + 2;
-  for (int x = threadIdx.x; x < n; x += 256) ints[x] = chol_persist_init_word(x, t, k0);
-  if (threadIdx.x == 0 && k0 == 0) *info = 0;
+// The sync words of one persistent launch (n = t + 2t² + 2, chol_persist_sync_words) and info: all zero.  One launch
+// in place of two memsets.
+__global__ __launch_bounds__(256) void chol_persist_init_kernel(int* __restrict__ ints, int n, int* __restrict__ info) {
+  for (int x = threadIdx.x; x < n; x += 256) ints[x] = 0;
+  if (threadIdx.x == 0) *info = 0;
 }
 
 template <bool AR>
 __global__ __launch_bounds__(256, kPersistWgPerCu) void chol_persist_kernel(double* __restrict__ A, int64_t N, int64_t lda, int t,
                                                               int total, double* __restrict__ Wf, CholSync sync,
-                                                              int* __restrict__ info, int spin_limit, int k0) {
+                                                              int* __restrict__ info, int spin_limit) {
   __shared__ __attribute__((aligned(16))) double Ds[kNB * kDP];
   __shared__ __attribute__((aligned(16))) double Lp[kNB * kDP];
   __shared__ __attribute__((aligned(16))) double Wl[4 * kWlP];
@@ -1540,17 +1176,7 @@ __global__ __launch_bounds__(256, kPersistWgPerCu) void chol_persist_kernel(doub
                                                              : (row == col ? 1.0 : 0.0);
         }
     };
-    // k0 > 0: the per-step launches factored blocks 0 .. k0 and formed panel column k0; the walk starts at k0 + 1
-    // from the panel tile (k0 + 1, k0) in A
-    const int kstart = k0 > 0 ? k0 + 1 : 0;
-    if (kstart > 0) {
-      const int64_t rb = (int64_t)kstart * kNB, cb = (int64_t)k0 * kNB;
-      for (int x = tid; x < kNB * kNB; x += 256) {
-        const int r = x >> 6, cc = x & 63;
-        Lp[r * kDP + cc] = rb + r < N ? ld_sc1(A + (rb + r) * lda + cb + cc) : 0.0;
-      }
-    }
-    load_av(kstart);
+    load_av(0);
     if (tid < kBlkFlags) fl[tid] = 0;
     // Round 6: the next panel tile and the next diagonal tile reach the walker through LDS (chol_dma_tile: all four
     // waves, direct-to-LDS) and the panel product reads them there — one load latency for both tiles instead of the
@@ -1558,7 +1184,7 @@ __global__ __launch_bounds__(256, kPersistWgPerCu) void chol_persist_kernel(doub
     // the copies 1.0 → 2.2 µs; N = 3000 0.911-0.922 → 0.895-0.900 ms, profiles/r06_aa_*)
     const bool aligned = (lda & 1) == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0;
     __syncthreads();
-    for (int k = kstart; k < t; ++k) {
+    for (int k = 0; k < t; ++k) {
       OMB_PDBG(0, 1000 * k + 1);
       OMB_PTIME(8 * k + 0);
       const int64_t r0 = (int64_t)k * kNB;
@@ -1588,7 +1214,7 @@ __global__ __launch_bounds__(256, kPersistWgPerCu) void chol_persist_kernel(doub
           }
         }
       }
-      if (k > kstart && w >= 2) {   // the previous step's panel tile (k, k − 1): this wave's rows drained, its share
+      if (k > 0 && w >= 2) {   // the previous step's panel tile (k, k − 1): this wave's rows drained, its share
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if constexpr (AR)
           __hip_atomic_fetch_add(sync.pflag + k * t + k - 1, lane == 0 ? 2 : 0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
@@ -1677,43 +1303,21 @@ __global__ __launch_bounds__(256, kPersistWgPerCu) void chol_persist_kernel(doub
     // read as a wave-uniform value: loaded per lane, the compiler treats every branch on q as divergent and
     // restructures the loop around the barriers below (it sank the flag stores out of the task code, and the
     // launch hung at N = 130, gpurun_out/r04_o)
-    int q = __builtin_amdgcn_readfirstlane(s_task[0]);
+    const int q = __builtin_amdgcn_readfirstlane(s_task[0]);
     OMB_PDBG(8 * blockIdx.x, q + 1);
     OMB_PTIME(8 * t + 4 * q);
     if (q >= total) {
       OMB_PDBG(8 * blockIdx.x + 1, 99);
       return;
     }
-    // the task: from the table (round 5, lookahead order) or the step-major arithmetic order
-    int k = k0, i = 0, j = 0, nb = 1;
-    bool panel;
-    if (sync.tab) {
-      const int e = __builtin_amdgcn_readfirstlane(sync.tab[2 * q]);
-      nb = __builtin_amdgcn_readfirstlane(sync.tab[2 * q + 1]);
-      panel = (e >> 30) == 0;
-      k = (e >> 20) & 1023;
-      i = (e >> 10) & 1023;
-      j = e & 1023;
-    } else {
-      for (; k < t; ++k) {
-        const int nk = chol_persist_step_tasks(t, k, k0);
-        if (q < nk) break;
-        q -= nk;
-      }
-      const int np = chol_persist_np(t, k, k0);
-      panel = q < np;
-      if (panel) {
-        i = k + 2 + q;
-      } else {
-        int u = q - np + 1;                                     // + 1: (k+1, k+1) is the diagonal workgroup's
-        j = k + 1;
-        while (u >= t - j) {
-          u -= t - j;
-          ++j;
-        }
-        i = j + u;
-      }
-    }
+    // the task, from the table (chol_task_table: panel flag, k, i, j in 10-bit fields, and its number of steps)
+    const int e = __builtin_amdgcn_readfirstlane(sync.tab[2 * q]);
+    const int nb = __builtin_amdgcn_readfirstlane(sync.tab[2 * q + 1]);
+    const bool panel = (e >> 30) == 0;
+    int k = (e >> 20) & 1023, i = (e >> 10) & 1023, j = e & 1023;
+    // opaque from here on: knowing k, i, j < 1024 the compiler narrows the task bodies' address arithmetic and then
+    // issues the single-step update's A-tile loads behind its panel loads — N = 5000 2.42 against 2.39-2.40 ms
+    asm("" : "+s"(k), "+s"(i), "+s"(j));
     if (panel) {
       if (w == 0 && chol_poll_ge<AR>(sync.wflag + k, 1, sync, spin_limit, info))
         chol_poll_ge<AR>(sync.cnt + i * t + k, k, sync, spin_limit, info);
@@ -2851,7 +2455,7 @@ int64_t chol_ws_doubles(int64_t N) {
   return launches > persist ? launches : persist;
 }
 
-// The persistent launch's sync words inside ws (chol_persist_kernel's layout; all zero before a k0 = 0 launch, which
+// The persistent launch's sync words inside ws (chol_persist_kernel's layout; all zero before the launch, which
 // chol_persist_init_kernel or, in the Thompson chain, the covariance SYRK writes)
 int chol_persist_sync_words(double* ws, int64_t N, int** ints) {
   const int t = (int)((N + kNB - 1) / kNB);
@@ -2859,20 +2463,14 @@ int chol_persist_sync_words(double* ws, int64_t N, int** ints) {
   return t + 2 * t * t + 2;
 }
 
-struct CholPersistInit {
-  int* ints = nullptr;   // the persistent launch's sync words (nullptr: none to write)
-  int t = 0, k0 = 0;
-};
 static hipError_t chol_panel(hipStream_t stream, double* A, int64_t N, int64_t lda, int k, const double* ws,
-                             const int* info, bool vec, CholPersistInit pi = {}) {
+                             const int* info, bool vec) {
   const int64_t rest = N - (int64_t)(k + 1) * kNB;          // rows below the diagonal block
   const unsigned pblocks = (unsigned)((rest + 15) / 16);
   if (vec)
-    hipLaunchKernelGGL((chol_panel_kernel<true>), dim3(pblocks), dim3(128), 0, stream, A, N, lda, k, ws, info, pi.ints,
-                       pi.t, pi.k0);
+    hipLaunchKernelGGL((chol_panel_kernel<true>), dim3(pblocks), dim3(128), 0, stream, A, N, lda, k, ws, info);
   else
-    hipLaunchKernelGGL((chol_panel_kernel<false>), dim3(pblocks), dim3(128), 0, stream, A, N, lda, k, ws, info, pi.ints,
-                       pi.t, pi.k0);
+    hipLaunchKernelGGL((chol_panel_kernel<false>), dim3(pblocks), dim3(128), 0, stream, A, N, lda, k, ws, info);
   return hipGetLastError();
 }
 
@@ -2888,12 +2486,11 @@ constexpr size_t g_chol_update_lds = 0;
 constexpr int g_chol_update_delay = 0;
 #endif
 
-// Round 4: the diagonal blocks by tiles of 16 (chol64_blocked), one launch per step with the next panel inside.
+// The per-step schedule: the diagonal blocks by tiles of 16 (chol64_blocked), one launch per step with the next panel
+// inside.  The first kernel zeroes info and the steps' flags.
 static hipError_t launch_cholesky_blocked(hipStream_t stream, double* A, int64_t N, int64_t lda, int* info, double* ws,
-                                          int spin_limit, int acq_rel, int steps_limit, CholPersistInit pi) {
-  int steps = (int)((N + kNB - 1) / kNB);
-  // steps_limit k0 ≥ 1: only the launches that factor blocks 0 .. k0 and form panel columns 0 .. k0
-  if (steps_limit > 0 && steps_limit + 1 < steps) steps = steps_limit + 1;
+                                          int spin_limit, int acq_rel) {
+  const int steps = (int)((N + kNB - 1) / kNB);
   const bool vec = (lda % 2 == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0);
   int* flags = reinterpret_cast<int*>(ws + kCholWsDoubles);
   hipLaunchKernelGGL(chol_diag_blk_kernel, dim3(1), dim3(256), 0, stream, A, N, lda, ws, info, flags, steps);
@@ -2902,37 +2499,20 @@ static hipError_t launch_cholesky_blocked(hipStream_t stream, double* A, int64_t
     const int64_t rest = N - (int64_t)(k + 1) * kNB;
     const int t = (int)((rest + kGT - 1) / kGT);
     if (k == 0) {
-      e = chol_panel(stream, A, N, lda, k, ws, info, vec, pi);
+      e = chol_panel(stream, A, N, lda, k, ws, info, vec);
       if (e != hipSuccess) break;
     }
-    hipLaunchKernelGGL((chol_update_kernel<true, true>), dim3((unsigned)(t * (t + 1) / 2)), dim3(256), g_chol_update_lds,
+    hipLaunchKernelGGL(chol_update_kernel, dim3((unsigned)(t * (t + 1) / 2)), dim3(256), g_chol_update_lds,
                        stream, A, N, lda, k, t, ws, info, flags, spin_limit, acq_rel, g_chol_update_delay);
     e = hipGetLastError();
   }
   return e;
 }
 
-// Per-step launches before the persistent one (k0, launch_cholesky_persist); tools/ablate sets it, the library
-// picks it from the number of 64-column steps t.
-#ifdef OMB_TOOLS_KNOBS
-static int g_chol_hybrid_k0 = -1;
-void set_chol_hybrid_k0(int k0) { g_chol_hybrid_k0 = k0; }
-#else
-constexpr int g_chol_hybrid_k0 = -1;
-#endif
-// Rounds 4-5: the persistent launch's trailing updates kept up with the walk only once ≤ ≈ 32 block columns remained,
-// so the first t − 32 steps ran as per-step launches (three workgroups per CU, LDS-staged).  Round 6: with the far
-// tiles' updates batched (chol_task_table) the persistent launch alone is the fastest schedule at every size measured
-// (GPU time, tools/ablate/chol_hybrid_sweep): N = 3000 0.910 ms (round 5's hybrid 0.98, per-step 1.10), 5000 2.358
-// (2.48, 2.56), 6500 4.55-4.69 for every k0 (per-step 4.68), 8000 7.38 (k0 = 16 … 93: 7.75-7.89, per-step 7.90;
-// profiles/r06_d_chol_sweep.txt, r06_e_chol_sweep.txt, r06_f_chol_sweep_large_n.txt).  The per-step prefix stays
-// available to the tools (k0 > 0).
-static int chol_hybrid_k0(int t) {
-  (void)t;
-  return g_chol_hybrid_k0 >= 0 ? g_chol_hybrid_k0 : 0;
-}
-
-// Round 4: one persistent launch (chol_persist_kernel), kPersistWgPerCu workgroups per CU.
+// One persistent launch (chol_persist_kernel), kPersistWgPerCu workgroups per CU.  With the far tiles' updates
+// batched (chol_task_table) it is the fastest schedule at every size measured (GPU time,
+// tools/ablate/chol_hybrid_sweep): N = 3000 0.910 ms (per-step 1.10), 5000 2.358 (2.56), 6500 4.55-4.69 (4.68), 8000
+// 7.38 (7.90; profiles/r06_d_chol_sweep.txt, r06_e_chol_sweep.txt, r06_f_chol_sweep_large_n.txt).
 static int device_cus() {
   static int cus[64] = {0};
   int dev = 0;
@@ -2949,10 +2529,7 @@ static bool chol_persist_fits(int64_t N, int64_t lda) {
   return ((N + kNB) * lda + kNB) * 8 < 0x7fffffff;   // 32-bit buffer offsets (rows past N included)
 }
 
-static hipError_t launch_cholesky_blocked(hipStream_t stream, double* A, int64_t N, int64_t lda, int* info, double* ws,
-                                          int spin_limit, int acq_rel, int steps_limit = -1, CholPersistInit pi = {});
-
-// Round 5: the persistent launch's task order.  Step-major tickets put step k's critical tasks (its panel tiles, the
+// The persistent launch's task order.  Step-major tickets put step k's critical tasks (its panel tiles, the
 // next column's updates) behind every far-column update of step k − 1, and the diagonal walk waited for them.  Here
 // the host sorts the tasks by
 //     P(i, k): (k + 1, k, 0, ·, i)        U(i, j, k): (min(j, k + L), k, 1, j, i)
@@ -2960,11 +2537,11 @@ static hipError_t launch_cholesky_blocked(hipStream_t stream, double* A, int64_t
 // panel needs them).  Every task's inputs (U(i, j, k − 1), P(i, k), P(j, k); P(i, k)'s U(i, k, k − 1)) sort before
 // it, and everything the walk waits for at step k (tiles (k + 1, k), (k + 1, k + 1) through step k − 1) sorts before
 // every task that needs W_k, so the order stays topological and the grid needs no co-residency.  The table (per task
-// the code — panel flag, k, i, j in 10-bit fields — and its number of steps) is built once per (device, t, k0, L,
+// the code — panel flag, k, i, j in 10-bit fields — and its number of steps) is built once per (device, t, L,
 // batch, window) and kept.
 #ifdef OMB_TOOLS_KNOBS
 static int g_chol_lookahead = -1;
-void set_chol_lookahead(int L) { g_chol_lookahead = L; }
+void set_chol_lookahead(int L) { g_chol_lookahead = L == 0 ? 1 : L; }   // L ≥ 1 (negative: the default)
 #else
 constexpr int g_chol_lookahead = -1;
 #endif
@@ -2972,14 +2549,14 @@ constexpr int g_chol_lookahead = -1;
 // 2.403 ms (tools/ablate/chol_hybrid_sweep, profiles/r06_e_chol_sweep.txt)
 constexpr int kCholLookahead = 2;
 
-// Round 6: far tiles take their updates in batches (chol_persist_update_batch).  Tile (i, j)'s worker steps are
-// [k0, e) — e = j below the diagonal, i − 1 on it (the walker applies step i − 1 to its own D); the last `window`
+// Far tiles take their updates in batches (chol_persist_update_batch).  Tile (i, j)'s worker steps are
+// [0, e) — e = j below the diagonal, i − 1 on it (the walker applies step i − 1 to its own D); the last `window`
 // steps before e (the ones the walk is about to need) stay single tasks, the earlier ones go in batches of up to
 // `batch` steps aligned to multiples of `batch`.  A batch [ka, kb) sorts as its last step's update would,
 // (min(j, kb − 1 + L), kb − 1, 1, j, i): its inputs — the panels of its steps, the tile's previous batch — still sort
 // before it, and a tile the walk waits for at step k (its last worker step k − 1, inside the window) is a single
 // task sorting before every task that needs W_k, so the order stays topological.  The entries are pairs (code,
-// steps); batch 1 is round 5's table.
+// steps); batch 1 (single_steps) makes every update its own task.
 #ifdef OMB_TOOLS_KNOBS
 static int g_chol_batch = -1, g_chol_window = -1;
 void set_chol_batch(int batch, int window) {
@@ -2995,18 +2572,19 @@ constexpr int kCholBatch = 16;
 constexpr int kCholWindow = 4;
 
 struct CholTaskTab {
-  int dev, t, k0, L, batch, window, total;
+  int dev, t, L, batch, window, total;
   int* d;
 };
 
-static const int* chol_task_table(int t, int k0, int L, int batch, int window, int* total_out) {
+// The device table and its number of tasks, or nullptr (no table: the caller takes the per-step schedule).
+static const int* chol_task_table(int t, int L, int batch, int window, int* total_out) {
   static std::mutex mu;
   static std::vector<CholTaskTab> tabs;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || t > 1024 || batch < 1 || batch > 32) return nullptr;
+  if (hipGetDevice(&dev) != hipSuccess || t > 1024 || L < 1 || batch < 1 || batch > 32) return nullptr;
   std::lock_guard<std::mutex> lock(mu);
   for (const CholTaskTab& e : tabs)
-    if (e.dev == dev && e.t == t && e.k0 == k0 && e.L == L && e.batch == batch && e.window == window) {
+    if (e.dev == dev && e.t == t && e.L == L && e.batch == batch && e.window == window) {
       *total_out = e.total;
       return e.d;
     }
@@ -3014,18 +2592,17 @@ static const int* chol_task_table(int t, int k0, int L, int batch, int window, i
     int a, b, c, d, e, code, steps;
   };
   std::vector<Key> keys;
-  for (int k = k0; k < t; ++k)
-    if (!(k0 > 0 && k == k0))
-      for (int i = k + 2; i < t; ++i) keys.push_back({k + 1, k, 0, 0, i, (k << 20) | (i << 10), 1});
+  for (int k = 0; k < t; ++k)
+    for (int i = k + 2; i < t; ++i) keys.push_back({k + 1, k, 0, 0, i, (k << 20) | (i << 10), 1});
   auto add_update = [&](int i, int j, int ka, int kb) {   // steps [ka, kb) of tile (i, j)
     const int kl = kb - 1;
     keys.push_back({std::min(j, kl + L), kl, 1, j, i, (1 << 30) | (ka << 20) | (i << 10) | j, kb - ka});
   };
-  for (int j = k0 + 1; j < t; ++j)
+  for (int j = 1; j < t; ++j)
     for (int i = j; i < t; ++i) {
-      const int e = (i == j) ? i - 1 : j;                     // worker steps [k0, e)
-      const int near = std::max(k0, e - window);
-      for (int ka = k0; ka < near;) {                         // batches, aligned to multiples of `batch`
+      const int e = (i == j) ? i - 1 : j;                     // worker steps [0, e)
+      const int near = std::max(0, e - window);
+      for (int ka = 0; ka < near;) {                          // batches, aligned to multiples of `batch`
         const int kb = std::min(near, (ka / batch + 1) * batch);
         add_update(i, j, ka, kb);
         ka = kb;
@@ -3051,94 +2628,51 @@ static const int* chol_task_table(int t, int k0, int L, int batch, int window, i
     (void)hipFree(d);
     return nullptr;
   }
-  tabs.push_back({dev, t, k0, L, batch, window, total, d});
+  tabs.push_back({dev, t, L, batch, window, total, d});
   *total_out = total;
   return d;
 }
 
-// k0 > 0: steps 0 .. k0 − 1 as per-step launches (their bulk trailing updates run at three workgroups per CU), the
-// rest in one persistent launch (the diagonal walk without kernel boundaries once the trailing matrix is small).
+// The whole factorisation in one persistent launch.  zeroed / n_zeroed: ints that an earlier launch on the stream has
+// set to 0 together with info; the init kernel is skipped only where they are exactly this launch's sync words (a
+// launch that starts on other values spins on them until its waits run out).  Without a task table the per-step
+// schedule runs instead.
 static hipError_t launch_cholesky_persist(hipStream_t stream, double* A, int64_t N, int64_t lda, int* info, double* ws,
-                                          int spin_limit, int k0 = 0, int acq_rel = 0, int single_steps = 0,
-                                          bool sync_zeroed = false) {
+                                          int spin_limit, int acq_rel, int single_steps, const int* zeroed,
+                                          int n_zeroed) {
   const int t = (int)((N + kNB - 1) / kNB);
-  if (k0 > t - 2) k0 = 0;
-  hipError_t e = hipSuccess;
-  double* Wf = ws;
-  int* ints = reinterpret_cast<int*>(ws + (int64_t)t * kCholWsDoubles);
-  if (k0 > 0) e = launch_cholesky_blocked(stream, A, N, lda, info, ws, spin_limit, acq_rel, k0, CholPersistInit{ints, t, k0});
-  if (e != hipSuccess) return e;
-  int total = 0;
-  for (int k = k0; k < t; ++k) total += chol_persist_step_tasks(t, k, k0);
-  const int L = g_chol_lookahead >= 0 ? g_chol_lookahead : kCholLookahead;
+  const int L = g_chol_lookahead >= 1 ? g_chol_lookahead : kCholLookahead;
   const int batch = single_steps ? 1 : (g_chol_batch >= 1 ? g_chol_batch : kCholBatch);
   const int window = g_chol_window >= 0 ? g_chol_window : kCholWindow;
-  // L = 0 (tools): the step-major arithmetic order of round 4 (single-step tasks)
-  int tab_total = 0;
-  const int* tab = L > 0 ? chol_task_table(t, k0, L, batch, window, &tab_total) : nullptr;
-  if (tab) total = tab_total;
+  int total = 0;
+  const int* tab = chol_task_table(t, L, batch, window, &total);
+  if (!tab) return launch_cholesky_blocked(stream, A, N, lda, info, ws, spin_limit, acq_rel);
+  double* Wf = ws;
+  int* ints = nullptr;
+  const int n_sync = chol_persist_sync_words(ws, N, &ints);
   CholSync sync{ints, ints + t, ints + t + t * t, ints + t + 2 * t * t, ints + t + 2 * t * t + 1, tab};
-  if (k0 == 0 && !sync_zeroed) {   // with k0 > 0 step 0's panel launch wrote the sync words
-    hipLaunchKernelGGL(chol_persist_init_kernel, dim3(1), dim3(256), 0, stream, ints, t, k0, info);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (zeroed != ints || n_zeroed != n_sync) {
+    hipLaunchKernelGGL(chol_persist_init_kernel, dim3(1), dim3(256), 0, stream, ints, n_sync, info);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
   }
   const int slots = kPersistWgPerCu * device_cus() - 1;
   const int grid = 1 + (total < slots ? total : slots);
   if (acq_rel)
     hipLaunchKernelGGL(chol_persist_kernel<true>, dim3((unsigned)grid), dim3(256), 0, stream, A, N, lda, t, total, Wf,
-                       sync, info, spin_limit, k0);
+                       sync, info, spin_limit);
   else
     hipLaunchKernelGGL(chol_persist_kernel<false>, dim3((unsigned)grid), dim3(256), 0, stream, A, N, lda, t, total, Wf,
-                       sync, info, spin_limit, k0);
+                       sync, info, spin_limit);
   return hipGetLastError();
 }
 
 hipError_t launch_cholesky_mode(hipStream_t stream, double* A, int64_t N, int64_t lda, int* info, double* ws, int mode,
-                                int spin_limit, int acq_rel, int single_steps, bool sync_zeroed) {
+                                int spin_limit, int acq_rel, int single_steps, const int* zeroed, int n_zeroed) {
   if (N <= 0) return hipSuccess;
-  if (mode == kCholAuto) mode = kCholPersistent;
-  if (mode == kCholPersistOnly) {
-    if (chol_persist_fits(N, lda))
-      return launch_cholesky_persist(stream, A, N, lda, info, ws, spin_limit, 0, acq_rel, single_steps, sync_zeroed);
-    mode = kCholBlocked;
-  }
-  if (mode == kCholPersistent) {
-    if (chol_persist_fits(N, lda))
-      return launch_cholesky_persist(stream, A, N, lda, info, ws, spin_limit, chol_hybrid_k0((int)((N + kNB - 1) / kNB)),
-                                     acq_rel, single_steps, sync_zeroed);
-    mode = kCholBlocked;
-  }
-  if (acq_rel && mode == kCholBlocked) mode = kCholBlockedAcqRel;
-  const int steps = (int)((N + kNB - 1) / kNB);
-  const bool vec = (lda % 2 == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0);
-  const bool fuse = mode == kCholFused;
-  const bool blk = mode == kCholBlocked || mode == kCholBlockedAcqRel;
-  if (blk) return launch_cholesky_blocked(stream, A, N, lda, info, ws, spin_limit, mode == kCholBlockedAcqRel ? 1 : 0);
-  int* flags = reinterpret_cast<int*>(ws + kCholWsDoubles);
-  hipLaunchKernelGGL(chol_diag_kernel, dim3(1), dim3(256), 0, stream, A, N, lda, ws, info, flags, fuse ? steps : 0);
-  hipError_t e = hipGetLastError();
-  for (int k = 0; k + 1 < steps && e == hipSuccess; ++k) {
-    const int64_t rest = N - (int64_t)(k + 1) * kNB;
-    const int t = (int)((rest + kGT - 1) / kGT);
-    // fused: step k's panel came from step k−1's update launch (step 0's from its own launch)
-    if (!fuse || k == 0) {
-      e = chol_panel(stream, A, N, lda, k, ws, info, vec);
-      if (e != hipSuccess) break;
-    }
-    const unsigned wgs = (unsigned)(t * (t + 1) / 2);
-    if (fuse)
-      hipLaunchKernelGGL((chol_update_kernel<true, false>), dim3(wgs), dim3(256), g_chol_update_lds, stream, A, N, lda, k,
-                         t, ws, info, flags, spin_limit, 0, 0);
-    else
-      hipLaunchKernelGGL((chol_update_kernel<false, false>), dim3(wgs), dim3(256), g_chol_update_lds, stream, A, N, lda,
-                         k, t, ws, info, flags, spin_limit, 0, 0);
-    e = hipGetLastError();
-  }
-  return e;
-}
-
-hipError_t launch_cholesky(hipStream_t stream, double* A, int64_t N, int64_t lda, int* info, double* ws, int spin_limit) {
-  return launch_cholesky_mode(stream, A, N, lda, info, ws, kCholAuto, spin_limit);
+  if (mode == kCholPersistent && chol_persist_fits(N, lda))
+    return launch_cholesky_persist(stream, A, N, lda, info, ws, spin_limit, acq_rel, single_steps, zeroed, n_zeroed);
+  return launch_cholesky_blocked(stream, A, N, lda, info, ws, spin_limit, acq_rel ? 1 : 0);
 }
 
 hipError_t launch_trinv(hipStream_t stream, const double* L, int64_t n, int64_t lda, double* X, int64_t ldx,

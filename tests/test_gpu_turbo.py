@@ -122,16 +122,16 @@ def spd(N, seed):
 @pytest.fixture(params=[0, 1, 8, 4, 5, 12], ids=["auto", "steps", "persistent-single", "auto-ar", "steps-ar",
                                                  "persistent-single-ar"])
 def chol_mode(ctx, request):
-    """omb_debug_set(CHOL_MODE): the default schedule (round 6: the whole factorisation in one persistent launch, far
+    """omb_debug_set(CHOL_MODE): the default schedule (the whole factorisation in one persistent launch, far
     tiles' trailing updates batched), the per-step launches, the persistent launch with one task per trailing update
-    (round 5's table, + 8); + 4: the same schedule with release / acquire hand-offs."""
+    (+ 8); + 4: the same schedule with release / acquire hand-offs."""
     ctx.debug_set("chol_mode", request.param)
     yield request.param
     ctx.debug_set("chol_mode", 0)
 
 
-# 2048 / 2049 / 2112 / 2113: 32, 33, 33 and 34 steps — round 5's hand-over from per-step launches to the persistent
-# launch (k0 = 0, 1, 1, 2); kept as sizes where the batched far updates' windows and batches meet the last steps
+# 2048 / 2049 / 2112 / 2113: 32, 33, 33 and 34 steps — sizes where the batched far updates' windows and batches meet
+# the last steps
 @pytest.mark.parametrize("N", [1, 2, 63, 64, 65, 130, 192, 193, 333, 1000, 2048, 2049, 2112, 2113, 3000])
 def test_cholesky_vs_lapack(ctx, chol_mode, N):
     A = spd(N, N)
@@ -235,6 +235,20 @@ def test_cholesky_step_wait_timeout_is_reported(ctx, chol_mode):
         assert e.value.code == _lib.OMB_EHIP and "Cholesky" in str(e.value)
     finally:
         ctx.debug_set("spin_limit", 1 << 22)
+    At = dev(A)
+    assert ctx.cholesky(At) == 0
+    np.testing.assert_allclose(np.tril(At.cpu().numpy()), np.linalg.cholesky(A), rtol=1e-10, atol=1e-12)
+
+
+def test_cholesky_mode_rejects_unknown_values(ctx):
+    """OMB_DEBUG_CHOL_MODE takes 0, 1, 2, alone or + 4 and / or + 8: a schedule number 3, a negative value and one
+    above 14 are OMB_EINVAL and leave the context on the default schedule, which then factors a 2-block matrix."""
+    from optimobo_amd import _lib
+    for v in (-1, 3, 7, 11, 15):
+        with pytest.raises(_lib.OMBError) as e:
+            ctx.debug_set("chol_mode", v)
+        assert e.value.code == _lib.OMB_EINVAL, v
+    A = spd(65, 1)
     At = dev(A)
     assert ctx.cholesky(At) == 0
     np.testing.assert_allclose(np.tril(At.cpu().numpy()), np.linalg.cholesky(A), rtol=1e-10, atol=1e-12)

@@ -1,30 +1,15 @@
-// Timing of the blocked Cholesky (launch_cholesky: chol_diag / chol_panel / chol_update kernels) on an
-// SPD matrix (tools only; not part of the library).  Correctness is tests/test_gpu_turbo.py.
+// Timing of the blocked Cholesky (launch_cholesky_mode: chol_diag_blk / chol_panel / chol_update kernels, and the
+// persistent launch) on an SPD matrix (tools only; not part of the library).  Correctness is tests/test_gpu_turbo.py.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/ablate/ablate_chol tools/ablate/ablate_chol.hip \
 //          -lrocsolver -lrocblas
 // Run on the GPU box: ./tools/ablate/ablate_chol [N ...]
-// Round 4: the blocked diagonal factor (kCholBlocked) against round 3's (kCholFused), interleaved, with its
-// per-wave phase trace; rocsolver_dpotrf on the same matrices as a stated reference rate (not a dependency).
+// The per-step launches (kCholSteps), the same with release / acquire hand-offs, and the persistent launch
+// (kCholPersistent), interleaved, with the per-wave phase trace of the blocked diagonal factor; rocsolver_dpotrf on
+// the same matrices as a stated reference rate (not a dependency).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-
-// phase timestamps of chol_diag_kernel: shader clock (s_memtime) and the 100 MHz constant clock
-__device__ unsigned long long g_trace[2][32];
-#define OMB_CHOL_TRACE(id, cond)                                  \
-  do {                                                            \
-    if (cond) {                                                   \
-      g_trace[0][id] = __builtin_readcyclecounter();              \
-      g_trace[1][id] = __builtin_amdgcn_s_memrealtime();          \
-    }                                                             \
-  } while (0)
-
-__device__ unsigned long long g_col[4][64];
-#define OMB_CHOL_COL(w, j, cond)                                  \
-  do {                                                            \
-    if (cond) g_col[w][j] = __builtin_readcyclecounter();         \
-  } while (0)
 
 __device__ unsigned long long g_btrace[4][16];
 __device__ int64_t g_btrace_r0 = 0;        // chol64_blocked calls traced: the block at this r0
@@ -53,46 +38,6 @@ __device__ unsigned long long g_strace[2][8];
 using namespace omb;
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1);} } while (0)
-
-static void trace_diag() {
-  const int N = 64;
-  std::vector<double> h(N * N);
-  for (int i = 0; i < N; ++i)
-    for (int j = 0; j < N; ++j) h[i * N + j] = (i == j) ? N : 1.0 / (1.0 + std::abs((double)(i - j)));
-  double *A, *ws;
-  int* info;
-  CK(hipMalloc(&A, N * N * 8));
-  CK(hipMalloc(&ws, chol_ws_doubles(N) * 8));
-  CK(hipMalloc(&info, 64));
-  const char* names[17] = {"start", "loaded", "b0 begin", "b0 factored", "b1 begin", "b1 factored", "b2 begin",
-                           "b2 factored", "b3 begin", "b3 factored", "w0 L + W_00", "w1 L + W_11", "w2 L + W_22",
-                           "w3 L + W_33", "(unused)", "barrier", "W done"};
-  for (int rep = 0; rep < 3; ++rep) {
-    CK(hipMemcpy(A, h.data(), N * N * 8, hipMemcpyHostToDevice));
-    CK(hipMemset(info, 0, 4));
-    hipLaunchKernelGGL(chol_diag_kernel, dim3(1), dim3(256), 0, 0, A, (int64_t)N, (int64_t)N, ws, info,
-                       reinterpret_cast<int*>(ws + kCholWsDoubles), 0);
-    CK(hipDeviceSynchronize());
-    unsigned long long t[2][32];
-    CK(hipMemcpyFromSymbol(t, HIP_SYMBOL(g_trace), sizeof(t)));
-    if (rep < 2) continue;
-    printf("chol_diag_kernel phases (cycles of s_memtime from start; us from the 100 MHz clock)\n");
-    for (int i = 0; i < 17; ++i)
-      printf("  %-12s %8lld cyc  %7.2f us\n", names[i], (long long)(t[0][i] - t[0][0]), (t[1][i] - t[1][0]) / 100.0);
-    unsigned long long c[4][64];
-    CK(hipMemcpyFromSymbol(c, HIP_SYMBOL(g_col), sizeof(c)));
-    printf("per column j: cycle (from start) at which wave w has applied (j < 16w) or factored (16w <= j < 16w+16) "
-           "column j\n");
-    for (int j = 0; j < 64; ++j) {
-      printf("  col %2d:", j);
-      for (int w = 0; w < 4; ++w) {
-        if (j < 16 * w + 16) printf(" w%d %7lld", w, (long long)(c[w][j] - t[0][0]));
-      }
-      printf("\n");
-    }
-  }
-  CK(hipFree(A)); CK(hipFree(ws)); CK(hipFree(info));
-}
 
 static void* g_strace_ptr() {
   void* p = nullptr;
@@ -208,7 +153,7 @@ static void trace_steps(int64_t N, int st) {
   for (int rep = 0; rep < 3; ++rep) {
     CK(hipMemcpy(A, h.data(), N * N * 8, hipMemcpyHostToDevice));
     CK(hipMemset(g_strace_ptr(), 0, sizeof(t)));
-    CK(launch_cholesky_mode(0, A, N, N, info, ws, kCholBlocked));
+    CK(launch_cholesky_mode(0, A, N, N, info, ws, kCholSteps));
     CK(hipDeviceSynchronize());
   }
   CK(hipMemcpyFromSymbol(t, HIP_SYMBOL(g_strace), sizeof(t)));
@@ -238,7 +183,6 @@ static void trace_steps(int64_t N, int st) {
 
 int main(int argc, char** argv) {
   setvbuf(stdout, nullptr, _IOLBF, 0);
-  trace_diag();
   trace_diag_blocked();
   trace_steps(3000, 20);
   trace_steps(3000, 2);
@@ -259,20 +203,21 @@ int main(int argc, char** argv) {
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
-    // the launch schedules interleaved: kCholTwoLaunch (round 2), kCholFused (round 3), kCholBlocked (round 4),
-    // kCholBlockedAcqRel (round 4 with the agent-scope release / acquire flag), kCholPersistent (round 4, one launch)
-    const int modes[5] = {kCholTwoLaunch, kCholFused, kCholBlocked, kCholBlockedAcqRel, kCholPersistent};
-    float msum[5] = {0, 0, 0, 0, 0}, mbest[5] = {1e30f, 1e30f, 1e30f, 1e30f, 1e30f};
+    // the launch schedules interleaved: the per-step launches, the same with the agent-scope release / acquire flag,
+    // the persistent launch
+    const int modes[3] = {kCholSteps, kCholSteps, kCholPersistent};
+    const int acq_rel[3] = {0, 1, 0};
+    float msum[3] = {0, 0, 0}, mbest[3] = {1e30f, 1e30f, 1e30f};
     const int reps = 10;
     std::vector<double> Lref(N * N), Lm(N * N);
-    double mdiff[5] = {0, 0, 0, 0, 0};
-    int minfo[5] = {0, 0, 0, 0, 0};
+    double mdiff[3] = {0, 0, 0};
+    int minfo[3] = {0, 0, 0};
     for (int r = 0; r < reps + 1; ++r) {
-      for (int m = 0; m < 5; ++m) {
+      for (int m = 0; m < 3; ++m) {
         CK(hipMemcpy(A, A0, N * N * 8, hipMemcpyDeviceToDevice));
         CK(hipMemset(info, 0, 4));
         CK(hipEventRecord(e0));
-        CK(launch_cholesky_mode(0, A, N, N, info, ws, modes[m]));
+        CK(launch_cholesky_mode(0, A, N, N, info, ws, modes[m], kDefaultSpinLimit, acq_rel[m]));
         CK(hipEventRecord(e1));
         CK(hipEventSynchronize(e1));
         float ms;
@@ -290,15 +235,12 @@ int main(int argc, char** argv) {
         }
       }
     }
-    printf("N=%lld  two-launch %.3f (best %.3f) | fused %.3f (%.3f) | blocked %.3f (%.3f) | blocked acq/rel %.3f (%.3f) | "
-           "persistent %.3f (%.3f) ms; info %d %d %d %d %d; max |L - L_twolaunch|/sqrt(A_ii) %.1e %.1e %.1e %.1e\n",
-           (long long)N, msum[0] / reps, mbest[0], msum[1] / reps, mbest[1], msum[2] / reps, mbest[2], msum[3] / reps,
-           mbest[3], msum[4] / reps, mbest[4], minfo[0], minfo[1], minfo[2], minfo[3], minfo[4], mdiff[1], mdiff[2],
-           mdiff[3], mdiff[4]);
-    float best = mbest[1], sum = msum[1], best2 = mbest[0], sum2 = msum[0];
-    printf("N=%lld  two launches per step %.3f ms (best %.3f)\n", (long long)N, sum2 / reps, best2);
+    printf("N=%lld  per-step %.3f (best %.3f) | per-step acq/rel %.3f (%.3f) | persistent %.3f (%.3f) ms; info %d %d %d; "
+           "max |L - L_steps|/sqrt(A_ii) %.1e %.1e\n",
+           (long long)N, msum[0] / reps, mbest[0], msum[1] / reps, mbest[1], msum[2] / reps, mbest[2], minfo[0],
+           minfo[1], minfo[2], mdiff[1], mdiff[2]);
     {
-      // round 4: the non-diagonal workgroups of each blocked step start after delay × ≈ 0.85 µs
+      // the non-diagonal workgroups of each per-step launch start after delay × ≈ 0.85 µs
       const int delays[5] = {0, 1, 2, 4, 6};
       float sx[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
       for (int r = 0; r < reps + 1; ++r)
@@ -306,7 +248,7 @@ int main(int argc, char** argv) {
           set_chol_update_delay(delays[v]);
           CK(hipMemcpy(A, A0, N * N * 8, hipMemcpyDeviceToDevice));
           CK(hipEventRecord(e0));
-          CK(launch_cholesky_mode(0, A, N, N, info, ws, kCholBlocked));
+          CK(launch_cholesky_mode(0, A, N, N, info, ws, kCholSteps));
           CK(hipEventRecord(e1));
           CK(hipEventSynchronize(e1));
           float ms;
@@ -325,7 +267,7 @@ int main(int argc, char** argv) {
       hipGraph_t graph;
       hipGraphExec_t exec;
       CK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-      CK(launch_cholesky(s, A, N, N, info, ws));
+      CK(launch_cholesky_mode(s, A, N, N, info, ws, kCholPersistent));
       CK(hipStreamEndCapture(s, &graph));
       CK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
       for (int r = 0; r < reps + 1; ++r) {
@@ -360,9 +302,9 @@ int main(int argc, char** argv) {
       for (int64_t k = 0; k <= j; ++k) s += L[i * N + k] * L[j * N + k];
       worst = std::max(worst, std::abs(s - h[i * N + j]) / std::abs(h[i * N + i]));
     }
-    // the library's default schedule after the loops above: the residual of launch_cholesky's factor
-    printf("N=%lld  Cholesky (fused) %.3f ms (best %.3f, %d steps = %.1f us/step)  info %d  max |LLt - A|/A_ii %.2e\n",
-           (long long)N, sum / reps, best, (int)((N + 63) / 64), best * 1e3 / ((N + 63) / 64), hinfo, worst);
+    // the library's default schedule after the loops above: the residual of the persistent launch's factor
+    printf("N=%lld  Cholesky (persistent) %.3f ms (best %.3f, %d steps = %.1f us/step)  info %d  max |LLt - A|/A_ii %.2e\n",
+           (long long)N, msum[2] / reps, mbest[2], (int)((N + 63) / 64), mbest[2] * 1e3 / ((N + 63) / 64), hinfo, worst);
     CK(hipFree(A0)); CK(hipFree(A)); CK(hipFree(ws)); CK(hipFree(info));
   }
   time_rocsolver(sizes);

@@ -1,9 +1,10 @@
-// Per-step launches for the first k0 steps, then the persistent launch (launch_cholesky_persist's k0): time and
-// factor against the per-step launches alone, for a list of k0 (tools only).
+// The persistent launch over its lookahead L and the far tiles' update batching: time and factor against the
+// per-step launches (tools only).  The file keeps the name of the sweep over the retired hybrid schedule (k0 per-step
+// launches before the persistent one), which profiles/ and DESIGN.md cite.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/ablate/chol_hybrid_sweep tools/ablate/chol_hybrid_sweep.hip
-// Run:   ./tools/ablate/chol_hybrid_sweep N [N ...]   (k0 list from CHOL_K0S, default 0,4,8,12,16,24,32; the
-//        persistent launch's lookahead L list from CHOL_LS, default 3 — 0 = round 4's step-major task order; the
-//        far tiles' update batching from CHOL_BW, "batch:window" pairs, default the library's — 1:0 = round 5's table)
+// Run:   ./tools/ablate/chol_hybrid_sweep N [N ...]   (the persistent launch's lookahead L list from CHOL_LS, default
+//        3, L ≥ 1; the far tiles' update batching from CHOL_BW, "batch:window" pairs, default the library's — 1:0 =
+//        every update its own task)
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -30,18 +31,6 @@ __global__ void busy_kernel(int us) {
 
 int main(int argc, char** argv) {
   setvbuf(stdout, nullptr, _IOLBF, 0);
-  std::vector<int> k0s = {0, 4, 8, 12, 16, 24, 32};
-  if (const char* e = getenv("CHOL_K0S")) {
-    k0s.clear();
-    std::string s(e);
-    size_t p = 0;
-    while (p < s.size()) {
-      size_t q = s.find(',', p);
-      if (q == std::string::npos) q = s.size();
-      k0s.push_back(atoi(s.substr(p, q - p).c_str()));
-      p = q + 1;
-    }
-  }
   std::vector<int> Ls = {3};
   if (const char* e = getenv("CHOL_LS")) {
     Ls.clear();
@@ -86,8 +75,7 @@ int main(int argc, char** argv) {
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
     std::vector<double> R(N * N), L(N * N);
-    auto run = [&](int mode, int k0, float& best) {
-      set_chol_hybrid_k0(k0);
+    auto run = [&](int mode, float& best) {
       best = 1e30f;
       for (int r = 0; r < 6; ++r) {
         CK(hipMemcpy(A, A0, N * N * 8, hipMemcpyDeviceToDevice));
@@ -106,34 +94,32 @@ int main(int argc, char** argv) {
       return hinfo;
     };
     float tb;
-    int ib = run(kCholBlocked, -1, tb);
+    int ib = run(kCholSteps, tb);
     CK(hipMemcpy(R.data(), A, N * N * 8, hipMemcpyDeviceToHost));
     printf("N=%lld per-step launches %.3f ms info %d\n", (long long)N, tb, ib);
     std::vector<double> L1(N * N);
-    for (int la : Ls)
-    for (int k0 : k0s) {
+    for (int la : Ls) {
       for (size_t v = 0; v < bws.size(); ++v) {
         set_chol_lookahead(la);
         set_chol_batch(bws[v].first, bws[v].second);
         float tp;
-        const int ip = run(kCholPersistent, k0, tp);
+        const int ip = run(kCholPersistent, tp);
         CK(hipMemcpy(L.data(), A, N * N * 8, hipMemcpyDeviceToHost));
         double md = 0.0;
         for (int64_t i = 0; i < N; ++i)
           for (int64_t j = 0; j <= i; ++j) md = std::max(md, std::abs(L[i * N + j] - R[i * N + j]) / std::sqrt(h[i * N + i]));
-        // batches are bitwise the single-step tasks: every variant against the first of this (L, k0)
+        // batches are bitwise the single-step tasks: every variant against the first of this L
         long long ndiff = 0;
         if (v == 0) L1 = L;
         else
           for (int64_t i = 0; i < N; ++i)
             for (int64_t j = 0; j <= i; ++j) ndiff += L[i * N + j] != L1[i * N + j];
-        printf("N=%lld L=%d k0=%d batch=%d window=%d: %.3f ms info %d max |L - L_steps|/sqrt(A_ii) %.2e  bits != first %lld\n",
-               (long long)N, la, k0, bws[v].first, bws[v].second, tp, ip, md, ndiff);
+        printf("N=%lld L=%d batch=%d window=%d: %.3f ms info %d max |L - L_steps|/sqrt(A_ii) %.2e  bits != first %lld\n",
+               (long long)N, la, bws[v].first, bws[v].second, tp, ip, md, ndiff);
       }
     }
     set_chol_lookahead(-1);
     set_chol_batch(-1, -1);
-    set_chol_hybrid_k0(-1);
     CK(hipFree(A0)); CK(hipFree(A)); CK(hipFree(ws)); CK(hipFree(info));
   }
   return 0;
