@@ -386,7 +386,8 @@ int omb_ea_search(omb_ctx* ctx, int mode, double best, double var_eps, const dou
 
 /* ---------------------------------------------------------------------------------------
  * GP fit on the device — GPy GPRegression(X, y, Matern52(d, ARD=True)) with the noise variance
- * fixed (optimisers.py:223-231 and every other driver's fit): exact inference with GPy's jitchol
+ * fixed (optimisers.py:223-231 and every other driver's fit) or free (the *_noise entries): exact inference
+ * with GPy's jitchol
  * (Ky = K + (σ_n² + 1e-8) I; on failure + mean(diag Ky)·1e-6·10^t, t < 5), the log marginal
  * likelihood and its gradient for the hyperparameter search.  X_dev (n, d), y_dev (n) device.
  * ------------------------------------------------------------------------------------- */
@@ -408,6 +409,25 @@ int omb_gp_lml_grad(omb_ctx* ctx, int kernel, int n, int d, const double* X_dev,
 int omb_gp_lml_grad_batch(omb_ctx* ctx, int kernel, int k, int n, int d, const double* X_dev,
                           const double* const* y_dev, const double* lengthscale_host, const double* variance_host,
                           double noise, double* lml, double* grad_host, double* jitter_used, int* status);
+/* The same evaluation with the noise variance as a free parameter (GPy's default for GPRegression; the
+ * reference's drivers fix it at 0).  With Ky = K + (σ_n² + 1e-8 + jitter) I,
+ *     ∂ lml / ∂ log σ_n² = ½ tr((ααᵀ − Ky⁻¹) σ_n² I) = ½ σ_n² (αᵀα − tr Ky⁻¹),
+ * taken at the jitter jitchol ended on (what GPy's formula does with its L).  The kernels of omb_gp_lml_grad
+ * leave αᵀα and tr Ky⁻¹ beside their other sums in the same launches, so the two calls cost the same and
+ * share every other result bit for bit.
+ * As omb_gp_lml_grad; grad_host (d + 2): the d + 1 entries of omb_gp_lml_grad, then ∂ lml / ∂ log σ_n²
+ * (exactly 0 at noise = 0).  Synchronises. */
+int omb_gp_lml_grad_noise(omb_ctx* ctx, int kernel, int n, int d, const double* X_dev, const double* y_dev,
+                          const double* lengthscale_host, double variance, double noise, double* lml,
+                          double* grad_host, double* jitter_used);
+/* As omb_gp_lml_grad_batch with a noise variance per problem: noise_host (k), grad_host k·(d + 2), problem p's
+ * entries at grad_host[p·(d+2) ..].  The same argument checks, limits (n ≤ 16384, k ≤ 4), per-problem status and
+ * choice between one launch and one problem after another; every problem's results are exactly its own
+ * omb_gp_lml_grad_noise's.  Synchronises. */
+int omb_gp_lml_grad_noise_batch(omb_ctx* ctx, int kernel, int k, int n, int d, const double* X_dev,
+                                const double* const* y_dev, const double* lengthscale_host,
+                                const double* variance_host, const double* noise_host, double* lml,
+                                double* grad_host, double* jitter_used, int* status);
 /* Fit the exact-inference state of objective `obj` on the device (Cholesky, L⁻¹, α) and install
  * it as omb_set_gp would — the device replacement for the host O(n³) factorisation. */
 int omb_gp_fit_state(omb_ctx* ctx, int obj, int kernel, int n, int d, const double* X_dev, const double* y_dev,

@@ -92,6 +92,8 @@ SIGNATURES = {
     # GP fit on the device
     "omb_gp_lml_grad": (_i, [_p, _i, _i, _i, _p, _p, _dp, _d, _d, _dp, _dp, _dp]),
     "omb_gp_lml_grad_batch": (_i, [_p, _i, _i, _i, _i, _p, _p, _dp, _dp, _d, _dp, _dp, _dp, _p]),
+    "omb_gp_lml_grad_noise": (_i, [_p, _i, _i, _i, _p, _p, _dp, _d, _d, _dp, _dp, _dp]),
+    "omb_gp_lml_grad_noise_batch": (_i, [_p, _i, _i, _i, _i, _p, _p, _dp, _dp, _dp, _dp, _dp, _dp, _p]),
     "omb_gp_fit_state": (_i, [_p, _i, _i, _i, _i, _p, _p, _dp, _d, _d, _dp]),
 }
 

@@ -11,14 +11,14 @@ import numpy as np
 from .. import pareto
 from .. import util_functions
 from ..acquisition import engine_for
-from ..gp import GPRegression, Matern52, fit_concurrently
+from ..gp import GPRegression, Matern52, apply_noise_option, check_noise_option, fit_concurrently
 from ..parallel import agree_host_rng
 from ..result import Res
 
 
 class BODriver:
     def __init__(self, test_problem, ideal_point=None, max_point=None, mode="reference", n_candidates=1 << 14,
-                 refine_rounds=2, seed=None, device=None, polish=True, starts=None):
+                 refine_rounds=2, seed=None, device=None, polish=True, starts=None, noise=0.0):
         self.test_problem = test_problem
         self.max_point = max_point
         self.ideal_point = ideal_point
@@ -41,6 +41,9 @@ class BODriver:
         # the device gradient) and its number of starts (None: maximise's default)
         self.polish = polish
         self.starts = starts
+        # the surrogates' noise variance (not in the reference, which fixes it at 0): 0.0 or a positive float
+        # fixes it there, "fit" leaves it free for the hyperparameter search (GPy's own default)
+        self.noise = check_noise_option(noise)
         self._iteration = 0
 
     def _objective_function(self, problem, x):
@@ -69,8 +72,7 @@ class BODriver:
 
     def _model(self, X, y):
         model = GPRegression(X, np.reshape(y, (-1, 1)), Matern52(self.n_vars, ARD=True))
-        model.Gaussian_noise.variance.fix(0)
-        return model
+        return apply_noise_option(model, self.noise)
 
     def _fit(self, X, y):
         model = self._model(X, y)

@@ -19,7 +19,7 @@ from scipy.stats import qmc
 
 from .. import pareto
 from .. import util_functions
-from ..gp import GPRegression, Matern52
+from ..gp import GPRegression, Matern52, apply_noise_option, check_noise_option
 from ..refdirs import get_reference_directions
 from ..result import Res
 
@@ -27,7 +27,7 @@ from ..result import Res
 class TuRBO_1:  # noqa: N801 — reference class name
     """https://doi.org/10.48550/arXiv.1910.01739 — one trust region (turbo.py:17-304)."""
 
-    def __init__(self, test_problem, batch_size, ideal_point=None, max_point=None, device=None):
+    def __init__(self, test_problem, batch_size, ideal_point=None, max_point=None, device=None, noise=0.0):
         self.test_problem = test_problem
         self.max_point = max_point
         self.ideal_point = ideal_point
@@ -52,6 +52,9 @@ class TuRBO_1:  # noqa: N801 — reference class name
         self.is_ideal_known = ideal_point is not None
         self.is_max_known = max_point is not None
         self.device = device            # not in the reference: GPU of the sampling path
+        # not in the reference either (it fixes the noise variance at 0): 0.0 or a positive float fixes it there,
+        # "fit" leaves it free for the hyperparameter search
+        self.noise = check_noise_option(noise)
 
     def _objective_function(self, problem, x):
         return problem.evaluate(x)
@@ -62,9 +65,12 @@ class TuRBO_1:  # noqa: N801 — reference class name
     def denormalise(self, X):
         return (X * (self.upper - self.lower)) + self.lower
 
-    def _fit(self, X, y):
+    def _model(self, X, y):
         model = GPRegression(X, np.reshape(y, (-1, 1)), Matern52(self.n_vars, ARD=True))
-        model.Gaussian_noise.variance.fix(0)
+        return apply_noise_option(model, self.noise)
+
+    def _fit(self, X, y):
+        model = self._model(X, y)
         model.optimize(messages=False, max_f_eval=1000)
         return model
 
@@ -189,10 +195,10 @@ class TuRBO_1:  # noqa: N801 — reference class name
 class TuRBO_M(TuRBO_1):  # noqa: N801 — reference class name
     """TuRBO-m: several trust regions competing for one batch (turbo.py:307-574)."""
 
-    def __init__(self, test_problem, ideal_point, max_point, batch_size, n_trust_regions, device=None):
+    def __init__(self, test_problem, ideal_point, max_point, batch_size, n_trust_regions, device=None, noise=0.0):
         self.n_trust_regions = n_trust_regions
         super().__init__(test_problem=test_problem, ideal_point=ideal_point, max_point=max_point,
-                         batch_size=batch_size, device=device)
+                         batch_size=batch_size, device=device, noise=noise)
         self.succtol = 3
         self.failtol = max(5, self.n_vars)
         self.hypers = [{} for _ in range(self.n_trust_regions)]

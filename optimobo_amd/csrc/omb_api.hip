@@ -1338,7 +1338,7 @@ struct GPFactor {
   double* v;       // (n)
   double* ls;      // (DP)
   double* part;    // gp_grad_blocks(n)·(DP+1)
-  double* out;     // DP + 3
+  double* out;     // DP + 5
   double* cws;     // cand_cov_ws_doubles(n, DP): X/ℓ and its squared norms for K(X, X)
   double jitter;   // jitter added by jitchol (0 when the first factorisation succeeded)
 };
@@ -1350,7 +1350,7 @@ static int gp_factor(omb_ctx* ctx, int kernel, int n, int d, const double* X, co
   const int DP = pad_dim(d);
   const size_t nn = (size_t)n * n;
   const size_t doubles = 3 * nn + 64 * (size_t)n + 2 * (size_t)n + DP +
-                         (size_t)gp_grad_blocks(n) * (DP + 1) + DP + 3 + (size_t)cand_cov_ws_doubles(n, DP);
+                         (size_t)gp_grad_blocks(n) * (DP + 1) + DP + 5 + (size_t)cand_cov_ws_doubles(n, DP);
   int rc = grow_dev(ctx, &ctx->fws, &ctx->fws_cap, sizeof(double) * doubles, "GP fit workspace");
   if (rc) return rc;
   double* p = static_cast<double*>(ctx->fws);
@@ -1362,7 +1362,7 @@ static int gp_factor(omb_ctx* ctx, int kernel, int n, int d, const double* X, co
   f->v = p; p += n;
   f->ls = p; p += DP;
   f->part = p; p += (size_t)gp_grad_blocks(n) * (DP + 1);
-  f->out = p; p += DP + 3;
+  f->out = p; p += DP + 5;
   f->cws = p;
   void* h = nullptr;
   if ((rc = stage_begin(ctx, sizeof(double) * DP, &h))) return rc;
@@ -1394,9 +1394,16 @@ static int gp_factor(omb_ctx* ctx, int kernel, int n, int d, const double* X, co
   return OMB_OK;
 }
 
-int omb_gp_lml_grad(omb_ctx* ctx, int kernel, int n, int d, const double* X_dev, const double* y_dev,
-                    const double* lengthscale_host, double variance, double noise, double* lml, double* grad,
-                    double* jitter_used) {
+// ∂ lml / ∂ log σ_n² = ½ tr((ααᵀ − Ky⁻¹) ∂Ky/∂log σ_n²) = ½ σ_n² (αᵀα − tr Ky⁻¹); exactly 0 at σ_n² = 0
+static double noise_entry(double noise, double aa, double tr_kinv) {
+  return noise == 0.0 ? 0.0 : 0.5 * noise * (aa - tr_kinv);
+}
+
+// omb_gp_lml_grad (noise_grad false: grad has d + 1 entries) and omb_gp_lml_grad_noise (d + 2): the same
+// launches and the same first d + 1 entries; the kernels always leave αᵀα and tr Ky⁻¹ beside the other sums.
+static int gp_lml_grad_impl(omb_ctx* ctx, int kernel, int n, int d, const double* X_dev, const double* y_dev,
+                            const double* lengthscale_host, double variance, double noise, double* lml, double* grad,
+                            double* jitter_used, bool noise_grad) {
   int rc = enter(ctx);
   if (rc) return rc;
   if (kernel != OMB_KERNEL_MATERN52 && kernel != OMB_KERNEL_RBF) return fail(ctx, OMB_EINVAL, "unknown kernel %d", kernel);
@@ -1409,7 +1416,7 @@ int omb_gp_lml_grad(omb_ctx* ctx, int kernel, int n, int d, const double* X_dev,
   const int DP = pad_dim(d);
   if (gp_lml_small_fits(n, DP)) {
     // one workgroup, one launch, one synchronisation (launch_gp_lml_small); the kernel stores its
-    // DP + 5 results straight into the pinned, host-mapped fit_host (no D2H copy per evaluation)
+    // DP + 7 results straight into the pinned, host-mapped fit_host (no D2H copy per evaluation)
     OMB_HIP(ctx, launch_gp_lml_small(ctx->stream, kernel, DP, X_dev, d, n, lengthscale_host, variance, noise + 1e-8,
                                      y_dev, ctx->fit_dev));
     OMB_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1418,6 +1425,7 @@ int omb_gp_lml_grad(omb_ctx* ctx, int kernel, int n, int d, const double* X_dev,
       return fail(ctx, OMB_ENOTPD, "K + jitter is not positive definite, even with jitter (column %d)", (int)h[DP + 4]);
     *lml = -0.5 * h[DP + 2] - h[DP + 1] - 0.5 * n * log(2.0 * M_PI);
     for (int q = 0; q <= d; ++q) grad[q] = h[q];
+    if (noise_grad) grad[d + 1] = noise_entry(noise, h[DP + 5], -h[DP + 6]);   // slot DP+6 holds −tr Ky⁻¹
     if (jitter_used) *jitter_used = h[DP + 3];
     return OMB_OK;
   }
@@ -1427,35 +1435,54 @@ int omb_gp_lml_grad(omb_ctx* ctx, int kernel, int n, int d, const double* X_dev,
   OMB_HIP(ctx, launch_gemm_tn_lower(ctx->stream, n, n, 1.0, f.Linv, n, 0.0, f.Kinv, n));
   OMB_HIP(ctx, launch_gp_grad(ctx->stream, kernel, DP, X_dev, d, n, f.ls, variance, f.alpha, f.Kinv, n, f.part,
                               f.Ky, n, y_dev, f.out));
-  OMB_HIP(ctx, hipMemcpyAsync(ctx->fit_host, f.out, sizeof(double) * (DP + 3), hipMemcpyDeviceToHost, ctx->stream));
+  OMB_HIP(ctx, hipMemcpyAsync(ctx->fit_host, f.out, sizeof(double) * (DP + 5), hipMemcpyDeviceToHost, ctx->stream));
   OMB_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const volatile double* h = ctx->fit_host;
   // GPy: log p(y) = −½ yᵀα − Σ log L_ii − ½ n log 2π
   *lml = -0.5 * h[DP + 2] - h[DP + 1] - 0.5 * n * log(2.0 * M_PI);
   for (int q = 0; q <= d; ++q) grad[q] = h[q];
+  if (noise_grad) grad[d + 1] = noise_entry(noise, h[DP + 3], h[DP + 4]);
   if (jitter_used) *jitter_used = f.jitter;
   return OMB_OK;
 }
 
-int omb_gp_lml_grad_batch(omb_ctx* ctx, int kernel, int k, int n, int d, const double* X_dev,
-                          const double* const* y_dev, const double* lengthscale_host, const double* variance_host,
-                          double noise, double* lml, double* grad_host, double* jitter_used, int* status) {
+int omb_gp_lml_grad(omb_ctx* ctx, int kernel, int n, int d, const double* X_dev, const double* y_dev,
+                    const double* lengthscale_host, double variance, double noise, double* lml, double* grad,
+                    double* jitter_used) {
+  return gp_lml_grad_impl(ctx, kernel, n, d, X_dev, y_dev, lengthscale_host, variance, noise, lml, grad, jitter_used,
+                          false);
+}
+
+int omb_gp_lml_grad_noise(omb_ctx* ctx, int kernel, int n, int d, const double* X_dev, const double* y_dev,
+                          const double* lengthscale_host, double variance, double noise, double* lml, double* grad,
+                          double* jitter_used) {
+  return gp_lml_grad_impl(ctx, kernel, n, d, X_dev, y_dev, lengthscale_host, variance, noise, lml, grad, jitter_used,
+                          true);
+}
+
+// omb_gp_lml_grad_batch (one noise for all, d + 1 entries per problem) and omb_gp_lml_grad_noise_batch (a noise
+// per problem, d + 2 entries): noise_host has k values in both.
+static int gp_lml_grad_batch_impl(omb_ctx* ctx, int kernel, int k, int n, int d, const double* X_dev,
+                                  const double* const* y_dev, const double* lengthscale_host,
+                                  const double* variance_host, const double* noise_host, double* lml,
+                                  double* grad_host, double* jitter_used, int* status, bool noise_grad) {
   int rc = enter(ctx);
   if (rc) return rc;
   if (k < 1 || k > kFitBatchMax) return fail(ctx, OMB_EUNSUP, "k=%d outside [1, %d]", k, kFitBatchMax);
   if (kernel != OMB_KERNEL_MATERN52 && kernel != OMB_KERNEL_RBF) return fail(ctx, OMB_EINVAL, "unknown kernel %d", kernel);
   if (n < 1 || n > 16384) return fail(ctx, OMB_EUNSUP, "n_train=%d outside [1, 16384]", n);
   if (d < 1 || d > OMB_MAX_DIM) return fail(ctx, OMB_EUNSUP, "n_var=%d outside [1, %d]", d, OMB_MAX_DIM);
-  if (!X_dev || !y_dev || !lengthscale_host || !variance_host || !lml || !grad_host || !status)
+  if (!X_dev || !y_dev || !lengthscale_host || !variance_host || !noise_host || !lml || !grad_host || !status)
     return fail(ctx, OMB_EINVAL, "null pointer");
+  const int G = noise_grad ? d + 2 : d + 1;   // gradient entries per problem
   for (int p = 0; p < k; ++p) {
     if (!y_dev[p]) return fail(ctx, OMB_EINVAL, "null y_dev[%d]", p);
     for (int j = 0; j < d; ++j)
       if (!(lengthscale_host[p * d + j] > 0.0))
         return fail(ctx, OMB_EINVAL, "lengthscale[%d][%d]=%g must be > 0", p, j, lengthscale_host[p * d + j]);
     if (!(variance_host[p] > 0.0)) return fail(ctx, OMB_EINVAL, "variance[%d] must be > 0", p);
+    if (!(noise_host[p] >= 0.0)) return fail(ctx, OMB_EINVAL, "noise must be >= 0");
   }
-  if (!(noise >= 0.0)) return fail(ctx, OMB_EINVAL, "noise must be >= 0");
   const int DP = pad_dim(d);
   // n ≤ 96, n_var ≤ 8: one launch.  (Batching up to the one-workgroup kernel's n ≤ 128 was 17% faster on
   // config 1, but between n = 97 and 128 a single evaluation takes the blocked path, and on ill-conditioned
@@ -1464,27 +1491,50 @@ int omb_gp_lml_grad_batch(omb_ctx* ctx, int kernel, int k, int n, int d, const d
   if (!gp_lml_small_fits(n, DP)) {
     // blocked path: the problems one after another, each exactly omb_gp_lml_grad
     for (int p = 0; p < k; ++p) {
-      rc = omb_gp_lml_grad(ctx, kernel, n, d, X_dev, y_dev[p], lengthscale_host + p * d, variance_host[p], noise,
-                           lml + p, grad_host + p * (d + 1), jitter_used ? jitter_used + p : nullptr);
+      rc = gp_lml_grad_impl(ctx, kernel, n, d, X_dev, y_dev[p], lengthscale_host + p * d, variance_host[p],
+                            noise_host[p], lml + p, grad_host + p * G, jitter_used ? jitter_used + p : nullptr,
+                            noise_grad);
       if (rc != OMB_OK && rc != OMB_ENOTPD) return rc;
       status[p] = rc;
     }
     return OMB_OK;
   }
-  // fit_host holds OMB_MAX_DIM + 8 doubles: problem p's DP + 5 results at p·(DP + 5) (k·13 ≤ 52 ≤ 72)
+  // fit_host holds OMB_MAX_DIM + 8 doubles: problem p's DP + 7 results at p·(DP + 7) (DP ≤ 8: k·15 ≤ 60 ≤ 264)
   double* outs[kFitBatchMax];
-  for (int p = 0; p < k; ++p) outs[p] = ctx->fit_dev + p * (DP + 5);
+  double base[kFitBatchMax];
+  for (int p = 0; p < k; ++p) {
+    outs[p] = ctx->fit_dev + p * (DP + 7);
+    base[p] = noise_host[p] + 1e-8;
+  }
   OMB_HIP(ctx, launch_gp_lml_small_batch(ctx->stream, kernel, DP, X_dev, d, n, k, y_dev, lengthscale_host,
-                                         variance_host, noise + 1e-8, outs));
+                                         variance_host, base, outs));
   OMB_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (int p = 0; p < k; ++p) {
-    const volatile double* h = ctx->fit_host + p * (DP + 5);
+    const volatile double* h = ctx->fit_host + p * (DP + 7);
     status[p] = h[DP + 4] != 0.0 ? OMB_ENOTPD : OMB_OK;
     lml[p] = -0.5 * h[DP + 2] - h[DP + 1] - 0.5 * n * log(2.0 * M_PI);
-    for (int q = 0; q <= d; ++q) grad_host[p * (d + 1) + q] = h[q];
+    for (int q = 0; q <= d; ++q) grad_host[p * G + q] = h[q];
+    if (noise_grad) grad_host[p * G + d + 1] = noise_entry(noise_host[p], h[DP + 5], -h[DP + 6]);
     if (jitter_used) jitter_used[p] = h[DP + 3];
   }
   return OMB_OK;
+}
+
+int omb_gp_lml_grad_batch(omb_ctx* ctx, int kernel, int k, int n, int d, const double* X_dev,
+                          const double* const* y_dev, const double* lengthscale_host, const double* variance_host,
+                          double noise, double* lml, double* grad_host, double* jitter_used, int* status) {
+  double noises[kFitBatchMax];
+  for (int p = 0; p < kFitBatchMax; ++p) noises[p] = noise;
+  return gp_lml_grad_batch_impl(ctx, kernel, k, n, d, X_dev, y_dev, lengthscale_host, variance_host, noises, lml,
+                                grad_host, jitter_used, status, false);
+}
+
+int omb_gp_lml_grad_noise_batch(omb_ctx* ctx, int kernel, int k, int n, int d, const double* X_dev,
+                                const double* const* y_dev, const double* lengthscale_host,
+                                const double* variance_host, const double* noise_host, double* lml, double* grad_host,
+                                double* jitter_used, int* status) {
+  return gp_lml_grad_batch_impl(ctx, kernel, k, n, d, X_dev, y_dev, lengthscale_host, variance_host, noise_host, lml,
+                                grad_host, jitter_used, status, true);
 }
 
 int omb_gp_fit_state(omb_ctx* ctx, int obj, int kernel, int n, int d, const double* X_dev, const double* y_dev,

@@ -196,19 +196,21 @@ hipError_t launch_gemm_tn(hipStream_t s, int64_t M, int64_t Nc, int64_t K, doubl
 hipError_t launch_trinv(hipStream_t stream, const double* L, int64_t n, int64_t lda, double* X, int64_t ldx,
                         double* T);
 // GP log-marginal-likelihood pieces: out[0..DP] = ½ Σ W ∂K/∂θ (θ = log σ_f², log ℓ_j; entries past
-// d are 0), out[DP+1] = Σ log L_ii, out[DP+2] = yᵀα.  partials: gp_grad_blocks(n)·(DP+1) doubles.
+// d are 0), out[DP+1] = Σ log L_ii, out[DP+2] = yᵀα, and the noise entry's sums out[DP+3] = αᵀα,
+// out[DP+4] = tr Ky⁻¹ (out: DP+5 doubles).  partials: gp_grad_blocks(n)·(DP+1) doubles.
 int64_t gp_grad_blocks(int64_t n);
 // n ≤ 128 and n_var ≤ 8 (gp_lml_small_fits): the whole evaluation in one workgroup (sweep-operator
-// inverse in LDS, jitter retries in-kernel); out (DP+5 doubles): the launch_gp_grad layout +
-// out[DP+3] = jitter, out[DP+4] = info.
+// inverse in LDS, jitter retries in-kernel); out (DP+7 doubles): launch_gp_grad's first DP+3 slots, then
+// out[DP+3] = jitter, out[DP+4] = info, out[DP+5] = αᵀα, out[DP+6] = −tr Ky⁻¹ (at that jitter).
 bool gp_lml_small_fits(int n, int DP);
 hipError_t launch_gp_lml_small(hipStream_t stream, int kind, int DP, const double* X, int d, int n,
                                const double* ls_host, double variance, double base, const double* y, double* out);
-// k ≤ kFitBatchMax problems on the same X (y[p], ls_host[p·d..], variance[p] → out[p]), one workgroup each
+// k ≤ kFitBatchMax problems on the same X (y[p], ls_host[p·d..], variance[p], base[p] = σ_n² + 1e-8 of
+// problem p → out[p]), one workgroup each
 constexpr int kFitBatchMax = 4;
 hipError_t launch_gp_lml_small_batch(hipStream_t stream, int kind, int DP, const double* X, int d, int n, int k,
                                      const double* const* y, const double* ls_host, const double* variance,
-                                     double base, double* const* out);
+                                     const double* base, double* const* out);
 // dense posterior path: μ, σ² of a candidate chunk from K* (n, Nc) and V = L⁻¹K* (n, Nc).
 hipError_t launch_post_colreduce(hipStream_t stream, const double* Kst, const double* V, int64_t n, int64_t Nc,
                                  const double* alpha, double variance, double* mu, double* var,

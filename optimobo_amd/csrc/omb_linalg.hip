@@ -1466,21 +1466,29 @@ __global__ __launch_bounds__(256) void gp_grad_kernel(const double* __restrict__
   if (tid <= DP) partials[blk * (DP + 1) + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
 }
 
-// out[q] = Σ_blocks partials (q ≤ DP, fixed order); out[DP+1] = Σ log L_ii; out[DP+2] = yᵀα.
+// out[q] = Σ_blocks partials (q ≤ DP, fixed order); out[DP+1] = Σ log L_ii; out[DP+2] = yᵀα; then the two sums
+// of the noise entry ∂ lml / ∂ log σ_n² = ½ σ_n² (αᵀα − tr Ky⁻¹): out[DP+3] = αᵀα, out[DP+4] = tr Ky⁻¹ (the
+// diagonal of the Kinv that gp_grad_kernel read).
 __global__ __launch_bounds__(256) void gp_reduce_kernel(const double* __restrict__ partials, int64_t nblk, int P,
                                                         const double* __restrict__ L, int64_t n, int64_t lda,
                                                         const double* __restrict__ y,
-                                                        const double* __restrict__ alpha, double* __restrict__ out) {
+                                                        const double* __restrict__ alpha,
+                                                        const double* __restrict__ Kinv, int64_t ldk,
+                                                        double* __restrict__ out) {
   __shared__ double red[256];
   const int tid = threadIdx.x;
-  for (int q = 0; q < P + 2; ++q) {
+  for (int q = 0; q < P + 4; ++q) {
     double v = 0.0;
     if (q < P) {
       for (int64_t b = tid; b < nblk; b += 256) v += partials[b * P + q];
     } else if (q == P) {
       for (int64_t t = tid; t < n; t += 256) v += log(L[t * lda + t]);
-    } else {
+    } else if (q == P + 1) {
       for (int64_t t = tid; t < n; t += 256) v = fma(y[t], alpha[t], v);
+    } else if (q == P + 2) {
+      for (int64_t t = tid; t < n; t += 256) v = fma(alpha[t], alpha[t], v);
+    } else {
+      for (int64_t t = tid; t < n; t += 256) v += Kinv[t * ldk + t];
     }
     red[tid] = v;
     __syncthreads();
@@ -1519,7 +1527,9 @@ __global__ __launch_bounds__(256) void gp_reduce_kernel(const double* __restrict
 //   * α = Ky⁻¹y, then ½ Σ_ik W_ik ∂K_ik/∂θ with W = ααᵀ − Ky⁻¹ over the full matrix (the same sums as
 //     gp_grad_kernel), all reductions in a fixed order (deterministic).
 // out[0..DP] gradient, out[DP+1] = Σ log L_ii, out[DP+2] = yᵀα, out[DP+3] = jitter, out[DP+4] = info
-// (0, or the 1-based column of the failed pivot after the last retry).
+// (0, or the 1-based column of the failed pivot after the last retry), then the two sums of the noise entry
+// ∂ lml / ∂ log σ_n² = ½ σ_n² (αᵀα − tr Ky⁻¹) at that jitter: out[DP+5] = αᵀα = Σ α_i², out[DP+6] = Σ A_ii =
+// −tr Ky⁻¹ (both over the n real rows, not the identity padding).
 constexpr int kSmallFitN = 128;
 constexpr int kSmallFitLD = 136;    // row pitch (doubles) of the LDS copy of Ky
 constexpr int kSmallFitThreads = 512;
@@ -1595,7 +1605,7 @@ __device__ __forceinline__ void gp_lml_small_body(const double* __restrict__ X, 
   __shared__ double Ls[16 * 17];                   // L_B⁻¹ (inverse Cholesky factor of the pivot block)
   __shared__ double Lf[16 * 17];                   // L_B
   __shared__ double piv[kSmallFitN], alpha[kSmallFitN];
-  __shared__ double red[NW][DP + 3];
+  __shared__ double red[NW][DP + 5];
   __shared__ int flag;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1827,6 +1837,8 @@ __device__ __forceinline__ void gp_lml_small_body(const double* __restrict__ X, 
       for (int q = 0; q < DP + 3; ++q) out[q] = 0.0;
       out[DP + 3] = jit;
       out[DP + 4] = (double)bad;
+      out[DP + 5] = 0.0;
+      out[DP + 6] = 0.0;
     }
     return;
   }
@@ -1842,9 +1854,9 @@ __device__ __forceinline__ void gp_lml_small_body(const double* __restrict__ X, 
     if (lane == 0) alpha[i] = -s;
   }
   __syncthreads();
-  double acc[DP + 3];
+  double acc[DP + 5];
 #pragma unroll
-  for (int q = 0; q < DP + 3; ++q) acc[q] = 0.0;
+  for (int q = 0; q < DP + 5; ++q) acc[q] = 0.0;
   const double al0 = h0 ? alpha[j0] : 0.0, al1 = h1 ? alpha[j1] : 0.0;
   double b0[DP], b1[DP];
   load_cols(b0, b1);
@@ -1872,20 +1884,23 @@ __device__ __forceinline__ void gp_lml_small_body(const double* __restrict__ X, 
   if (tid < n) {
     acc[DP + 1] = 0.5 * log(piv[tid]);
     acc[DP + 2] = y[tid] * alpha[tid];
+    // the noise entry's sums ride the same reduction (row tid, like the two above): Σ α_i², Σ A_ii
+    acc[DP + 3] = alpha[tid] * alpha[tid];
+    acc[DP + 4] = A[tid * LD + tid];
   }
 #pragma unroll
-  for (int q = 0; q < DP + 3; ++q) {
+  for (int q = 0; q < DP + 5; ++q) {
     double v = acc[q];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     if (lane == 0) red[wave][q] = v;
   }
   __syncthreads();
-  if (tid < DP + 3) {
+  if (tid < DP + 5) {
     double v = 0.0;
 #pragma unroll
     for (int w = 0; w < NW; ++w) v += red[w][tid];
-    out[tid] = v;
+    out[tid < DP + 3 ? tid : tid + 2] = v;          // the two new sums after jitter and info: out[DP+5], out[DP+6]
   }
   if (tid == 0) {
     out[DP + 3] = jit;
@@ -1908,16 +1923,17 @@ struct FitBatch {
   double* out[kFitBatchMax];
   double ls[kFitBatchMax][8];
   double variance[kFitBatchMax];
+  double base[kFitBatchMax];   // σ_n² + 1e-8 of each problem
 };
 
 template <int DP, int KIND, int ABL = 0>
 __global__ __launch_bounds__(kSmallFitThreads) void gp_lml_small_batch_kernel(const double* __restrict__ X, int d,
-                                                                              int n, FitBatch b, double base) {
+                                                                              int n, FitBatch b) {
   const int p = blockIdx.x;
   FitLs ls;
 #pragma unroll
   for (int j = 0; j < kSmallFitMaxDP; ++j) ls.v[j] = b.ls[p][j];
-  gp_lml_small_body<DP, KIND, ABL>(X, d, n, ls, b.variance[p], base, b.y[p], b.out[p]);
+  gp_lml_small_body<DP, KIND, ABL>(X, d, n, ls, b.variance[p], b.base[p], b.y[p], b.out[p]);
 }
 
 // DP ≤ 8: the two candidate columns' scaled coordinates stay in registers (DP = 16 spills at 1024 threads).
@@ -1949,7 +1965,7 @@ hipError_t launch_gp_lml_small(hipStream_t stream, int kind, int DP, const doubl
 
 hipError_t launch_gp_lml_small_batch(hipStream_t stream, int kind, int DP, const double* X, int d, int n, int k,
                                      const double* const* y, const double* ls_host, const double* variance,
-                                     double base, double* const* out) {
+                                     const double* base, double* const* out) {
   if (!gp_lml_small_fits(n, DP) || d < 1 || d > DP || DP > 8 || k < 1 || k > kFitBatchMax)
     return hipErrorInvalidValue;
   FitBatch b{};
@@ -1957,16 +1973,17 @@ hipError_t launch_gp_lml_small_batch(hipStream_t stream, int kind, int DP, const
     b.y[p] = y[p];
     b.out[p] = out[p];
     b.variance[p] = variance[p];
+    b.base[p] = base[p];
     for (int j = 0; j < 8; ++j) b.ls[p][j] = (j < d) ? ls_host[p * d + j] : 1.0;
   }
 #define OMB_GSB(DPV)                                                                                        \
   case DPV:                                                                                                 \
     if (kind == OMB_KERNEL_RBF)                                                                             \
       hipLaunchKernelGGL((gp_lml_small_batch_kernel<DPV, OMB_KERNEL_RBF>), dim3(k), dim3(kSmallFitThreads), 0, \
-                         stream, X, d, n, b, base);                                                          \
+                         stream, X, d, n, b);                                                                \
     else                                                                                                    \
       hipLaunchKernelGGL((gp_lml_small_batch_kernel<DPV, OMB_KERNEL_MATERN52>), dim3(k),                    \
-                         dim3(kSmallFitThreads), 0, stream, X, d, n, b, base);                              \
+                         dim3(kSmallFitThreads), 0, stream, X, d, n, b);                                    \
     break;
   switch (DP) {
     OMB_GSB(2) OMB_GSB(4) OMB_GSB(6) OMB_GSB(8)
@@ -2704,7 +2721,7 @@ hipError_t launch_gp_grad(hipStream_t stream, int kind, int DP, const double* X,
     hipError_t e = launch_gp_grad_partials_wide(stream, kind, DP, X, d, n, ls, variance, alpha, Kinv, ldk, partials);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(gp_reduce_kernel, dim3(1), dim3(256), 0, stream, partials, (int64_t)t * t, DP + 1, L, n, lda, y,
-                       alpha, out);
+                       alpha, Kinv, ldk, out);
     return hipGetLastError();
   }
 #define OMB_GG(DPV)                                                                                              \
@@ -2724,7 +2741,7 @@ hipError_t launch_gp_grad(hipStream_t stream, int kind, int DP, const double* X,
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(gp_reduce_kernel, dim3(1), dim3(256), 0, stream, partials, (int64_t)t * t, DP + 1, L, n, lda, y,
-                     alpha, out);
+                     alpha, Kinv, ldk, out);
   return hipGetLastError();
 }
 

@@ -376,9 +376,11 @@ class AcqContext:
         return out
 
     # ------------------------------------------------------------------ GP fit on the device
-    def gp_lml_grad(self, X, y, lengthscale, variance, noise=0.0, kernel="matern52"):
-        """GPy's exact-inference log marginal likelihood at (σ_f², ℓ) with the noise fixed, its gradient
-        w.r.t. (log σ_f², log ℓ_1..d) and jitchol's extra jitter: (lml, grad (d+1,), jitter)."""
+    def gp_lml_grad(self, X, y, lengthscale, variance, noise=0.0, kernel="matern52", noise_grad=False):
+        """GPy's exact-inference log marginal likelihood at (σ_f², ℓ, σ_n²), its gradient w.r.t.
+        (log σ_f², log ℓ_1..d) and jitchol's extra jitter: (lml, grad (d+1,), jitter).  ``noise_grad=True``
+        (omb_gp_lml_grad_noise) appends ∂/∂log σ_n² = ½ σ_n² (αᵀα − tr Ky⁻¹): grad (d+2,), the rest bitwise the
+        same."""
         X = _dev_f64(X, self.device)
         y = _dev_f64(y, self.device).reshape(-1)
         n, d = X.shape
@@ -387,16 +389,18 @@ class AcqContext:
         ls = np.broadcast_to(np.asarray(lengthscale, np.float64), (d,))
         kid = {"matern52": _lib.KERNEL_MATERN52, "rbf": _lib.KERNEL_RBF}[kernel]
         lml, jit = ctypes.c_double(), ctypes.c_double()
-        grad = (ctypes.c_double * (d + 1))()
+        grad = (ctypes.c_double * (d + 2 if noise_grad else d + 1))()
+        name = "omb_gp_lml_grad_noise" if noise_grad else "omb_gp_lml_grad"
         self._stream()
-        self._check(self.lib.omb_gp_lml_grad(self._h, kid, n, d, _ptr(X), _ptr(y), _lib.darr(ls), float(variance),
-                                             float(noise), ctypes.byref(lml), grad, ctypes.byref(jit)),
-                    "omb_gp_lml_grad")
+        self._check(getattr(self.lib, name)(self._h, kid, n, d, _ptr(X), _ptr(y), _lib.darr(ls), float(variance),
+                                            float(noise), ctypes.byref(lml), grad, ctypes.byref(jit)), name)
         return lml.value, np.array(grad[:]), jit.value
 
-    def gp_lml_grad_batch(self, X, ys, lengthscales, variances, noise=0.0, kernel="matern52"):
+    def gp_lml_grad_batch(self, X, ys, lengthscales, variances, noise=0.0, kernel="matern52", noise_grad=False):
         """omb_gp_lml_grad_batch: k ≤ 4 GPs on the same inputs in one call — (lml (k,), grad (k, d+1),
-        jitter (k,), status (k,)); status[p] is 0 or OMB_ENOTPD for problem p."""
+        jitter (k,), status (k,)); status[p] is 0 or OMB_ENOTPD for problem p.  ``noise_grad=True``
+        (omb_gp_lml_grad_noise_batch): ``noise`` is a scalar or one value per problem and grad is (k, d+2),
+        the last entry ∂/∂log σ_n²."""
         X = _dev_f64(X, self.device)
         ys = [_dev_f64(y, self.device).reshape(-1) for y in ys]
         n, d = X.shape
@@ -408,11 +412,18 @@ class AcqContext:
         kid = {"matern52": _lib.KERNEL_MATERN52, "rbf": _lib.KERNEL_RBF}[kernel]
         yptr = (ctypes.c_void_p * k)(*[y.data_ptr() for y in ys])
         lml = np.zeros(k)
-        grad = np.zeros((k, d + 1))
+        grad = np.zeros((k, d + 2 if noise_grad else d + 1))
         jit = np.zeros(k)
         status = np.zeros(k, np.int32)
         dp = ctypes.POINTER(ctypes.c_double)
         self._stream()
+        if noise_grad:
+            nz = np.ascontiguousarray(np.broadcast_to(np.asarray(noise, np.float64), (k,)))
+            self._check(self.lib.omb_gp_lml_grad_noise_batch(
+                self._h, kid, k, n, d, _ptr(X), ctypes.cast(yptr, ctypes.c_void_p), ls.ctypes.data_as(dp),
+                var.ctypes.data_as(dp), nz.ctypes.data_as(dp), lml.ctypes.data_as(dp), grad.ctypes.data_as(dp),
+                jit.ctypes.data_as(dp), ctypes.c_void_p(status.ctypes.data)), "omb_gp_lml_grad_noise_batch")
+            return lml, grad, jit, status
         self._check(self.lib.omb_gp_lml_grad_batch(
             self._h, kid, k, n, d, _ptr(X), ctypes.cast(yptr, ctypes.c_void_p), ls.ctypes.data_as(dp),
             var.ctypes.data_as(dp), float(noise), lml.ctypes.data_as(dp), grad.ctypes.data_as(dp),

@@ -9,9 +9,9 @@ Mirrors the part of GPy the reference uses (optimobo/algorithms/optimisers.py:22
 
 The fit (kernel matrix, jittered Cholesky, α, L⁻¹, and the L-BFGS hyperparameter search) is
 O(n³) per likelihood evaluation.  With a GPU it runs on the device: each
-L-BFGS-B evaluation is one omb_gp_lml_grad call (K, Cholesky, L⁻¹, Ky⁻¹ and the gradient sums in
-HIP; scipy's L-BFGS-B drives it on the host) and the final state is factorised in place by
-omb_gp_fit_state.  Without a GPU (the CPU test suite) the same arithmetic runs in numpy.
+L-BFGS-B evaluation is one omb_gp_lml_grad call — omb_gp_lml_grad_noise when the noise variance is
+free — (K, Cholesky, L⁻¹, Ky⁻¹ and the gradient sums in HIP; scipy's L-BFGS-B drives it on the
+host) and the final state is factorised in place by omb_gp_fit_state.  Without a GPU (the CPU test suite) the same arithmetic runs in numpy.
 ``predict`` — the hot path — runs on the GPU through the HIP posterior kernel
 (optimobo_amd.device); there is no CPU prediction path.
 """
@@ -323,35 +323,38 @@ def _thread_context(device):
     return per_dev[device]
 
 
-def _single_on_thread(device, X_dev, y_dev, ls, var, noise, kernel):
+def _single_on_thread(device, X_dev, y_dev, ls, var, noise, kernel, noise_grad=False):
     import torch
     from . import _lib
     ctx, stream = _thread_context(device)
     with torch.cuda.stream(stream):
         try:
-            lml, g, _ = ctx.gp_lml_grad(X_dev, y_dev, ls, var, noise, kernel)
+            lml, g, _ = ctx.gp_lml_grad(X_dev, y_dev, ls, var, noise, kernel, noise_grad=noise_grad)
             return lml, g, 0
         except _lib.OMBError as e:
             if e.code != _lib.OMB_ENOTPD:
                 raise
-            return 0.0, np.zeros(X_dev.shape[1] + 1), _lib.OMB_ENOTPD
+            return 0.0, np.zeros(X_dev.shape[1] + (2 if noise_grad else 1)), _lib.OMB_ENOTPD
 
 
-def _parallel_singles(ctx, X_dev, y_devs, lss, vs, noise, kernel):
+def _parallel_singles(ctx, X_dev, y_devs, lss, vs, noises, kernel, noise_grad=False):
     global _FIT_POOL
     with _FIT_POOL_LOCK:
         if _FIT_POOL is None:
             _FIT_POOL = concurrent.futures.ThreadPoolExecutor(max_workers=4, thread_name_prefix="omb-gp-fit")
     dev = ctx.device.index
-    futs = [_FIT_POOL.submit(_single_on_thread, dev, X_dev, y, ls, v, noise, kernel)
-            for y, ls, v in zip(y_devs, lss, vs)]
+    futs = [_FIT_POOL.submit(_single_on_thread, dev, X_dev, y, ls, v, nz, kernel, noise_grad)
+            for y, ls, v, nz in zip(y_devs, lss, vs, noises)]
     res = [f.result() for f in futs]
     return (np.array([r[0] for r in res]), np.stack([r[1] for r in res]), np.array([r[2] for r in res]))
 
 
 def _batched_objective(ctx, X_dev, y_devs, kernel, noise, models, ps):
-    """The optimize() objective (GPy Logexp parameters p → −log p(y), ∂/∂p) of several models at once."""
+    """The optimize() objective (GPy Logexp parameters p → −log p(y), ∂/∂p) of several models at once.
+    ``noise``: the fixed value the models share, or None when every model's noise is free (its own value, the
+    last free parameter, and one more gradient entry)."""
     from . import _lib
+    free = noise is None
     thetas, ths = [], []
     for m, p in zip(models, ps):
         th = _logexp(p)
@@ -361,11 +364,13 @@ def _batched_objective(ctx, X_dev, y_devs, kernel, noise, models, ps):
         ths.append(th)
     lss = [m.kern.ls_vector() for m in models]
     vs = [float(m.kern.variance) for m in models]
+    noises = [float(m.Gaussian_noise.variance) if free else noise for m in models]
     n, d = X_dev.shape
     if len(models) > 1 and not _one_launch(n, d):
-        lml, grad, status = _parallel_singles(ctx, X_dev, y_devs, lss, vs, noise, kernel)
+        lml, grad, status = _parallel_singles(ctx, X_dev, y_devs, lss, vs, noises, kernel, free)
     else:
-        lml, grad, _, status = ctx.gp_lml_grad_batch(X_dev, y_devs, np.stack(lss), vs, noise, kernel)
+        lml, grad, _, status = ctx.gp_lml_grad_batch(X_dev, y_devs, np.stack(lss), vs, noises if free else noise,
+                                                     kernel, noise_grad=free)
     out = []
     for q, m in enumerate(models):
         if status[q] == _lib.OMB_ENOTPD:
@@ -373,7 +378,9 @@ def _batched_objective(ctx, X_dev, y_devs, kernel, noise, models, ps):
         else:
             g = grad[q]
             nl = m.kern.lengthscale.values.size
-            gl = [g[0]] + ([float(np.sum(g[1:]))] if nl == 1 else list(g[1:1 + nl]))
+            gl = [g[0]] + ([float(np.sum(g[1:1 + d]))] if nl == 1 else list(g[1:1 + nl]))
+            if free:
+                gl.append(g[d + 1])
             f, g_log = -float(lml[q]), -np.asarray(gl)
         out.append((f, g_log * _logexp_gradfactor(ths[q]) / ths[q]))
     return out
@@ -384,7 +391,8 @@ class _LeanBatch:
     once (a BO iteration's fits make ~100 rounds of evaluations; at n ≈ 20 the kernel takes ~30 µs and the
     generic path's per-call conversions took twice that).  Each model's arithmetic is that of
     ``_batched_objective``: θ = log(Logexp(p)), σ_f² = exp(θ_0), ℓ = exp(θ_1..) (what ``_set_free`` stores
-    and ``ls_vector`` / ``float(variance)`` read back), the same gradient assembly."""
+    and ``ls_vector`` / ``float(variance)`` read back), the same gradient assembly.  ``noise`` None: every model's
+    noise is free, σ_n² = exp(θ_last) per model (omb_gp_lml_grad_noise_batch)."""
 
     def __init__(self, ctx, X_dev, y_devs, kernel, noise, models):
         import ctypes
@@ -392,7 +400,8 @@ class _LeanBatch:
         self.ctx, self.lib, self.h = ctx, ctx.lib, ctx._h
         self.n, self.d = X_dev.shape
         self.kid = {"matern52": _lib.KERNEL_MATERN52, "rbf": _lib.KERNEL_RBF}[kernel]
-        self.noise = float(noise)
+        self.free = noise is None
+        self.noise = 0.0 if self.free else float(noise)
         self.enotpd = _lib.OMB_ENOTPD
         self.X_ptr = ctypes.c_void_p(X_dev.data_ptr())
         self.y_addr = [y.data_ptr() for y in y_devs]
@@ -401,7 +410,9 @@ class _LeanBatch:
         self.ls = np.zeros((k, self.d))
         self.var = np.zeros(k)
         self.lml = np.zeros(k)
-        self.grad = np.zeros((k, self.d + 1))
+        self.G = self.d + 2 if self.free else self.d + 1
+        self.grad = np.zeros((k * self.G,))
+        self.nz = np.zeros(k)
         self.jit = np.zeros(k)
         self.status = np.zeros(k, np.int32)
         self.yptr = (ctypes.c_void_p * k)()
@@ -409,7 +420,7 @@ class _LeanBatch:
         dp = ctypes.POINTER(ctypes.c_double)
         self.a_ls, self.a_var = self.ls.ctypes.data_as(dp), self.var.ctypes.data_as(dp)
         self.a_lml, self.a_grad = self.lml.ctypes.data_as(dp), self.grad.ctypes.data_as(dp)
-        self.a_jit = self.jit.ctypes.data_as(dp)
+        self.a_jit, self.a_nz = self.jit.ctypes.data_as(dp), self.nz.ctypes.data_as(dp)
         self.a_status = ctypes.c_void_p(self.status.ctypes.data)
 
     def __call__(self, idx, ps):
@@ -419,21 +430,30 @@ class _LeanBatch:
             theta = np.log(th)
             self.var[q] = np.exp(theta[0])
             self.ls[q] = np.exp(theta[1:1 + self.nls[i]])
+            if self.free:
+                self.nz[q] = np.exp(theta[1 + self.nls[i]])
             self.yptr[q] = self.y_addr[i]
             ths.append(th)
             thetas.append(theta)
         self.ctx._stream()
-        self.ctx._check(self.lib.omb_gp_lml_grad_batch(
-            self.h, self.kid, len(idx), self.n, self.d, self.X_ptr, self.yptr_v, self.a_ls, self.a_var, self.noise,
-            self.a_lml, self.a_grad, self.a_jit, self.a_status), "omb_gp_lml_grad_batch")
+        if self.free:
+            self.ctx._check(self.lib.omb_gp_lml_grad_noise_batch(
+                self.h, self.kid, len(idx), self.n, self.d, self.X_ptr, self.yptr_v, self.a_ls, self.a_var, self.a_nz,
+                self.a_lml, self.a_grad, self.a_jit, self.a_status), "omb_gp_lml_grad_noise_batch")
+        else:
+            self.ctx._check(self.lib.omb_gp_lml_grad_batch(
+                self.h, self.kid, len(idx), self.n, self.d, self.X_ptr, self.yptr_v, self.a_ls, self.a_var, self.noise,
+                self.a_lml, self.a_grad, self.a_jit, self.a_status), "omb_gp_lml_grad_batch")
         out = []
         for q, i in enumerate(idx):
             if self.status[q] == self.enotpd:
                 f, g_log = 1e25, np.zeros_like(thetas[q])
             else:
-                g = self.grad[q]
+                g = self.grad[q * self.G:(q + 1) * self.G]
                 nl = self.nls[i]
-                gl = [g[0]] + ([float(np.sum(g[1:]))] if nl == 1 else list(g[1:1 + nl]))
+                gl = [g[0]] + ([float(np.sum(g[1:1 + self.d]))] if nl == 1 else list(g[1:1 + nl]))
+                if self.free:
+                    gl.append(g[self.d + 1])
                 f, g_log = -float(self.lml[q]), -np.asarray(gl)
             out.append((f, g_log * _logexp_gradfactor(ths[q]) / ths[q]))
         return out
@@ -441,18 +461,22 @@ class _LeanBatch:
 
 def fit_concurrently(models, device=None, max_f_eval=1000, max_iters=None, **kw):
     """``model.optimize(max_f_eval=…)`` for every model; in lockstep with batched device evaluations when
-    they are fitted on the GPU on the same inputs, else one after another."""
+    they are fitted on the GPU on the same inputs, else one after another.  The noise variances are all fixed
+    at one shared value or all free (each model fits its own); a mixed set runs one after another."""
     models = list(models)
     same_inputs = all(m.X.shape == models[0].X.shape and np.array_equal(m.X, models[0].X) for m in models)
+    all_fixed = all(m.Gaussian_noise.variance.fixed for m in models)
+    all_free = not any(m.Gaussian_noise.variance.fixed for m in models)
     if (len(models) < 2 or len(models) > 4 or not same_inputs or not _lockstep_ok() or
-            not all(m.device_fit and m.Gaussian_noise.variance.fixed for m in models) or
-            len({(m.kern.kind, float(m.Gaussian_noise.variance)) for m in models}) != 1):
+            not all(m.device_fit for m in models) or not (all_fixed or all_free) or
+            len({m.kern.kind for m in models}) != 1 or
+            (all_fixed and len({float(m.Gaussian_noise.variance) for m in models}) != 1)):
         return [m.optimize(max_f_eval=max_f_eval, max_iters=max_iters) for m in models]
     import torch
     ctx = _fit_context(device)
     X_dev = torch.as_tensor(models[0].X, device=ctx.device)
     y_devs = [torch.as_tensor(np.ascontiguousarray(m.Y[:, 0]), device=ctx.device) for m in models]
-    kernel, noise = models[0].kern.kind, float(models[0].Gaussian_noise.variance)
+    kernel, noise = models[0].kern.kind, (float(models[0].Gaussian_noise.variance) if all_fixed else None)
     torch.cuda.current_stream(ctx.device).synchronize()   # inputs ready for the pool threads' streams
     maxfun, maxiter = int(max_f_eval), int(max_iters or max_f_eval)
     p0 = [np.atleast_1d(_logexp_inv(np.exp(m._get_free()))).astype(np.float64) for m in models]
@@ -560,7 +584,8 @@ class GPRegression:
         self._state = None
 
     def _neg_lml_and_grad_device(self, theta):
-        """−log p(y) and its gradient from omb_gp_lml_grad (noise fixed, as every driver fits it)."""
+        """−log p(y) and its gradient from omb_gp_lml_grad, or from omb_gp_lml_grad_noise with the log-noise
+        entry appended when the noise variance is free."""
         import torch
         from . import _lib
         self._set_free(theta)
@@ -568,15 +593,19 @@ class GPRegression:
         if self._dev_xy is None:
             self._dev_xy = (torch.as_tensor(self.X, device=ctx.device), torch.as_tensor(self.Y[:, 0], device=ctx.device))
         Xd, yd = self._dev_xy
+        free = not self.Gaussian_noise.variance.fixed
+        d = self.X.shape[1]
         try:
             lml, g, _ = ctx.gp_lml_grad(Xd, yd, self.kern.ls_vector(), float(self.kern.variance),
-                                        float(self.Gaussian_noise.variance), self.kern.kind)
+                                        float(self.Gaussian_noise.variance), self.kern.kind, noise_grad=free)
         except _lib.OMBError as e:
             if e.code != _lib.OMB_ENOTPD:
                 raise
             return 1e25, np.zeros_like(theta)
         nl = self.kern.lengthscale.values.size
-        grad = [g[0]] + ([float(np.sum(g[1:]))] if nl == 1 else list(g[1:1 + nl]))
+        grad = [g[0]] + ([float(np.sum(g[1:1 + d]))] if nl == 1 else list(g[1:1 + nl]))
+        if free:
+            grad.append(g[d + 1])
         return -lml, -np.asarray(grad)
 
     def _neg_lml_and_grad(self, theta):
@@ -616,11 +645,11 @@ class GPRegression:
         GPy constrains σ_f², ℓ (and a free noise variance) positive with its Logexp transform,
         θ = log(1 + e^p), and runs L-BFGS-B on p without bounds; this does the same, with the
         log-marginal-likelihood gradient (taken w.r.t. log θ) carried to p by the chain factor
-        dθ/dp = 1 − e^(−θ)."""
+        dθ/dp = 1 − e^(−θ).  With ``device_fit`` every evaluation runs on the device, the noise fixed or
+        free; the numpy evaluation below is the CPU path and the specification."""
         theta0 = self._get_free()                       # log θ
         p0 = _logexp_inv(np.exp(theta0))
-        on_device = self.device_fit and self.Gaussian_noise.variance.fixed
-        inner = self._neg_lml_and_grad_device if on_device else self._neg_lml_and_grad
+        inner = self._neg_lml_and_grad_device if self.device_fit else self._neg_lml_and_grad
 
         def fun(p):
             th = _logexp(p)
@@ -688,6 +717,30 @@ class GPRegression:
         f = self.posterior_samples_f(X, size)
         noise = float(self.Gaussian_noise.variance)
         return f + np.sqrt(noise) * np.random.standard_normal(f.shape) if noise > 0 else f
+
+
+def check_noise_option(noise):
+    """The drivers' ``noise`` keyword: 0.0 (the reference's ``fix(0)``) or a positive float fixes the noise
+    variance there, "fit" leaves it free at GPy's initial 1.0; anything else is a ValueError."""
+    if isinstance(noise, str):
+        if noise != "fit":
+            raise ValueError(f"noise must be a float >= 0 or 'fit', not {noise!r}")
+        return noise
+    if isinstance(noise, bool) or not isinstance(noise, (int, float, np.integer, np.floating)):
+        raise ValueError(f"noise must be a float >= 0 or 'fit', not {noise!r}")
+    if not (np.isfinite(noise) and noise >= 0.0):
+        raise ValueError(f"noise must be a float >= 0 or 'fit', not {noise!r}")
+    return float(noise)
+
+
+def apply_noise_option(model, noise):
+    """Set ``model``'s noise variance as a checked ``noise`` option asks: fixed at the value, or free at 1.0."""
+    if noise == "fit":
+        model.Gaussian_noise.variance.values[:] = 1.0
+        model.Gaussian_noise.variance.unfix()
+    else:
+        model.Gaussian_noise.variance.fix(noise)
+    return model
 
 
 class kern:  # noqa: N801  — GPy.kern namespace look-alike

@@ -29,11 +29,11 @@ float run(const double* X, int n, const FitBatch& b, int reps) {
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
   hipLaunchKernelGGL((gp_lml_small_batch_kernel<2, OMB_KERNEL_MATERN52, ABL>), dim3(2), dim3(kSmallFitThreads), 0, 0, X,
-                     2, n, b, 1e-8);
+                     2, n, b);
   CK(hipEventRecord(e0));
   for (int i = 0; i < reps; ++i)
     hipLaunchKernelGGL((gp_lml_small_batch_kernel<2, OMB_KERNEL_MATERN52, ABL>), dim3(2), dim3(kSmallFitThreads), 0, 0,
-                       X, 2, n, b, 1e-8);
+                       X, 2, n, b);
   CK(hipEventRecord(e1));
   CK(hipEventSynchronize(e1));
   float ms;
@@ -60,6 +60,7 @@ int main() {
       b.y[p] = y + p * n;
       b.out[p] = out + p * 16;
       b.variance[p] = p ? 3.0 : 1e5;
+      b.base[p] = 1e-8;
       for (int j = 0; j < 8; ++j) b.ls[p][j] = p ? 0.9 : 1.7;
     }
     float t[4] = {0, 0, 0, 0};
