@@ -433,6 +433,27 @@ int omb_gp_lml_grad_noise_batch(omb_ctx* ctx, int kernel, int k, int n, int d, c
 int omb_gp_fit_state(omb_ctx* ctx, int obj, int kernel, int n, int d, const double* X_dev, const double* y_dev,
                      const double* lengthscale_host, double variance, double noise, double* jitter_used);
 
+/* ---------------------------------------------------------------------------------------
+ * Conditioning an installed state on more observations without a refit (sequential-greedy batch proposals with
+ * the Kriging believer; incremental conditioning on real observations between hyperparameter refits).
+ * Per point, with k = K(X, x), mu = k'alpha, v = L^-1 k, delta^2 = variance + noise + 1e-8 - v'v, w = L^-T v and
+ * zeta = (y - mu)/delta:  L^-1' = [[L^-1, 0], [-w'/delta, 1/delta]],  alpha' = [alpha - w zeta/delta ; zeta/delta],
+ * X' = [X ; x] -- two mat-vecs over the dense L^-1, O(n^2); fixed-order sums, bitwise repeatable.
+ * ------------------------------------------------------------------------------------- */
+/* Condition the installed state of objective obj on q more observations, one after another (point j sees points < j):
+ * Xnew_dev (q, d); ynew_dev (q) or NULL = Kriging believer (y_j = the posterior mean at x_j when it is appended);
+ * noise = the sigma_n^2 the state was factorised with (plus any jitchol jitter the caller knows of);
+ * mu_out_dev (q, may be NULL) receives that posterior mean of every point, var_out_dev (q, may be NULL) its delta^2_j.
+ * All or nothing: on any failure the installed state is what it was.  Synchronises.
+ *   OMB_ESTATE  objective not set
+ *   OMB_EINVAL  q < 1, null Xnew_dev, negative or non-finite noise
+ *   OMB_EUNSUP  n_train + q > OMB_MAX_TRAIN_DENSE
+ *   OMB_ENOTPD  a delta^2 that is not positive and finite (a duplicate of a training point at zero noise can round
+ *               below the jitter); omb_last_error names the 1-based index of the point
+ * A plan that is set stays set (plans hold acquisition geometry, not GP state). */
+int omb_gp_append(omb_ctx* ctx, int obj, int q, const double* Xnew_dev, const double* ynew_dev, double noise,
+                  double* mu_out_dev, double* var_out_dev);
+
 #ifdef __cplusplus
 }
 #endif

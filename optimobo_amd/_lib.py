@@ -95,6 +95,8 @@ SIGNATURES = {
     "omb_gp_lml_grad_noise": (_i, [_p, _i, _i, _i, _p, _p, _dp, _d, _d, _dp, _dp, _dp]),
     "omb_gp_lml_grad_noise_batch": (_i, [_p, _i, _i, _i, _i, _p, _p, _dp, _dp, _dp, _dp, _dp, _dp, _p]),
     "omb_gp_fit_state": (_i, [_p, _i, _i, _i, _i, _p, _p, _dp, _d, _d, _dp]),
+    # conditioning an installed state on more observations
+    "omb_gp_append": (_i, [_p, _i, _i, _p, _p, _d, _p, _p]),
 }
 
 

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import pareto
+from ._lib import OMB_ENOTPD, OMBError
 from .device import AcqContext
 from .gp import GPState
 from .parallel import global_argmax, shard_range, world
@@ -34,17 +35,62 @@ class AcquisitionEngine:
         self.ctx = AcqContext(device)
         self.device = self.ctx.device
         self._resident = {}
+        self._stale = set()     # objectives whose device state was conditioned on top of _resident[o]
+        self.condition_jitter = 0.0
         self.n_obj = 0
 
     # ------------------------------------------------------------------ model state
     def load_models(self, models):
         for o, m in enumerate(models):
             st = _state_of(m)
-            if self._resident.get(o) is not st:
+            if self._resident.get(o) is not st or o in self._stale:
                 self.ctx.set_gp_state(o, st)
                 self._resident[o] = st
+                self._stale.discard(o)
         self.n_obj = len(models)
         return self
+
+    def condition(self, Xnew, Y=None):
+        """Condition every loaded objective on the rows of Xnew (q, d) in place, without a refit
+        (AcqContext.gp_append): ``Y`` (q, n_obj) are their values, None the Kriging believer (each point takes
+        its posterior mean, so only σ² shrinks).  Returns the (q, n_obj) predictive means.
+
+        The noise of the bordered update is the resident state's ``noise``, plus ``DeviceGPState.jitter`` when
+        the device fit had to add one.  A host ``GPState`` does not record the jitter its jitchol escalated to;
+        for such a state the update is exact only when the first factorisation succeeded (the usual case).
+
+        A point the update cannot take at that noise (δ² ≤ 0: OMB_ENOTPD, the state untouched) — a proposal on
+        top of a training point under a large σ_f², where the 1e-8 jitter is far below the rounding of vᵀv — is
+        tried again with jitchol's escalation on the new points' diagonal, σ_n² + σ_f²·1e-6·10^t for t = 0..4
+        (the appended observations are then taken as that much noisier; the points already in the state keep
+        their factorisation).  ``condition_jitter`` holds the largest such addition of the last call (0.0 when
+        none was needed); the OMBError is raised when even t = 4 fails.
+
+        The touched entries are marked stale: the next ``load_models`` uploads the fitted state again even for
+        the same state object, so fantasies never reach the next iteration."""
+        Xnew = np.atleast_2d(np.asarray(Xnew, np.float64))
+        q = Xnew.shape[0]
+        if Y is not None:
+            Y = np.asarray(Y, np.float64).reshape(q, self.n_obj)
+        Xd = self._dev(Xnew)
+        mus = np.empty((q, self.n_obj))
+        self.condition_jitter = 0.0
+        for o in range(self.n_obj):
+            st = self._resident.get(o)
+            if st is None:
+                raise RuntimeError(f"condition: objective {o} holds no state (call load_models first)")
+            noise = float(getattr(st, "noise", 0.0)) + float(getattr(st, "jitter", None) or 0.0)
+            self._stale.add(o)
+            for t in range(-1, 5):
+                extra = 0.0 if t < 0 else float(st.variance) * 1e-6 * 10.0 ** t
+                try:
+                    mus[:, o], _ = self.ctx.gp_append(o, Xd, None if Y is None else Y[:, o], noise + extra)
+                    break
+                except OMBError as e:
+                    if e.code != OMB_ENOTPD or t == 4:
+                        raise
+            self.condition_jitter = max(self.condition_jitter, extra)
+        return mus
 
     def _dev(self, x):
         return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64), device=self.device)

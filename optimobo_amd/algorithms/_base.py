@@ -18,7 +18,7 @@ from ..result import Res
 
 class BODriver:
     def __init__(self, test_problem, ideal_point=None, max_point=None, mode="reference", n_candidates=1 << 14,
-                 refine_rounds=2, seed=None, device=None, polish=True, starts=None, noise=0.0):
+                 refine_rounds=2, seed=None, device=None, polish=True, starts=None, noise=0.0, batch_size=1):
         self.test_problem = test_problem
         self.max_point = max_point
         self.ideal_point = ideal_point
@@ -44,6 +44,12 @@ class BODriver:
         # the surrogates' noise variance (not in the reference, which fixes it at 0): 0.0 or a positive float
         # fixes it there, "fit" leaves it free for the hyperparameter search (GPy's own default)
         self.noise = check_noise_option(noise)
+        # points proposed per BO iteration (not in the reference, which proposes one).  MultiSurrogateOptimiser and
+        # MonoSurrogateOptimiser build a batch greedily with the Kriging believer (AcquisitionEngine.condition);
+        # the other drivers accept the keyword and ignore it.  1 is the reference's loop, call for call.
+        if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
+            raise ValueError(f"batch_size must be an integer >= 1, not {batch_size!r}")
+        self.batch_size = int(batch_size)
         self._iteration = 0
 
     def _objective_function(self, problem, x):
@@ -87,9 +93,12 @@ class BODriver:
         fit_concurrently(models, device=self.device, messages=False, max_f_eval=1000)
         return models
 
-    def _maximise(self, models, acq_fn):
-        """acq_fn None: the plan set on the engine (fused chain); else a batched callable."""
-        eng = engine_for(models, self.device)
+    def _maximise(self, models, acq_fn, eng=None):
+        """acq_fn None: the plan set on the engine (fused chain); else a batched callable.  ``eng``: the engine
+        to search on as it stands (a batch's later picks, whose states carry fantasies that loading ``models``
+        again would undo); None loads ``models``."""
+        if eng is None:
+            eng = engine_for(models, self.device)
         seed = (self.seed if self.seed is not None else np.random.randint(0, 2 ** 31 - 1)) + 7919 * self._iteration
         self._iteration += 1
         return eng.maximise(acq_fn, self.test_problem.xl, self.test_problem.xu, n_candidates=self.n_candidates,

@@ -59,7 +59,8 @@ def _penalise(aggregated, gsample, mask, feasible_pairs, infeasible_pairs, n_var
 
 
 class ParEGO_C1(BODriver):  # noqa: N801 — reference class name
-    """ParEGO-C1: penalised scalarisation, subset selection, EI on the scalarised model."""
+    """ParEGO-C1: penalised scalarisation, subset selection, EI on the scalarised model.
+    ``batch_size`` is accepted through ``BODriver`` and ignored: one proposal per iteration, as in the reference (ParEGO_C2 likewise)."""
 
     _rows_have_g = False      # C1 keeps [X | y | S] rows, C2 [X | y | g | S]
 

@@ -10,6 +10,8 @@ from ._base import BODriver
 
 
 class EMO(BODriver):
+    """emo.py:244-328.  ``batch_size`` is accepted through ``BODriver`` and ignored: one proposal per iteration, as in the reference."""
+
     def decompose_into_cells(self, data_points):
         """emo.py:55-152 (2 objectives)."""
         return pareto.decompose_into_cells(data_points, self.ideal_point, self.max_point)

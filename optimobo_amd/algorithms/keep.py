@@ -17,6 +17,8 @@ from ._base import BODriver
 
 
 class KEEP(BODriver):
+    """keep.py.  ``batch_size`` is accepted through ``BODriver`` and ignored: one proposal per iteration, as in the reference."""
+
     acq_search = "ea"
     def _expected_improvement(self, X, model, opt_value, kappa=0.01):
         """keep.py:118-137 (σ = sqrt(σ² + 1e-6)); X (d,) → (1,), X (N, d) → (N,)."""

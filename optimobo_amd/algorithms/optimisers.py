@@ -39,6 +39,12 @@ class MultiSurrogateOptimiser(BODriver):
         """optimisers.py:91-119 on the device: returns (x, −EHVI(x))."""
         from ..acquisition import engine_for
         eng = engine_for(models, self.device)
+        self._plan_EHVI(eng, function, max_point, pf, cache)
+        x, v = self._maximise(models, None)
+        return x, -v
+
+    def _plan_EHVI(self, eng, function, max_point, pf, cache):
+        """The EHVI plan of one proposal on ``eng``: 2-D, Monte-Carlo or exact, as mode and n_obj ask."""
         mc = function == "EHVI_3D" or self.n_obj >= 3          # optimisers.py:245-248: EHVI_3D for n_obj != 2
         if mc and self.mode == "textbook" and self.n_obj <= 3:
             eng.plan_ehvi_exact(max_point, pf)          # exact EHVI in place of the MC estimate (k = 2, 3)
@@ -48,8 +54,6 @@ class MultiSurrogateOptimiser(BODriver):
             eng.plan_ehvi3d(max_point, pf, cache)       # the reference's Monte-Carlo form, any k ≥ 3
         else:
             eng.plan_ehvi(max_point, pf, cache, mode=self.mode)
-        x, v = self._maximise(models, None)
-        return x, -v
 
     def _plan_exact_kd(self, eng, max_point, pf, cache):
         """Plans the exact EHVI at n_obj ≥ 4; when the box budget or the kernel's grid limit rules it out, the
@@ -78,6 +82,10 @@ class MultiSurrogateOptimiser(BODriver):
         return x, -v, ref_dir
 
     def solve(self, budget=100, n_init_samples=5, sample_exponent=5, acquisition_func=None):
+        """``budget`` true evaluations.  With ``batch_size`` q > 1 they come in ⌈budget/q⌉ iterations of q proposals
+        (the last one truncated), one ``hypervolume_convergence`` entry per iteration: see ``_solve_batched``."""
+        if self.batch_size > 1:
+            return self._solve_batched(budget, n_init_samples, sample_exponent, acquisition_func)
         problem = self.test_problem
         Xsample, ysample = self._initial_samples(n_init_samples)
         cached_samples = self._get_cached_samples(self.n_obj, sample_exponent)
@@ -99,6 +107,46 @@ class MultiSurrogateOptimiser(BODriver):
             y_next = self._objective_function(problem, X_next)
             ysample = np.vstack((ysample, y_next))
             Xsample = np.vstack((Xsample, X_next))
+        return self._result(ysample, Xsample, hypervolume_convergence, n_init_samples)
+
+    def _solve_batched(self, budget, n_init_samples, sample_exponent, acquisition_func):
+        """Sequential-greedy batches with the Kriging believer: one fit per iteration; every pick plans the
+        acquisition from the samples plus the fantasies so far (front, or the scalarisation's minimum under a fresh
+        reference direction) and maximises it; before the next pick the resident GPs are conditioned on the point
+        with their own posterior mean as its value (AcquisitionEngine.condition: μ stays, σ² collapses around the
+        pick, so the next arg-max moves on).  The picks are then evaluated for real; the next iteration's fit
+        uploads the fitted states again, so no fantasy outlives its batch."""
+        from ..acquisition import engine_for
+        problem = self.test_problem
+        q = self.batch_size
+        Xsample, ysample = self._initial_samples(n_init_samples)
+        cached_samples = self._get_cached_samples(self.n_obj, sample_exponent)
+        ref_dirs = get_reference_directions("das-dennis", self.n_obj, n_partitions=100)
+        hypervolume_convergence = []
+        done = 0
+        while done < budget:
+            b = min(q, budget - done)
+            self._update_bounds(ysample, acquisition_func)
+            hypervolume_convergence.append(self._hypervolume(ysample))
+            models = self._fit_many(Xsample, ysample[:, :problem.n_obj])
+            eng = engine_for(models, self.device)
+            yfant, picks = ysample[:, :problem.n_obj], []
+            for p in range(b):
+                ref_dir = np.asarray(ref_dirs[np.random.randint(0, len(ref_dirs))])
+                if acquisition_func is None:
+                    fn = "EHVI" if problem.n_obj == 2 else "EHVI_3D"
+                    self._plan_EHVI(eng, fn, self.max_point, pareto.calc_pf(yfant), cached_samples)
+                else:
+                    min_scalar = np.min([acquisition_func(y, ref_dir) for y in yfant])
+                    eng.plan_expected_decomposition(ref_dir, acquisition_func, min_scalar, cached_samples)
+                x, _ = self._maximise(models, None, eng=eng)
+                picks.append(x)
+                if p + 1 < b:
+                    yfant = np.vstack((yfant, eng.condition(x[None, :])))
+            for x in picks:
+                ysample = np.vstack((ysample, self._objective_function(problem, x)))
+                Xsample = np.vstack((Xsample, x))
+            done += b
         return self._result(ysample, Xsample, hypervolume_convergence, n_init_samples)
 
 
@@ -123,6 +171,9 @@ class MonoSurrogateOptimiser(BODriver):
         return (data - np.min(data)) / (np.max(data) - np.min(data))
 
     def solve(self, aggregation_func, budget=100, n_init_samples=5):
+        """``budget`` true evaluations; with ``batch_size`` q > 1 in ⌈budget/q⌉ iterations (``_solve_batched``)."""
+        if self.batch_size > 1:
+            return self._solve_batched(aggregation_func, budget, n_init_samples)
         problem = self.test_problem
         weights = np.asarray([1 / problem.n_obj] * problem.n_obj)
         Xsample, ysample = self._initial_samples(n_init_samples)
@@ -141,4 +192,40 @@ class MonoSurrogateOptimiser(BODriver):
             ref_dir = ref_dirs[np.random.randint(0, len(ref_dirs))]
             aggregated_samples = np.append(aggregated_samples, aggregation_func(next_y, ref_dir))
             Xsample = np.vstack((Xsample, next_X))
+        return self._result(ysample, Xsample, hypervolume_convergence, n_init_samples)
+
+    def _solve_batched(self, aggregation_func, budget, n_init_samples):
+        """Sequential-greedy batches with the Kriging believer (see MultiSurrogateOptimiser._solve_batched): one
+        fit per iteration; every pick's ``current_best`` is the minimum over the true and the fantasised
+        aggregated values, and the resident GP is conditioned on the pick with its posterior mean before the next."""
+        from ..acquisition import engine_for
+        problem = self.test_problem
+        q = self.batch_size
+        weights = np.asarray([1 / problem.n_obj] * problem.n_obj)
+        Xsample, ysample = self._initial_samples(n_init_samples)
+        self._update_bounds(ysample, aggregation_func)
+        aggregated_samples = np.asarray([aggregation_func(i, weights) for i in ysample]).flatten()
+        ref_dirs = get_reference_directions("das-dennis", problem.n_obj, n_partitions=100)
+        hypervolume_convergence = []
+        done = 0
+        while done < budget:
+            b = min(q, budget - done)
+            self._update_bounds(ysample, aggregation_func)
+            hypervolume_convergence.append(self._hypervolume(ysample))
+            model = self._fit(Xsample, aggregated_samples)
+            eng = engine_for([model], self.device)
+            fant, picks = aggregated_samples, []
+            for p in range(b):
+                eng.plan_ei(fant[np.argmin(fant)], 0.0)
+                x, _ = self._maximise([model], None, eng=eng)
+                picks.append(x)
+                if p + 1 < b:
+                    fant = np.append(fant, eng.condition(x[None, :])[0, 0])
+            for x in picks:
+                next_y = self._objective_function(problem, x)
+                ysample = np.vstack((ysample, next_y))
+                ref_dir = ref_dirs[np.random.randint(0, len(ref_dirs))]
+                aggregated_samples = np.append(aggregated_samples, aggregation_func(next_y, ref_dir))
+                Xsample = np.vstack((Xsample, x))
+            done += b
         return self._result(ysample, Xsample, hypervolume_convergence, n_init_samples)

@@ -16,6 +16,8 @@ from ._base import BODriver
 
 
 class ParEGO(BODriver):
+    """parego.py:148-298.  ``batch_size`` is accepted through ``BODriver`` and ignored: one proposal per iteration, as in the reference."""
+
     acq_search = "ea"
     def _expected_improvement(self, X, model, opt_value, kappa=0.01):
         """parego.py:126-145; X (d,) → (1,), X (N, d) → (N,)."""

@@ -17,9 +17,11 @@ struct ObjState {
   bool set = false;
   int n = 0, d = 0, DP = 0, R = 0, n_pad = 0, kind = 0;
   double variance = 0.0;
-  double* buf = nullptr;  // one allocation: Xs | xsq | alpha | ls | Lp | Ld
+  double* buf = nullptr;  // one allocation: Xs | xsq | alpha | ls | Lp | Ld | Xf | X
   size_t cap = 0;         // bytes
   const double* Ld = nullptr;  // dense row-major L⁻¹ (n, n): the full-covariance path's GEMM operand
+  const double* Xraw = nullptr;  // unscaled inputs (n, d) and the host ℓ: what omb_gp_append packs the grown state from
+  double ls[OMB_MAX_DIM] = {};
   GPDev dev{};
 };
 
@@ -86,6 +88,9 @@ struct omb_ctx {
   // gradient chain (omb_posterior_grad / omb_eval_grad): ∂a/∂μ | ∂a/∂σ² | K* | V | w per objective
   void* gws = nullptr;
   size_t gws_cap = 0;
+  // omb_gp_append: the bordered state (AppendWs)
+  void* aws = nullptr;
+  size_t aws_cap = 0;
   // device fault word (pinned, mapped host memory): kernels mark it, enter() reports it
   int* fault_host = nullptr;
   int* fault_dev = nullptr;
@@ -429,6 +434,7 @@ int omb_destroy(omb_ctx* ctx) {
   if (ctx->fws) (void)hipFree(ctx->fws);
   if (ctx->dws) (void)hipFree(ctx->dws);
   if (ctx->gws) (void)hipFree(ctx->gws);
+  if (ctx->aws) (void)hipFree(ctx->aws);
   if (ctx->fault_host) (void)hipHostFree(ctx->fault_host);
   if (ctx->fit_host) (void)hipHostFree(ctx->fit_host);
   for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
@@ -517,49 +523,45 @@ int omb_debug_set(omb_ctx* ctx, int what, int64_t value) {
 
 const char* omb_last_error(const omb_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
-int omb_set_gp(omb_ctx* ctx, int obj, int kernel, int n, int d, const double* X_dev, const double* lengthscale_host,
-               double variance, const double* alpha_dev, const double* Linv_dev) {
-  int rc = enter(ctx);
-  if (rc) return rc;
-  if ((rc = check_gp_args(E(ctx), obj, kernel, n, d, X_dev, lengthscale_host, variance, alpha_dev, Linv_dev)))
-    return rc;
+// Bytes of one objective's buffer at n points, and the packing of a state into it (omb_set_gp, omb_gp_append).
+static size_t gp_state_bytes(int n, int d) {
+  const int DP = pad_dim(d);
+  const int R = (n + 15) / 16;
+  const int n_pad = kChunkRows * ((R + 3) / 4);
+  const int R_pack = (n <= OMB_MAX_TRAIN) ? R : 0;   // the packed L⁻¹ feeds only the fused kernel
+  const size_t doubles = (size_t)n_pad * DP + 2 * (size_t)n_pad + DP + (size_t)packed_L_size(R_pack) + (size_t)n * n +
+                         (size_t)packed_X_size(n_pad, DP) + (size_t)n * d;
+  return doubles * sizeof(double);
+}
 
-  ObjState& s = ctx->obj[obj];
-  // The previous state may still be read by queued kernels.
-  OMB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+// Packs (X, ℓ, α, L⁻¹) of n points into buf (≥ gp_state_bytes(n, d)) on the stream and makes it the state of s;
+// s.buf / s.cap are the caller's business.
+static hipError_t install_gp(omb_ctx* ctx, ObjState& s, double* buf, int kernel, int n, int d, const double* X_dev,
+                             const double* lengthscale_host, double variance, const double* alpha_dev,
+                             const double* Linv_dev) {
   const int DP = pad_dim(d);
   const int R = (n + 15) / 16;
   const int Q = (R + 3) / 4;
   const int n_pad = kChunkRows * Q;
-  const int R_pack = (n <= OMB_MAX_TRAIN) ? R : 0;   // the packed L⁻¹ feeds only the fused kernel
-  const size_t doubles = (size_t)n_pad * DP + 2 * (size_t)n_pad + DP + (size_t)packed_L_size(R_pack) + (size_t)n * n +
-                         (size_t)packed_X_size(n_pad, DP);
-  const size_t bytes = doubles * sizeof(double);
-  if (bytes > s.cap) {
-    if (s.buf) (void)hipFree(s.buf);
-    s.buf = nullptr;
-    s.cap = 0;
-    if (hipMalloc(&s.buf, bytes) != hipSuccess) {
-      s.set = false;
-      return fail(ctx, OMB_ENOMEM, "hipMalloc(%zu) for objective %d", bytes, obj);
-    }
-    s.cap = bytes;
-  }
-  double* Xs = s.buf;
+  const int R_pack = (n <= OMB_MAX_TRAIN) ? R : 0;
+  double* Xs = buf;
   double* xsq = Xs + (size_t)n_pad * DP;
   double* alpha_p = xsq + n_pad;
   double* ls_p = alpha_p + n_pad;
   double* Lp = ls_p + DP;
   double* Ld = Lp + packed_L_size(R_pack);
   double* Xf = Ld + (size_t)n * n;
+  double* Xraw = Xf + (size_t)packed_X_size(n_pad, DP);
   hipError_t e = launch_pack_gp(ctx->stream, n, d, DP, X_dev, lengthscale_host, alpha_dev, Linv_dev, Xs, xsq,
                                 alpha_p, Lp, R_pack, n_pad);
   if (e == hipSuccess) e = launch_pack_x(ctx->stream, d, DP, n_pad, Xs, xsq, Xf);
   if (e == hipSuccess)
     e = hipMemcpyAsync(Ld, Linv_dev, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToDevice, ctx->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(Xraw, X_dev, sizeof(double) * (size_t)n * d, hipMemcpyDeviceToDevice, ctx->stream);
   if (e != hipSuccess) {
     s.set = false;
-    return hip_fail(ctx, e, "pack_gp");
+    return e;
   }
   s.set = true;
   s.n = n;
@@ -570,7 +572,96 @@ int omb_set_gp(omb_ctx* ctx, int obj, int kernel, int n, int d, const double* X_
   s.kind = kernel;
   s.variance = variance;
   s.Ld = Ld;
+  s.Xraw = Xraw;
+  for (int j = 0; j < d; ++j) s.ls[j] = lengthscale_host[j];
   s.dev = GPDev{Xs, xsq, alpha_p, Lp, ls_p, variance, n, R, kernel, 0, Xf};
+  return hipSuccess;
+}
+
+int omb_set_gp(omb_ctx* ctx, int obj, int kernel, int n, int d, const double* X_dev, const double* lengthscale_host,
+               double variance, const double* alpha_dev, const double* Linv_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if ((rc = check_gp_args(E(ctx), obj, kernel, n, d, X_dev, lengthscale_host, variance, alpha_dev, Linv_dev)))
+    return rc;
+
+  ObjState& s = ctx->obj[obj];
+  // The previous state may still be read by queued kernels.
+  OMB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const size_t bytes = gp_state_bytes(n, d);
+  if (bytes > s.cap) {
+    if (s.buf) (void)hipFree(s.buf);
+    s.buf = nullptr;
+    s.cap = 0;
+    if (hipMalloc(&s.buf, bytes) != hipSuccess) {
+      s.set = false;
+      return fail(ctx, OMB_ENOMEM, "hipMalloc(%zu) for objective %d", bytes, obj);
+    }
+    s.cap = bytes;
+  }
+  hipError_t e = install_gp(ctx, s, s.buf, kernel, n, d, X_dev, lengthscale_host, variance, alpha_dev, Linv_dev);
+  if (e != hipSuccess) return hip_fail(ctx, e, "pack_gp");
+  return OMB_OK;
+}
+
+int omb_gp_append(omb_ctx* ctx, int obj, int q, const double* Xnew_dev, const double* ynew_dev, double noise,
+                  double* mu_out_dev, double* var_out_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (obj < 0 || obj >= OMB_MAX_OBJ || !ctx->obj[obj].set) return fail(ctx, OMB_ESTATE, "objective %d not set", obj);
+  if (q < 1) return fail(ctx, OMB_EINVAL, "q=%d must be >= 1", q);
+  if (!Xnew_dev) return fail(ctx, OMB_EINVAL, "null Xnew_dev");
+  if (!(noise >= 0.0) || !(noise <= 1.79769313486231570815e308))
+    return fail(ctx, OMB_EINVAL, "noise=%g must be finite and >= 0", noise);
+  ObjState& s = ctx->obj[obj];
+  const int n = s.n, d = s.d, DP = s.DP;
+  if ((int64_t)n + q > OMB_MAX_TRAIN_DENSE)
+    return fail(ctx, OMB_EUNSUP, "n_train + q = %lld above %d", (long long)n + q, OMB_MAX_TRAIN_DENSE);
+  const int m = n + q;
+  if ((rc = grow_dev(ctx, &ctx->aws, &ctx->aws_cap, sizeof(double) * (size_t)append_ws_doubles(m, d, DP),
+                     "append workspace")))
+    return rc;
+  AppendWs ws;
+  append_ws_carve(static_cast<double*>(ctx->aws), m, d, DP, &ws);
+  hipStream_t st = ctx->stream;
+  const auto d2d = hipMemcpyDeviceToDevice;
+  // the installed state into the bordered copy; the new rows scaled by the kernel that packs every state's rows
+  OMB_HIP(ctx, hipMemsetAsync(ws.info, 0, sizeof(int), st));
+  OMB_HIP(ctx, hipMemcpyAsync(ws.alpha, s.dev.alpha, sizeof(double) * n, d2d, st));
+  OMB_HIP(ctx, hipMemcpyAsync(ws.Xs, s.dev.Xs, sizeof(double) * (size_t)n * DP, d2d, st));
+  OMB_HIP(ctx, hipMemcpyAsync(ws.xsq, s.dev.xsq, sizeof(double) * n, d2d, st));
+  OMB_HIP(ctx, hipMemcpyAsync(ws.X, s.Xraw, sizeof(double) * (size_t)n * d, d2d, st));
+  OMB_HIP(ctx, hipMemcpyAsync(ws.X + (size_t)n * d, Xnew_dev, sizeof(double) * (size_t)q * d, d2d, st));
+  OMB_HIP(ctx, launch_pack_gp(st, q, d, DP, Xnew_dev, s.ls, Xnew_dev, nullptr, ws.Xs + (size_t)n * DP, ws.xsq + n,
+                              ws.scratch, nullptr, 0, q));
+  OMB_HIP(ctx, launch_append_restride(st, ws, n, s.Ld));
+  for (int j = 0; j < q; ++j)
+    OMB_HIP(ctx, launch_append_point(st, ws, s.kind, s.variance, n + j, j, ynew_dev, noise, mu_out_dev, var_out_dev));
+  OMB_HIP(ctx, hipMemcpyAsync(ctx->info_host, ws.info, sizeof(int), hipMemcpyDeviceToHost, st));
+  OMB_HIP(ctx, hipStreamSynchronize(st));
+  if (ctx->info_host[0] != 0)
+    return fail(ctx, OMB_ENOTPD, "point %d: delta^2 = variance + noise + 1e-8 - v'v is not positive (the state is "
+                "unchanged)", ctx->info_host[0]);
+  // the grown state through omb_set_gp's packing, into a new buffer where the old one is too small (it is released
+  // only once the new one stands, so a failed allocation leaves the installed state as it was)
+  double* buf = s.buf;
+  double* old = nullptr;
+  const size_t need = gp_state_bytes(m, d);
+  if (need > s.cap) {
+    const int room = m + 64 < OMB_MAX_TRAIN_DENSE ? m + 64 : OMB_MAX_TRAIN_DENSE;   // further appends without a malloc
+    size_t cap = gp_state_bytes(room, d);
+    if (cap < need) cap = need;
+    if (hipMalloc(&buf, cap) != hipSuccess) return fail(ctx, OMB_ENOMEM, "hipMalloc(%zu) for objective %d", cap, obj);
+    old = s.buf;
+    s.buf = buf;
+    s.cap = cap;
+  }
+  double ls[OMB_MAX_DIM];
+  for (int j = 0; j < d; ++j) ls[j] = s.ls[j];
+  hipError_t e = install_gp(ctx, s, buf, s.kind, m, d, ws.X, ls, s.variance, ws.alpha, ws.L);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);   // the workspace is free again, and so is the old buffer
+  if (old) (void)hipFree(old);
+  if (e != hipSuccess) return hip_fail(ctx, e, "append install");
   return OMB_OK;
 }
 

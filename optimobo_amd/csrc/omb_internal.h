@@ -293,6 +293,33 @@ hipError_t launch_ehvi_boxes_grad(hipStream_t stream, int k, const double* mu, c
                                   int64_t N, const double* coords, int C, const uint16_t* boxes, int B, double* dadm,
                                   double* dadv);
 
+// ---------------------------------------------------------------------------------------
+// Conditioning an installed state on more observations (omb_append.hip): omb_gp_append.
+// The bordered state of m = n + q points as the kernels grow it, carved from one workspace.
+struct AppendWs {
+  double* L;        // (m, m) row-major L⁻¹, zeros above the diagonal
+  double* alpha;    // (m)
+  double* Xs;       // (m, DP) inputs / ℓ as pack_rows_kernel writes them
+  double* xsq;      // (m)
+  double* X;        // (m, d) unscaled inputs
+  double* kvec;     // (m) k = K(X, x) of the point being appended
+  double* v;        // (m) v = L⁻¹k
+  double* wpart;    // (⌈m/256⌉, m) partial sums of w = L⁻ᵀv
+  double* mupart;   // (⌈m/256⌉) partial sums of μ = k·α
+  double* scal;     // {δ, ζ/δ}
+  int* info;        // 0, or the 1-based index of the first point whose δ² is not positive and finite
+  double* scratch;  // (m + DP) pack_rows_kernel's α / ℓ outputs for the new rows (not used)
+  int m, d, DP;
+};
+int64_t append_ws_doubles(int m, int d, int DP);
+void append_ws_carve(double* base, int m, int d, int DP, AppendWs* ws);
+// ws.L ← the lower triangle of Ld (n, n), re-strided to pitch m, zeros elsewhere
+hipError_t launch_append_restride(hipStream_t stream, const AppendWs& ws, int n, const double* Ld);
+// point j of the call (row c = n + j of ws.Xs / ws.xsq, already scaled) joins the c points of ws: row c of ws.L,
+// ws.alpha updated; ynew null = the Kriging believer (y = μ); mu_out[j] = μ, var_out[j] = δ² (either may be null)
+hipError_t launch_append_point(hipStream_t stream, const AppendWs& ws, int kind, double variance, int c, int j,
+                               const double* ynew, double noise, double* mu_out, double* var_out);
+
 // Packed-L^-1 size in doubles for R row tiles: Σ_{r<R} 4(r+1)·64 = 128·R·(R+1).
 inline int64_t packed_L_size(int R) { return 128ll * R * (R + 1); }
 // k-step pairs of the training-row A fragments [x/ℓ, ‖x/ℓ‖², 1]: ⌈⌈(DP+2)/4⌉/2⌉

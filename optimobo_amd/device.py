@@ -445,6 +445,31 @@ class AcqContext:
         self.gp_info[obj] = dict(n=n, d=d, variance=float(variance), kernel=kernel)
         return jit.value
 
+    def gp_append(self, obj, Xnew, ynew=None, noise=0.0):
+        """Condition objective ``obj``'s installed state on the rows of Xnew (q, d), one after another, without a
+        refit (omb_gp_append).  ``ynew`` (q,) are their observed values; None is the Kriging believer: each point
+        takes the posterior mean it has when it is appended, so the mean surface stays and only σ² shrinks.
+        ``noise``: the σ_n² the state was factorised with (plus jitchol's jitter, where known).  Returns
+        (mu (q,), delta2 (q,)) as numpy: every point's predictive mean and δ² = σ² + σ_n² + 1e-8 at its turn.
+        OMBError (OMB_ENOTPD) for a δ² ≤ 0, the installed state then being what it was."""
+        Xnew = _dev_f64(Xnew, self.device)
+        if Xnew.dim() == 1:
+            Xnew = Xnew.reshape(1, -1)
+        self._check_width(Xnew, obj)
+        q = Xnew.shape[0]
+        y = None
+        if ynew is not None:
+            y = _dev_f64(ynew, self.device).reshape(-1)
+            if y.shape[0] != q:
+                raise ValueError(f"gp_append: {y.shape[0]} values for {q} points")
+        mu = torch.empty(max(q, 1), dtype=torch.float64, device=self.device)
+        d2 = torch.empty_like(mu)
+        self._stream()
+        self._check(self.lib.omb_gp_append(self._h, int(obj), q, _ptr(Xnew), _ptr(y) if y is not None else None,
+                                           float(noise), _ptr(mu), _ptr(d2)), "omb_gp_append")
+        self.gp_info[obj]["n"] += q
+        return mu[:q].cpu().numpy(), d2[:q].cpu().numpy()
+
     # ------------------------------------------------------------------ Thompson sampling (TuRBO)
     def posterior_cov(self, obj, Xc, out=None):
         """μ (N,), Σ (N, N): GPy predict(Xc, full_cov=True) of objective ``obj`` (σ_n² = 0)."""
