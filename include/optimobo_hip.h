@@ -127,7 +127,11 @@ const char* omb_last_error(const omb_ctx* ctx);
  * variance the planned acquisition loads — objective 0 alone for reference-mode EHVI-2D, Monte-Carlo EHVI, expected
  * decomposition and the plain / Pareto EI, whose reference uses σ²₀ for every objective; all of them for the other
  * plans — and μ of the rest without the triangular product V = L⁻¹K*.  Values and arg-max pairs are bit-identical
- * either way; omb_posterior and omb_eval_grad always compute every σ². */
+ * either way; omb_posterior and omb_eval_grad always compute every σ².
+ * omb_debug_set(ctx, OMB_DEBUG_POSTERIOR_MEAN_KERNEL, m) picks where μ of those masked objectives is computed when
+ * n_var ≤ 8 and some n_train > 128: 1 (default) in a small kernel of its own (one wavefront per 16 candidates, no LDS
+ * ring, no barriers) launched after the posterior kernel, which then covers the unmasked objectives only; 2 the same
+ * kernel launched before it; 0 inside the posterior launch, by its mean-only workgroups.  μ is bit-identical. */
 enum {
   OMB_DEBUG_SPIN_LIMIT = 1,
   OMB_DEBUG_COV_TABLE = 2,
@@ -139,7 +143,8 @@ enum {
   OMB_DEBUG_SELECT_SEQ = 9,
   OMB_DEBUG_SYRK_GLDS = 10,
   OMB_DEBUG_BOXES_KD = 11,
-  OMB_DEBUG_POSTERIOR_ALL_VAR = 12
+  OMB_DEBUG_POSTERIOR_ALL_VAR = 12,
+  OMB_DEBUG_POSTERIOR_MEAN_KERNEL = 13
 };
 int omb_debug_set(omb_ctx* ctx, int what, int64_t value);
 

@@ -31,6 +31,7 @@ DEBUG_SELECT_SEQ = 9
 DEBUG_SYRK_GLDS = 10
 DEBUG_BOXES_KD = 11
 DEBUG_POSTERIOR_ALL_VAR = 12
+DEBUG_POSTERIOR_MEAN_KERNEL = 13
 MAX_OBJ, MAX_DIM, MAX_TRAIN, MAX_TRAIN_DENSE = 8, 256, 1024, 16384
 
 _p = ctypes.c_void_p

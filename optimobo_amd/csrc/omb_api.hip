@@ -111,6 +111,7 @@ struct omb_ctx {
   bool select_seq = false;       // OMB_DEBUG_SELECT_SEQ: the sequential greedy walk for B ≤ 64 too
   bool boxes_kd_wave = false;    // OMB_DEBUG_BOXES_KD: omb_ehvi_boxes_k by one wavefront per candidate where that fits
   bool posterior_all_var = false;  // OMB_DEBUG_POSTERIOR_ALL_VAR: the chain computes σ² of every objective
+  int posterior_mean_kernel = kMeanKernelAfter;   // OMB_DEBUG_POSTERIOR_MEAN_KERNEL: masked objectives' μ in a launch of its own
 };
 
 namespace {
@@ -238,7 +239,7 @@ hipError_t posterior_any(omb_ctx* ctx, const GPArgs& args, const double* const* 
                          const double* Xc, int64_t N, double* mu, double* var) {
   // the fused kernel keeps the candidates' B fragments in registers: n_var ≤ 64 (kMaxFusedDP)
   if (16 * max_R <= OMB_MAX_TRAIN && args.DP <= kMaxFusedDP)
-    return launch_posterior(ctx->stream, args, n_obj, max_R, Xc, N, mu, var);
+    return launch_posterior(ctx->stream, args, n_obj, max_R, Xc, N, mu, var, ctx->posterior_mean_kernel);
   // the dense path ignores args.var_skip: it computes σ² of every objective
   for (int o = 0; o < n_obj; ++o) {
     const int64_t n = args.gp[o].n;
@@ -506,6 +507,13 @@ int omb_debug_set(omb_ctx* ctx, int what, int64_t value) {
   }
   if (what == OMB_DEBUG_POSTERIOR_ALL_VAR) {
     ctx->posterior_all_var = value != 0;
+    return OMB_OK;
+  }
+  if (what == OMB_DEBUG_POSTERIOR_MEAN_KERNEL) {
+    if (value < 0 || value > 2)
+      return fail(ctx, OMB_EINVAL, "posterior mean kernel %lld (0 off, 1 after the posterior launch, 2 before it)",
+                  (long long)value);
+    ctx->posterior_mean_kernel = (int)value;
     return OMB_OK;
   }
   if (what == OMB_DEBUG_CHOL_MODE) {

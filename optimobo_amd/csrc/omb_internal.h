@@ -42,7 +42,15 @@ struct GPArgs {
   // generation and μ as always, no V = L⁻¹K*, var_out untouched).  The complement of the plan's var_mask, so that
   // zeroed arguments compute everything.
   unsigned var_skip;
+  // non-zero: the launch covers the objectives whose bits are set and blockIdx.y counts them in ascending order (set
+  // by launch_posterior where it gives the masked objectives' μ a launch of its own); 0: objective blockIdx.y
+  unsigned obj_sel;
 };
+
+// launch_posterior's mean_kernel argument (OMB_DEBUG_POSTERIOR_MEAN_KERNEL): μ of the objectives in var_skip by
+// posterior_mean_kernel after (default) or before the launch that computes the others' μ and σ², or — off — inside
+// that launch, by its kernels' mean-only path
+enum { kMeanKernelOff = 0, kMeanKernelAfter = 1, kMeanKernelBefore = 2 };
 
 constexpr int kFaultSpin = 1;          // fault word bit: posterior counter-ring wait exhausted
 constexpr int kDefaultSpinLimit = 1 << 22;
@@ -60,7 +68,7 @@ hipError_t launch_kernel_block(hipStream_t stream, const GPArgs& args, int obj, 
                                double* K);
 
 hipError_t launch_posterior(hipStream_t stream, const GPArgs& args, int n_obj, int max_R, const double* Xc,
-                            int64_t N, double* mu, double* var);
+                            int64_t N, double* mu, double* var, int mean_kernel = kMeanKernelAfter);
 
 // EHVI-2D and the arg-max in one launch (omb_acquisition.hip): each workgroup's (value, index) pair goes to
 // `partials` (2 doubles per workgroup, ehvi2d_argmax_blocks(N) ≤ kArgmaxMaxBlocks); the last workgroup to finish (an

@@ -23,7 +23,9 @@
 //     accumulators followed by a fixed-order cross-wave LDS reduction (deterministic).
 //   * Objectives whose σ² nothing reads (GPArgs::var_skip, set by the fused chain from its plan) take a mean-only
 //     path in every kernel below: the same K* generation folded into μ in the same order (the same bits), no
-//     V = L⁻¹K*, no store to var_out.
+//     V = L⁻¹K*, no store to var_out.  At n_var ≤ 8 and n > 128 their μ has a launch of its own
+//     (posterior_mean_kernel: a wave per 16 candidates, no ring, no barriers; the same bits) and the ring kernel
+//     covers the other objectives only.
 #include <algorithm>
 #include <type_traits>
 
@@ -623,6 +625,129 @@ __device__ __forceinline__ d2 load_lpair(__amdgpu_buffer_rsrc_t rsrc, int lane, 
   return __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rsrc, 16 * lane, soff, 0));
 }
 
+// Objective of a workgroup: blockIdx.y itself, or — GPArgs::obj_sel non-zero — the blockIdx.y-th set bit of it
+// (a launch over a subset of the objectives; launch_posterior_dp).  Uniform over the workgroup.
+__device__ __forceinline__ int launch_objective(unsigned obj_sel) {
+  if (obj_sel == 0) return (int)blockIdx.y;
+  unsigned m = obj_sel;
+  for (unsigned i = 0; i < blockIdx.y; ++i) m &= m - 1;
+  return __builtin_ctz(m);
+}
+
+// Shape of the K* generation on MFMA.  At n_var ≤ 8 (kAug) posterior_kernel and posterior_mean_kernel instantiate the
+// same code (compute_tile); wider inputs generate inside posterior_kernel, which nothing has to match bit for bit.
+template <int DP, int KIND, int ABL>
+struct GenShape {
+  // d ≤ 8: r² straight from the MFMA (−1% time at config 3).  Wider inputs keep the cross-term form:
+  // the extra k-step bought nothing at d = 30 and its registers make the CT = 4 variants spill.
+  static constexpr bool kAug = DP <= 8 && !(ABL & 4096);   // ABL 4096: cross term only (ablation)
+  static constexpr int KSD = kAug ? (DP + 5) / 4 : (DP + 3) / 4;
+  static constexpr int KSDP = ((DP + 5) / 4 + 1) / 2;                 // = packed_X_pairs(DP)
+  // n_var ≤ 8 (r² on MFMA): the generation's per-lane loads (training fragments, α) as buffer loads with the
+  // wave-uniform part of the address in SGPRs, as load_lpair; rows ≥ n of α read as 0 (α's padding is 0).  Alternated
+  // A/B (profiles/r05_zi_ablate_posterior_bufgen_c{3,5}.txt, r05_zj_…_c4.txt): config 3 9.94-9.98 → 9.87-9.89 ms; at d =
+  // 30 (‖x/ℓ‖² loaded per element as well) it was 1.9% slower (10.01-10.08 → 10.21 ms) and stays off.  ABL 262144
+  // flips the choice (tools/ablate).
+  static constexpr bool kBufGen = kAug != ((ABL & 262144) != 0);
+  // Matern: 256-entry exp table (matern_r2_tab256_x2).  ABL 16384 keeps the 64-entry table of the
+  // RBF path (ablation: 10.21 → 10.12 ms at config 3, max rel. error 3.9e-14 → 1.6e-14), ABL 32768
+  // drops the sqrt correction (a further −1.2%, but 5e-13 max rel. error: not used).
+  static constexpr bool kTab256 = !(ABL & 16384) && KIND == OMB_KERNEL_MATERN52;
+  static constexpr int kTabN = kTab256 ? 256 : 64;
+};
+
+// The buffer resources of the generation's loads: Xf over the objective's own Q chunks, ‖x/ℓ‖² and α over its n rows.
+struct GenRsrc {
+  __amdgpu_buffer_rsrc_t X, xsq, al;
+};
+template <int DP>
+__device__ __forceinline__ GenRsrc gen_rsrc(const GPDev& g, int Q) {
+  constexpr int KSDP = ((DP + 5) / 4 + 1) / 2;
+  GenRsrc r;
+  r.X = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(g.Xf), (short)0, (int)(8ll * 4 * Q * KSDP * 128),
+                                          0x00020000);
+  r.xsq = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(g.xsq), (short)0, 8 * g.n, 0x00020000);
+  r.al = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(g.alpha), (short)0, 8 * g.n, 0x00020000);
+  return r;
+}
+
+// The training rows' A fragments of row tile t of chunk kc (KSD k-steps, two per 16-byte load).
+template <int DP, int KIND, int ABL>
+__device__ __forceinline__ void load_tile_a(const GPDev& g, const GenRsrc& rs, int lane, int kc, int t,
+                                            d2 (&a)[(GenShape<DP, KIND, ABL>::KSD + 1) / 2]) {
+  using GS = GenShape<DP, KIND, ABL>;
+  constexpr int KSD = GS::KSD, KSDP = GS::KSDP;
+  const d2* xa = reinterpret_cast<const d2*>(g.Xf + (int64_t)(4 * kc + t) * (KSDP * 128) + 2 * lane);
+#pragma unroll
+  for (int p = 0; p < (KSD + 1) / 2; ++p) {
+    if constexpr (GS::kBufGen)
+      a[p] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rs.X, 16 * lane,
+                                                                           8 * ((4 * kc + t) * (KSDP * 128) + 128 * p), 0));
+    else
+      a[p] = xa[64 * p];
+  }
+}
+// Entry k = kofs + (lane>>4) of a per-row vector (‖x/ℓ‖² or α), kofs wave-uniform: the buffer form takes kofs in
+// its scalar offset, the pointer form indexes with k
+template <int DP, int KIND, int ABL>
+__device__ __forceinline__ double load_row_val(__amdgpu_buffer_rsrc_t r, const double* __restrict__ v, int lane, int k,
+                                               int kofs) {
+  if constexpr (GenShape<DP, KIND, ABL>::kBufGen)
+    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, 8 * (lane >> 4), 8 * kofs, 0));
+  else
+    return v[k];
+}
+
+// One 16×16 K* tile at n_var ≤ 8 — row tile t of chunk kc (A fragments a) against the wave's 16 candidates
+// (B fragments bfr) — and its share of μ: r² by KSD MFMA k-steps, the transform on the lane's 4 values (e = 0, 2, rows k0 and k1 = k0 + 4
+// each), then mu_part = fma(α_k0, v0, mu_part), fma(α_k1, v1, ·) in that order.  alpha(i, k, kofs) gives α of row
+// k = kofs + (lane>>4) = rowbase + 4i + (lane>>4), i = 0..3, when it is needed (a load there, or a register loaded
+// earlier); sink(e, v0, v1) gets the values (the ring store of posterior_kernel; nothing on the mean-only paths).  The one copy of the
+// generation: every kernel that must agree on μ bit for bit calls it.
+template <int DP, int KIND, int ABL, class Alpha, class Sink>
+__device__ __forceinline__ void compute_tile(const GPDev& g, const ExpCoef& ec, const GenRsrc& rs, int lane, int kc,
+                                             int t, const d2 (&a)[(GenShape<DP, KIND, ABL>::KSD + 1) / 2],
+                                             const double* bfr, const double (&pm)[3], const double* etab,
+                                             double& mu_part, Alpha&& alpha, Sink&& sink) {
+  using GS = GenShape<DP, KIND, ABL>;
+  static_assert(GS::kAug, "r² straight from the MFMA: n_var ≤ 8 (wider inputs: posterior_kernel's own generation)");
+  constexpr bool kTab256 = GS::kTab256;
+  constexpr int KSD = GS::KSD;
+  const int rowbase = kc * kChunkRows + 16 * t;
+  d4 cr = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int s = 0; s < KSD; ++s)
+    cr = __builtin_amdgcn_mfma_f64_16x16x4f64((s & 1) ? a[s >> 1].y : a[s >> 1].x, bfr[s], cr, 0, 0, 0);
+#pragma unroll
+  for (int e = 0; e < 4; e += 2) {
+    const int k0 = rowbase + 4 * e + (lane >> 4), k1 = k0 + 4;
+    double v0, v1;
+    const double sf2 = (ABL & 256) ? 1.0 : g.variance;
+    const double r2a = cr[e], r2b = cr[e + 1];
+    if constexpr (ABL & 8192)   // ablation: the 17-instruction polynomial exp, two sqrt corrections
+      kernel_of_r2_k_x2<KIND>(r2a, r2b, sf2, ec, v0, v1);
+    else if constexpr (kTab256)
+      matern_r2_tab256_x2<(ABL & 32768) != 0, (ABL & 524288) != 0>(r2a, r2b, pm, ec, etab, v0, v1);
+    else
+      kernel_of_r2_tab_x2<KIND>(r2a, r2b, pm, ec, etab, v0, v1);
+    mu_part = fma(alpha(e, k0, rowbase + 4 * e), v0, mu_part);
+    mu_part = fma(alpha(e + 1, k1, rowbase + 4 * e + 4), v1, mu_part);
+    sink(e, v0, v1);
+  }
+}
+
+// compute_tile with every operand loaded where it is used (posterior_kernel: its other waves hide the latency)
+template <int DP, int KIND, int ABL, class Sink>
+__device__ __forceinline__ void generate_tile(const GPDev& g, const ExpCoef& ec, const GenRsrc& rs, int lane, int kc,
+                                              int t, const double* bfr, const double (&pm)[3], const double* etab,
+                                              double& mu_part, Sink&& sink) {
+  d2 a[(GenShape<DP, KIND, ABL>::KSD + 1) / 2];
+  load_tile_a<DP, KIND, ABL>(g, rs, lane, kc, t, a);
+  compute_tile<DP, KIND, ABL>(
+      g, ec, rs, lane, kc, t, a, bfr, pm, etab, mu_part,
+      [&](int, int k, int kofs) { return load_row_val<DP, KIND, ABL>(rs.al, g.alpha, lane, k, kofs); }, sink);
+}
+
 template <int RT, int CT, int DP, int KIND, int NW = 8, int ABL = 0, int WPE = NW / 4>
 __global__ __launch_bounds__(64 * NW, WPE) void posterior_kernel(GPArgs args, const double* __restrict__ Xc,
                                                                      int64_t N, double* __restrict__ mu_out,
@@ -642,15 +767,13 @@ __global__ __launch_bounds__(64 * NW, WPE) void posterior_kernel(GPArgs args, co
   // as [j][c] (lanes read consecutive doubles) so the 256-VGPR budget stays with the MFMA tiles.
   constexpr bool kCandLds = DP > 8 || RT >= 8;
   constexpr int kCtrDoubles = kCounters ? kMaxChunks : 0;
-  // Matern: 256-entry exp table (matern_r2_tab256_x2).  ABL 16384 keeps the 64-entry table of the
-  // RBF path (ablation: 10.21 → 10.12 ms at config 3, max rel. error 3.9e-14 → 1.6e-14), ABL 32768
-  // drops the sqrt correction (a further −1.2%, but 5e-13 max rel. error: not used).
-  constexpr bool kTab256 = !(ABL & 16384) && KIND == OMB_KERNEL_MATERN52;
-  constexpr int kTabN = kTab256 ? 256 : 64;
+  using GS = GenShape<DP, KIND, ABL>;
+  constexpr bool kTab256 = GS::kTab256;   // the exp table of the transform (GenShape)
+  constexpr int kTabN = GS::kTabN;
   __shared__ double kbuf[NBUF * CHUNK + kCtrDoubles + (kCandLds ? DP * BN : 0) + kTabN];
 
   OMB_POST_TRACE(0);
-  const int obj = blockIdx.y;
+  const int obj = DP <= 8 ? launch_objective(args.obj_sel) : (int)blockIdx.y;   // a subset only at n_var ≤ 8
   const GPDev g = args.gp[obj];
   const int d = args.d;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -690,11 +813,8 @@ __global__ __launch_bounds__(64 * NW, WPE) void posterior_kernel(GPArgs args, co
   // each lane applies the Matern transform to its 4 values and stores them to the ring as they are.
   // Rows past n need no guard: α and the L⁻¹ columns there are zero, and r² stays finite.
   constexpr bool kMfmaGen = !(ABL & 2048);   // ABL 2048: VALU dot products (ablation)
-  // d ≤ 8: r² straight from the MFMA (−1% time at config 3).  Wider inputs keep the cross-term form:
-  // the extra k-step bought nothing at d = 30 and its registers make the CT = 4 variants spill.
-  constexpr bool kAug = DP <= 8 && !(ABL & 4096);   // ABL 4096: cross term only (ablation)
-  constexpr int KSD = kAug ? (DP + 5) / 4 : (DP + 3) / 4;
-  constexpr int KSDP = ((DP + 5) / 4 + 1) / 2;                 // = packed_X_pairs(DP)
+  constexpr bool kAug = GS::kAug;                              // r² straight from the MFMA (GenShape)
+  constexpr int KSD = GS::KSD;
   constexpr int TPC = 4 * CT;                                  // K* tiles per chunk
   constexpr int TPW = TPC >= NW ? TPC / NW : 1;                 // tiles per generating wave
   static_assert(!kMfmaGen || (NW % CT == 0 && (TPC % NW == 0 || NW % TPC == 0)), "tile deal");
@@ -782,11 +902,10 @@ __global__ __launch_bounds__(64 * NW, WPE) void posterior_kernel(GPArgs args, co
   constexpr bool kPairs = !kCandLds && !(ABL & (1 | 16 | 512));
   const double pm_s = (ABL & 256) ? 1.0 : g.variance;
   const double pm[3] = {pm_s, kSqrt5 * pm_s, kFiveThirds * pm_s};
-  // n_var ≤ 8 (r² on MFMA): the generation's per-lane loads (training fragments, α) as buffer loads with the
-  // wave-uniform part of the address in SGPRs, as load_lpair; rows ≥ n of α read as 0 (α's padding is 0).  Alternated
-  // A/B (profiles/r05_zi_ablate_posterior_bufgen_c{3,5}.txt, r05_zj_…_c4.txt): config 3 9.94-9.98 → 9.87-9.89 ms; at d =
-  // 30 (‖x/ℓ‖² loaded per element as well) it was 1.9% slower (10.01-10.08 → 10.21 ms) and stays off.  ABL 262144
-  // flips the choice (tools/ablate).
+  // n_var ≤ 8: the generation's buffer loads (GenShape::kBufGen) and the tile itself (generate_tile) are shared
+  // with posterior_mean_kernel
+  const GenRsrc rs = gen_rsrc<DP>(g, Q);
+  constexpr int KSDP = GS::KSDP;
   constexpr bool kBufGen = kAug != ((ABL & 262144) != 0);
   const __amdgpu_buffer_rsrc_t rsrc_X = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<double*>(g.Xf), (short)0, (int)(8ll * 4 * Q * KSDP * 128), 0x00020000);
@@ -803,6 +922,17 @@ __global__ __launch_bounds__(64 * NW, WPE) void posterior_kernel(GPArgs args, co
       for (int i = 0; i < TPW; ++i) {
         const int u = (NW > TPC) ? wave % TPC : wave + NW * i;
         const int t = u / CT;                                    // row tile of the chunk (0..3)
+        if constexpr (kAug) {
+          generate_tile<DP, KIND, ABL>(g, args.ec, rs, lane, kc, t, bfr, pm, etab, mu_part,
+                                       [&](int e, double v0, double v1) {
+                                         if constexpr (decltype(keep)::value) {
+                                           buf[((4 * t + e) * CT + mg_ct) * 64 + lane] = v0;
+                                           buf[((4 * t + e + 1) * CT + mg_ct) * 64 + lane] = v1;
+                                         }
+                                       });
+          continue;
+        }
+        // n_var > 8 (and the cross-term ablation): r² = ‖x/ℓ‖² + ‖x*/ℓ‖² − 2·cross term, rows past n guarded
         const int rowbase = kc * kChunkRows + 16 * t;
         const d2* xa = reinterpret_cast<const d2*>(g.Xf + (int64_t)(4 * kc + t) * (KSDP * 128) + 2 * lane);
         d2 a[(KSD + 1) / 2];
@@ -1086,6 +1216,118 @@ __global__ __launch_bounds__(64 * NW, WPE) void posterior_kernel(GPArgs args, co
     }
   }
   OMB_POST_TRACE(4);
+}
+
+// ----------------------------------------------------------------------------- posterior mean alone
+// μ of the objectives whose σ² nothing reads (GPArgs::var_skip), n_var ≤ 8, in a launch of its own
+// (launch_posterior_dp): Σ_k α_k k(x*, x_k) over a column of 16 candidates needs no LDS ring, no counters and no
+// cooperation between waves, so each wave owns a column and walks the ⌈N/16⌉ columns in a grid-stride loop; the grid
+// fills the device once.  The exp table is staged once per workgroup; there is no barrier after it.  A column's raw
+// coordinates are loaded (one clamped load per B-fragment slot, all in flight together) while the column before
+// it generates, and a tile's training fragments and α while the tile before it does: loaded where they are used,
+// as in posterior_kernel, every tile waited for five L2 round trips one after the other (0.63 ms at config 3
+// against 0.59 with the loads a tile ahead).
+// μ keeps the bits of posterior_kernel<·, 2, DP, KIND, 8>: there wave w generates row tile t = w/2 of every chunk
+// for column w mod 2 and sums mu_part over the chunks in ascending order; the epilogue adds the four waves' sums
+// of a column as m = 0, m += s_0 … m += s_3.  Here the wave keeps one accumulator per t, each fed by the same
+// generate_tile in the same chunk order, reduces each by the same two shuffles and adds them in that order.
+// The B fragments are the same numbers: the quotient x*_j/ℓ_j of slot (s, lane>>4) is computed once in its own lane,
+// and ‖x*/ℓ‖² = fma(c_j, c_j, ·) over j ascending reads the c_j from the lanes that hold them.
+// Four waves per workgroup (one per SIMD).  The register budget is that of 4 waves per SIMD — with the next tile's
+// operands in flight that is enough to keep the FP64 pipe fed — and of 3 at n_var 7, 8, whose three k-steps
+// of fragments, held twice, spilled at 128 VGPRs.
+constexpr int kMeanWaves = 4;
+template <int DP, int KIND>
+__global__ __launch_bounds__(64 * kMeanWaves, DP == 8 ? 3 : 4) void posterior_mean_kernel(
+    GPArgs args, const double* __restrict__ Xc, int64_t N, double* __restrict__ mu_out) {
+  static_assert(DP <= 8, "the candidates' B fragments live in registers");
+  using GS = GenShape<DP, KIND, 0>;
+  constexpr int KSD = GS::KSD;
+  __shared__ double etab[GS::kTabN];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  for (int i = tid; i < GS::kTabN; i += 64 * kMeanWaves) etab[i] = GS::kTab256 ? kExp2Tab256[i] : kExp2Tab64[i];
+  __syncthreads();
+
+  const int obj = launch_objective(args.obj_sel);
+  const GPDev g = args.gp[obj];
+  const int d = args.d;
+  const int Q = (g.R + 3) >> 2;   // this objective's own chunks of 64 rows
+  const GenRsrc rs = gen_rsrc<DP>(g, Q);
+  const double pm[3] = {g.variance, kSqrt5 * g.variance, kFiveThirds * g.variance};
+  const int64_t ncols = (N + 15) >> 4;
+  const int64_t stride = (int64_t)gridDim.x * kMeanWaves;
+  int64_t col = (int64_t)blockIdx.x * kMeanWaves + wave;
+
+  // slot s of the B fragment holds dimension 4s + (lane>>4) of candidate lane&15: the index is clamped for the load
+  // (columns past N to N − 1, dimensions past d to d − 1) and the value selected afterwards
+  int jl[KSD];
+  double lsl[KSD];
+#pragma unroll
+  for (int s = 0; s < KSD; ++s) {
+    jl[s] = min(4 * s + (lane >> 4), d - 1);
+    lsl[s] = g.ls[jl[s]];
+  }
+  auto load_raw = [&](int64_t c, double (&x)[KSD]) {
+    const int64_t ci = min(16 * c + (lane & 15), N - 1);
+#pragma unroll
+    for (int s = 0; s < KSD; ++s) x[s] = Xc[ci * d + jl[s]];
+  };
+  // a tile's operands: the A fragments and α of its 16 rows
+  d2 ta[2][(KSD + 1) / 2];
+  double tal[2][4];
+  auto load_tile = [&](int kc, int t, d2 (&a)[(KSD + 1) / 2], double (&al)[4]) {
+    load_tile_a<DP, KIND, 0>(g, rs, lane, kc, t, a);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int kofs = kc * kChunkRows + 16 * t + 4 * i;
+      al[i] = load_row_val<DP, KIND, 0>(rs.al, g.alpha, lane, kofs + (lane >> 4), kofs);
+    }
+  };
+  double xraw[KSD];
+  if (col < ncols) load_raw(col, xraw);
+  for (; col < ncols; col += stride) {
+    load_tile(0, 0, ta[0], tal[0]);
+    double q[KSD];
+#pragma unroll
+    for (int s = 0; s < KSD; ++s) q[s] = (4 * s + (lane >> 4) < d) ? xraw[s] / lsl[s] : 0.0;
+    if (col + stride < ncols) load_raw(col + stride, xraw);   // in flight during this column's generation
+    double csq = 0.0;
+#pragma unroll
+    for (int j = 0; j < DP; ++j) {
+      const double c = __shfl(q[j >> 2], 16 * (j & 3) + (lane & 15));
+      csq = fma(c, c, csq);
+    }
+    double bfr[KSD];
+#pragma unroll
+    for (int s = 0; s < KSD; ++s) {
+      const int j = 4 * s + (lane >> 4);
+      bfr[s] = (j < d) ? -2.0 * q[s] : (j == d ? 1.0 : (j == d + 1 ? csq : 0.0));
+    }
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int kc = 0; kc < Q; ++kc) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        // the next tile's operands are in flight while this one computes (past the last tile the buffer loads
+        // are out of range and return 0)
+        const int cur = t & 1, nxt = cur ^ 1;
+        load_tile(kc + (t + 1) / 4, (t + 1) & 3, ta[nxt], tal[nxt]);
+        compute_tile<DP, KIND, 0>(
+            g, args.ec, rs, lane, kc, t, ta[cur], bfr, pm, etab, acc[t], [&](int i, int, int) { return tal[cur][i]; },
+            [](int, double, double) {});
+      }
+    }
+    double m = 0.0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      double s = acc[t];
+      s += __shfl_xor(s, 16);
+      s += __shfl_xor(s, 32);
+      m += s;
+    }
+    const int64_t c = 16 * col + lane;
+    if (lane < 16 && c < N) mu_out[(int64_t)obj * N + c] = m;
+  }
 }
 
 // ----------------------------------------------------------------------------- posterior, n ≤ 256
@@ -1590,12 +1832,57 @@ static dim3 reg_grid(int64_t N, int n_obj, int NW = 8, int per_cu = 2) {
 }
 
 // ----------------------------------------------------------------------------- dispatch
+// posterior_mean_kernel over the objectives in `masked`: a resident grid (the occupancy the compiler's register and
+// LDS use allows, times the CUs, shared between the masked objectives), never more workgroups than columns.
 template <int DP, int KIND>
-static hipError_t launch_posterior_dp(hipStream_t stream, const GPArgs& args, int n_obj, int max_R,
-                                      const double* Xc, int64_t N, double* mu, double* var) {
+static hipError_t launch_posterior_mean(hipStream_t stream, const GPArgs& args_in, unsigned masked, const double* Xc,
+                                        int64_t N, double* mu) {
+  static int per_cu = 0;   // the same for every device of one architecture
+  if (per_cu == 0) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, posterior_mean_kernel<DP, KIND>, 64 * kMeanWaves, 0) !=
+            hipSuccess || nb <= 0)
+      nb = 4;
+    per_cu = nb;
+  }
+  GPArgs args = args_in;
+  args.obj_sel = masked;
+  const int n_masked = __builtin_popcount(masked);
+  const int64_t wgs = ((N + 15) / 16 + kMeanWaves - 1) / kMeanWaves;
+  const int64_t resident = std::max<int64_t>(1, ((int64_t)per_cu * device_cu_count()) / n_masked);
+  const dim3 grid((unsigned)std::max<int64_t>(1, std::min(wgs, resident)), (unsigned)n_masked);
+  hipLaunchKernelGGL((posterior_mean_kernel<DP, KIND>), grid, dim3(64 * kMeanWaves), 0, stream, args, Xc, N, mu);
+  return hipGetLastError();
+}
+
+template <int DP, int KIND>
+static hipError_t launch_posterior_dp(hipStream_t stream, const GPArgs& args_in, int n_obj, int max_R,
+                                      const double* Xc, int64_t N, double* mu, double* var, int mean_kernel) {
   const int Q = (max_R + 3) / 4;
   const int RTneed = (Q + 1) / 2;
-  if (RTneed <= 1 && DP <= 8) {
+  // n_var ≤ 8 on the ring kernels (n > 128) with masked objectives: their μ by posterior_mean_kernel, and the ring
+  // kernel — still the instantiation max_R over all objectives picks, so σ² keeps its bits — over the others only
+  // (GPArgs::obj_sel; no launch if there are none).  The mean-only workgroups of the ring kernel keep its 51 KiB
+  // of LDS, its 32-candidate blocks and its per-workgroup prologue, barrier and reduction for 11 µs of work.
+  // kMeanKernelOff, the other kernels and n_var > 8 keep the in-kernel mean-only path.
+  const unsigned all = n_obj >= 32 ? ~0u : (1u << n_obj) - 1u;
+  const unsigned masked = args_in.var_skip & all;
+  GPArgs args = args_in;
+  bool split = false;
+  if constexpr (DP <= 8) split = mean_kernel != kMeanKernelOff && masked != 0 && RTneed > 1 && RTneed <= 8;
+  if (split) {
+    args.obj_sel = all & ~masked;
+    n_obj = __builtin_popcount(args.obj_sel);
+  }
+  if constexpr (DP <= 8) {
+    if (split && mean_kernel == kMeanKernelBefore) {
+      hipError_t e = launch_posterior_mean<DP, KIND>(stream, args_in, masked, Xc, N, mu);
+      if (e != hipSuccess) return e;
+    }
+  }
+  if (n_obj == 0) {
+    // every objective masked: the mean launch is the whole posterior
+  } else if (RTneed <= 1 && DP <= 8) {
     // n ≤ 128, n_var ≤ 8: persistent, L⁻¹ in LDS, K* in registers (posterior_reg_kernel)
     if constexpr (DP <= 8) {
       // 16 waves, one workgroup per CU, training rows staged in LDS: 0.062 ms at config 2 against
@@ -1651,30 +1938,36 @@ static hipError_t launch_posterior_dp(hipStream_t stream, const GPArgs& args, in
   } else {
     return hipErrorInvalidValue;
   }
-  return hipGetLastError();
+  hipError_t e = hipGetLastError();
+  if constexpr (DP <= 8) {
+    if (e == hipSuccess && split && mean_kernel == kMeanKernelAfter)
+      e = launch_posterior_mean<DP, KIND>(stream, args_in, masked, Xc, N, mu);
+  }
+  return e;
 }
 
 template <int KIND>
 static hipError_t launch_posterior_kind(hipStream_t stream, const GPArgs& args, int n_obj, int max_R,
-                                        const double* Xc, int64_t N, double* mu, double* var) {
+                                        const double* Xc, int64_t N, double* mu, double* var, int mean_kernel) {
   switch (args.DP) {
-    case 2: return launch_posterior_dp<2, KIND>(stream, args, n_obj, max_R, Xc, N, mu, var);
-    case 4: return launch_posterior_dp<4, KIND>(stream, args, n_obj, max_R, Xc, N, mu, var);
-    case 6: return launch_posterior_dp<6, KIND>(stream, args, n_obj, max_R, Xc, N, mu, var);
-    case 8: return launch_posterior_dp<8, KIND>(stream, args, n_obj, max_R, Xc, N, mu, var);
-    case 16: return launch_posterior_dp<16, KIND>(stream, args, n_obj, max_R, Xc, N, mu, var);
-    case 32: return launch_posterior_dp<32, KIND>(stream, args, n_obj, max_R, Xc, N, mu, var);
-    case 64: return launch_posterior_dp<64, KIND>(stream, args, n_obj, max_R, Xc, N, mu, var);
+    case 2: return launch_posterior_dp<2, KIND>(stream, args, n_obj, max_R, Xc, N, mu, var, mean_kernel);
+    case 4: return launch_posterior_dp<4, KIND>(stream, args, n_obj, max_R, Xc, N, mu, var, mean_kernel);
+    case 6: return launch_posterior_dp<6, KIND>(stream, args, n_obj, max_R, Xc, N, mu, var, mean_kernel);
+    case 8: return launch_posterior_dp<8, KIND>(stream, args, n_obj, max_R, Xc, N, mu, var, mean_kernel);
+    case 16: return launch_posterior_dp<16, KIND>(stream, args, n_obj, max_R, Xc, N, mu, var, mean_kernel);
+    case 32: return launch_posterior_dp<32, KIND>(stream, args, n_obj, max_R, Xc, N, mu, var, mean_kernel);
+    case 64: return launch_posterior_dp<64, KIND>(stream, args, n_obj, max_R, Xc, N, mu, var, mean_kernel);
     default: return hipErrorInvalidValue;
   }
 }
 
 hipError_t launch_posterior(hipStream_t stream, const GPArgs& args_in, int n_obj, int max_R, const double* Xc,
-                            int64_t N, double* mu, double* var) {
+                            int64_t N, double* mu, double* var, int mean_kernel) {
   GPArgs args = args_in;
   args.ec = exp_coef();
-  if (args.gp[0].kind == OMB_KERNEL_RBF) return launch_posterior_kind<OMB_KERNEL_RBF>(stream, args, n_obj, max_R, Xc, N, mu, var);
-  return launch_posterior_kind<OMB_KERNEL_MATERN52>(stream, args, n_obj, max_R, Xc, N, mu, var);
+  if (args.gp[0].kind == OMB_KERNEL_RBF)
+    return launch_posterior_kind<OMB_KERNEL_RBF>(stream, args, n_obj, max_R, Xc, N, mu, var, mean_kernel);
+  return launch_posterior_kind<OMB_KERNEL_MATERN52>(stream, args, n_obj, max_R, Xc, N, mu, var, mean_kernel);
 }
 
 template <int KIND>

@@ -79,13 +79,16 @@ class AcqContext:
         Thompson selection's parallel rounds (default) / its sequential walk for B <= 64; ("boxes_kd", 0/1) runs
         omb_ehvi_boxes_k candidate-blocked (default) / one wavefront per candidate where its tables fit;
         ("posterior_all_var", 0/1) lets the fused chain skip the posterior variance of objectives the planned
-        acquisition never reads (default) / compute every objective's (bit-identical values)."""
+        acquisition never reads (default) / compute every objective's (bit-identical values);
+        ("posterior_mean_kernel", 0/1/2) computes those objectives' mean inside the posterior launch / in a kernel
+        of its own after it (default) / in that kernel before it (bit-identical values)."""
         code = {"spin_limit": _lib.DEBUG_SPIN_LIMIT, "cov_table": _lib.DEBUG_COV_TABLE,
                 "fused_chain": _lib.DEBUG_FUSED_CHAIN, "argmax_passes": _lib.DEBUG_ARGMAX_PASSES,
                 "chol_mode": _lib.DEBUG_CHOL_MODE, "timing_stride": _lib.DEBUG_TIMING_STRIDE,
                 "cov_fused": _lib.DEBUG_COV_FUSED,
                 "select_seq": _lib.DEBUG_SELECT_SEQ, "syrk_glds": _lib.DEBUG_SYRK_GLDS,
-                "boxes_kd": _lib.DEBUG_BOXES_KD, "posterior_all_var": _lib.DEBUG_POSTERIOR_ALL_VAR}[what]
+                "boxes_kd": _lib.DEBUG_BOXES_KD, "posterior_all_var": _lib.DEBUG_POSTERIOR_ALL_VAR,
+                "posterior_mean_kernel": _lib.DEBUG_POSTERIOR_MEAN_KERNEL}[what]
         self._check(self.lib.omb_debug_set(self._h, code, int(value)), "omb_debug_set")
 
     # ------------------------------------------------------------------ GP state
