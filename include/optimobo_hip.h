@@ -245,6 +245,16 @@ int omb_ei(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_t N,
 int omb_ei_ext(omb_ctx* ctx, int kind, int k, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
                double best, double var_eps, double pof_eps, double* out_dev);
 
+/* Probability of feasibility over c rows of constraint-model moments (row j at mu_dev + j·ld; feasible is g ≤ 0):
+ *   z_j = (0 − μ_j) / sqrt(σ²_j + pof_eps),   F = (((1·Φ(z_0))·Φ(z_1))…·Φ(z_{c−1})),   out = acq · F
+ * (acq_dev NULL: out = F; out_dev may be acq_dev).  z and the multiplication order are OMB_EI_CONSTRAINED's, so
+ * omb_ei weighted here has that kind's bits.  A NaN acquisition value stays NaN; σ²_j + pof_eps < 0 gives NaN, as in
+ * OMB_EI_CONSTRAINED (σ² is not clamped).  1 ≤ c ≤ OMB_MAX_OBJ; OMB_EINVAL for c outside it, a null pointer with
+ * N > 0, ld < N with c > 1, or pof_eps negative or not finite (nothing is written); N = 0 is OMB_OK and touches
+ * nothing.  Asynchronous. */
+int omb_feasibility(omb_ctx* ctx, int c, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
+                    double pof_eps, const double* acq_dev /* may be NULL */, double* out_dev);
+
 /* Arg-max over vals_dev (N): lowest index among maxima, NaN and -inf never win
  * (replaces scipy differential_evolution(lambda x: -acq(x)), optimisers.py:87,118).
  * result_dev (2 doubles, device): {best value, best index + offset (as double)};
@@ -286,6 +296,19 @@ int omb_plan_expdec(omb_ctx* ctx, int k, const double* cache_host, int M, int sc
 int omb_plan_ei(omb_ctx* ctx, double best, double var_eps);
 /* EI family over objectives 0..k-1: as omb_ei_ext. */
 int omb_plan_ei_ext(omb_ctx* ctx, int kind, int k, double best, double var_eps, double pof_eps);
+
+/* Inequality constraints on the plan that is set (g ≤ 0 feasible).  From here on omb_eval, omb_eval_argmax,
+ * omb_eval_argmax_sobol and omb_eval_grad also compute the posterior (μ and σ²) of context slots k..k+n_con−1 — the
+ * constraint models, set like objectives with omb_set_gp / omb_gp_fit_state — and multiply the acquisition by their
+ * probability of feasibility (omb_feasibility's F at pof_eps) before the arg-max.  The objectives' σ² stay as the
+ * plan needs them.  Every omb_plan_* call starts a new plan and so clears the constraints: set them after the plan.
+ * n_con = 0 clears them.  OMB_ESTATE with no plan; OMB_EINVAL for n_con < 0 or pof_eps negative or not finite;
+ * OMB_EUNSUP for k + n_con > OMB_MAX_OBJ; a failed call leaves the plan and its constraints as they were.  A
+ * constraint slot with no GP is OMB_ESTATE from the eval calls, as for an objective.  With OMB_DEBUG_FUSED_CHAIN 1
+ * or 2 a constrained EHVI-2D plan takes the plain chain (the same pair).  omb_eval_grad keeps the gradient of
+ * every plan that has one (the product rule over a·F; finite where F underflows to 0) and its NaN-row rule.
+ * σ²_j + pof_eps < 0 gives NaN there as well. */
+int omb_plan_constraints(omb_ctx* ctx, int n_con, double pof_eps);
 
 /* Scrambled Sobol' candidates generated on the device (replaces the host-side sampling that
  * feeds the maximiser; same sequence as scipy.stats.qmc.Sobol, which the reference uses for

@@ -62,6 +62,7 @@ SIGNATURES = {
     "omb_expdec": (_i, [_p, _i, _p, _p, _i64, _i64, _p, _i, _i, _dp, _dp, _dp, _dp, _d, _p]),
     "omb_ei": (_i, [_p, _p, _p, _i64, _d, _d, _p]),
     "omb_ei_ext": (_i, [_p, _i, _i, _p, _p, _i64, _i64, _d, _d, _d, _p]),
+    "omb_feasibility": (_i, [_p, _i, _p, _p, _i64, _i64, _d, _p, _p]),
     "omb_argmax_dev": (_i, [_p, _p, _i64, _i64, _p]),
     "omb_argmax": (_i, [_p, _p, _i64, _i64, _dp, ctypes.POINTER(_i64)]),
     # fused chain (host pointers for plan geometry)
@@ -74,6 +75,7 @@ SIGNATURES = {
     "omb_plan_expdec": (_i, [_p, _i, _p, _i, _i, _dp, _dp, _dp, _dp, _d]),
     "omb_plan_ei": (_i, [_p, _d, _d]),
     "omb_plan_ei_ext": (_i, [_p, _i, _i, _d, _d, _d]),
+    "omb_plan_constraints": (_i, [_p, _i, _d]),
     "omb_set_sobol": (_i, [_p, _i, _i, _p, _p, _dp, _dp]),
     "omb_sobol": (_i, [_p, _i64, _i64, _p]),
     "omb_eval": (_i, [_p, _p, _i64, _p]),

@@ -53,7 +53,9 @@ class AcquisitionEngine:
     def condition(self, Xnew, Y=None):
         """Condition every loaded objective on the rows of Xnew (q, d) in place, without a refit
         (AcqContext.gp_append): ``Y`` (q, n_obj) are their values, None the Kriging believer (each point takes
-        its posterior mean, so only σ² shrinks).  Returns the (q, n_obj) predictive means.
+        its posterior mean, so only σ² shrinks).  Returns the (q, n_obj) predictive means.  "Every loaded objective"
+        includes constraint models loaded behind the objectives (``plan_constraints``): the believer conditions them
+        too.
 
         The noise of the bordered update is the resident state's ``noise``, plus ``DeviceGPState.jitter`` when
         the device fit had to add one.  A host ``GPState`` does not record the jitter its jitchol escalated to;
@@ -152,6 +154,15 @@ class AcquisitionEngine:
         mu, var = self.posterior(Xc)
         return self.ctx.ei_ext("constrained", mu, var, float(best), float(var_eps), float(pof_eps))
 
+    def feasibility(self, Xc, n_con, pof_eps=1e-5):
+        """Probability of feasibility Π_j Φ(−μ_j / sqrt(σ²_j + pof_eps)) on every row of Xc under the last ``n_con``
+        loaded models (rows n_obj − n_con .. of the posterior), each a GP of a constraint g_j with g_j ≤ 0 feasible."""
+        n_con = int(n_con)
+        if not 1 <= n_con <= self.n_obj:
+            raise ValueError(f"feasibility: n_con={n_con} outside [1, {self.n_obj}] loaded models")
+        mu, var = self.posterior(Xc)
+        return self.ctx.feasibility(mu[self.n_obj - n_con:], var[self.n_obj - n_con:], float(pof_eps))
+
     # ------------------------------------------------------------------ plans (fused chain)
     # One plan per BO iteration; each candidate batch is then a single omb_eval_argmax_sobol
     # (Sobol generation → posterior → acquisition → arg-max on the device).
@@ -184,6 +195,13 @@ class AcquisitionEngine:
 
     def plan_constrained_ei(self, best, var_eps=0.0, pof_eps=1e-5):
         self.ctx.plan_ei_ext("constrained", self.n_obj, float(best), float(var_eps), float(pof_eps))
+
+    def plan_constraints(self, n_con, pof_eps=1e-5):
+        """Weight the plan just set by the probability of feasibility of the ``n_con`` models loaded after its
+        objectives (slots k .. k + n_con − 1; g ≤ 0 feasible).  Call it after the plan_* method: every plan starts
+        without constraints.  ``condition`` appends to every loaded model, so a believer batch conditions the
+        constraint GPs on the fantasy points as well (their σ² shrinks there, their μ stays)."""
+        self.ctx.plan_constraints(int(n_con), float(pof_eps))
 
     # ------------------------------------------------------------------ maximiser
     def score(self, acq_fn, X):

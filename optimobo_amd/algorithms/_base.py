@@ -13,12 +13,18 @@ from .. import util_functions
 from ..acquisition import engine_for
 from ..gp import GPRegression, Matern52, apply_noise_option, check_noise_option, fit_concurrently
 from ..parallel import agree_host_rng
-from ..result import Res
+from ..result import Constrained_Res, Res
 
 
 class BODriver:
+    # constraints="pof": surrogates in front of the constraint models (n_obj for MultiSurrogateOptimiser, 1 for
+    # MonoSurrogateOptimiser); None: the driver does not take the keyword's "pof"
+    _pof_objective_models = None
+    pof_eps = 1e-5      # added to the constraint models' σ² inside the probability of feasibility (cParEGO's value)
+
     def __init__(self, test_problem, ideal_point=None, max_point=None, mode="reference", n_candidates=1 << 14,
-                 refine_rounds=2, seed=None, device=None, polish=True, starts=None, noise=0.0, batch_size=1):
+                 refine_rounds=2, seed=None, device=None, polish=True, starts=None, noise=0.0, batch_size=1,
+                 constraints=None):
         self.test_problem = test_problem
         self.max_point = max_point
         self.ideal_point = ideal_point
@@ -50,7 +56,51 @@ class BODriver:
         if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
             raise ValueError(f"batch_size must be an integer >= 1, not {batch_size!r}")
         self.batch_size = int(batch_size)
+        # inequality constraints of the problem (not in the reference, whose optimisers.py:22 says "Constraints not
+        # supported"): None ignores them, as the reference does; "pof" fits one GP per constraint and weights the
+        # acquisition by the probability of feasibility (g <= 0 feasible)
+        self.constraints = self._check_constraints_option(constraints)
         self._iteration = 0
+
+    def _check_constraints_option(self, constraints):
+        if constraints is None:
+            return None
+        if constraints != "pof":
+            raise ValueError(f"constraints must be None or 'pof', not {constraints!r}")
+        k = self._pof_objective_models
+        if k is None:
+            raise ValueError(f"{type(self).__name__} does not support constraints='pof' (MultiSurrogateOptimiser and "
+                             "MonoSurrogateOptimiser do)")
+        k = self.n_obj if k == "n_obj" else int(k)
+        n_ieq = int(getattr(self.test_problem, "n_ieq_constr", 0) or 0)
+        if n_ieq == 0:
+            raise ValueError("constraints='pof' needs a problem with n_ieq_constr > 0")
+        if int(getattr(self.test_problem, "n_eq_constr", 0) or 0) > 0:
+            raise ValueError("constraints='pof' does not handle equality constraints (n_eq_constr > 0)")
+        if k + n_ieq > 8:
+            raise ValueError(f"constraints='pof': {k} objective model(s) + {n_ieq} constraints exceed the device "
+                             "context's 8 models")
+        self.n_con = n_ieq
+        return "pof"
+
+    # -- constraints="pof"
+    def _constraint_values(self, X):
+        """G (len(X), n_ieq_constr) of the rows of X through ``problem.evaluate_constraints``."""
+        return np.asarray([np.atleast_1d(self.test_problem.evaluate_constraints(x, return_values_of=["G"])) for x in np.atleast_2d(X)],
+                          dtype=np.float64).reshape(len(np.atleast_2d(X)), -1)
+
+    @staticmethod
+    def _feasible(G):
+        """cParEGO's rule: a row is feasible when every g <= 0."""
+        return np.all(np.atleast_2d(G) <= 0, axis=1)
+
+    def _constrained_result(self, ysample, Xsample, gsample, hypervolume_convergence, n_init_samples):
+        feas = self._feasible(gsample)
+        y_feasible, X_feasible = ysample[feas], Xsample[feas]
+        pf_approx = util_functions.calc_pf(y_feasible)
+        idx = [i for i, y in enumerate(y_feasible) if any(np.array_equal(y, p) for p in np.atleast_2d(pf_approx))]
+        return Constrained_Res(ysample[~feas], y_feasible, Xsample[~feas], X_feasible, pf_approx, X_feasible[idx],
+                               ysample, Xsample, hypervolume_convergence, self.n_obj, n_init_samples)
 
     def _objective_function(self, problem, x):
         return problem.evaluate(x)

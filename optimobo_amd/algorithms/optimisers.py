@@ -30,6 +30,7 @@ class MultiSurrogateOptimiser(BODriver):
     """
 
     exact_max_boxes = 1 << 17       # boxes of one iteration's exact EHVI at n_obj ≥ 4
+    _pof_objective_models = "n_obj"
 
     def _get_cached_samples(self, dimensions, sample_exponent):
         """optimisers.py:121-141 — scrambled Sobol mapped through the normal ppf."""
@@ -83,7 +84,10 @@ class MultiSurrogateOptimiser(BODriver):
 
     def solve(self, budget=100, n_init_samples=5, sample_exponent=5, acquisition_func=None):
         """``budget`` true evaluations.  With ``batch_size`` q > 1 they come in ⌈budget/q⌉ iterations of q proposals
-        (the last one truncated), one ``hypervolume_convergence`` entry per iteration: see ``_solve_batched``."""
+        (the last one truncated), one ``hypervolume_convergence`` entry per iteration: see ``_solve_batched``.
+        With ``constraints="pof"``: ``_solve_pof``, which returns a ``Constrained_Res``."""
+        if self.constraints == "pof":
+            return self._solve_pof(budget, n_init_samples, sample_exponent, acquisition_func)
         if self.batch_size > 1:
             return self._solve_batched(budget, n_init_samples, sample_exponent, acquisition_func)
         problem = self.test_problem
@@ -150,8 +154,66 @@ class MultiSurrogateOptimiser(BODriver):
         return self._result(ysample, Xsample, hypervolume_convergence, n_init_samples)
 
 
+    def _solve_pof(self, budget, n_init_samples, sample_exponent, acquisition_func):
+        """``constraints="pof"``: the loop of ``_solve_batched`` (``batch_size`` 1 is a batch of one) with one GP per
+        objective and per inequality constraint on the same inputs, and the acquisition of every pick weighted by
+        the constraint models' probability of feasibility (AcquisitionEngine.plan_constraints).  A row is feasible
+        when every g ≤ 0; the front the acquisition is planned from, the scalarisation's minimum and the
+        hypervolume trace (0.0 while nothing is feasible) use feasible rows only — inside a batch, fantasies count
+        as feasible by the constraint models' means.  While no row is feasible the pick maximises the probability of
+        feasibility alone.  The believer conditions the constraint models as well."""
+        from ..acquisition import engine_for
+        problem = self.test_problem
+        q, k, c = self.batch_size, problem.n_obj, self.n_con
+        cached_samples = self._get_cached_samples(self.n_obj, sample_exponent)
+        if acquisition_func is None and k == 2 and self.mode == "reference" and \
+                pareto.cache_stats(np.asarray(cached_samples, np.float64))[1] <= 0:
+            # DESIGN §2 item 2: with s01 <= 0 the reference-mode acquisition is <= 0 everywhere, and a weight in
+            # [0, 1] on a non-positive value favours the infeasible points
+            raise ValueError("constraints='pof' with reference-mode 2-D EHVI needs a sample cache whose s01 > 0 "
+                             "(this seed / sample_exponent gives s01 <= 0); use mode='textbook'")
+        Xsample, ysample = self._initial_samples(n_init_samples)
+        gsample = self._constraint_values(Xsample)
+        ref_dirs = get_reference_directions("das-dennis", self.n_obj, n_partitions=100)
+        hypervolume_convergence = []
+        done = 0
+        while done < budget:
+            b = min(q, budget - done)
+            self._update_bounds(ysample, acquisition_func)
+            hypervolume_convergence.append(self._hypervolume(ysample[self._feasible(gsample)]))
+            models = self._fit_many(Xsample, np.hstack((ysample[:, :k], gsample)))
+            eng = engine_for(models, self.device)
+            yfant, gfant, picks = ysample[:, :k], gsample, []
+            for p in range(b):
+                ref_dir = np.asarray(ref_dirs[np.random.randint(0, len(ref_dirs))])
+                yfeas = yfant[self._feasible(gfant)]
+                if len(yfeas) == 0:
+                    x, _ = self._maximise(models, lambda Xd: eng.feasibility(Xd, c, self.pof_eps), eng=eng)
+                else:
+                    if acquisition_func is None:
+                        fn = "EHVI" if k == 2 else "EHVI_3D"
+                        self._plan_EHVI(eng, fn, self.max_point, pareto.calc_pf(yfeas), cached_samples)
+                    else:
+                        min_scalar = np.min([acquisition_func(y, ref_dir) for y in yfeas])
+                        eng.plan_expected_decomposition(ref_dir, acquisition_func, min_scalar, cached_samples)
+                    eng.plan_constraints(c, self.pof_eps)
+                    x, _ = self._maximise(models, None, eng=eng)
+                picks.append(x)
+                if p + 1 < b:
+                    m = eng.condition(x[None, :])
+                    yfant, gfant = np.vstack((yfant, m[:, :k])), np.vstack((gfant, m[:, k:]))
+            for x in picks:
+                ysample = np.vstack((ysample, self._objective_function(problem, x)))
+                Xsample = np.vstack((Xsample, x))
+            gsample = np.vstack((gsample, self._constraint_values(np.asarray(picks))))
+            done += b
+        return self._constrained_result(ysample, Xsample, gsample, hypervolume_convergence, n_init_samples)
+
+
 class MonoSurrogateOptimiser(BODriver):
     """One GP on scalarised objectives; EI as the acquisition (optimisers.py:283-527)."""
+
+    _pof_objective_models = 1
 
     def _expected_improvement(self, X, model, opt_value, kappa=0.01):
         """optimisers.py:325-344 (σ = sqrt(σ²)); X (d,) → (1,), X (N, d) → (N,)."""
@@ -171,7 +233,10 @@ class MonoSurrogateOptimiser(BODriver):
         return (data - np.min(data)) / (np.max(data) - np.min(data))
 
     def solve(self, aggregation_func, budget=100, n_init_samples=5):
-        """``budget`` true evaluations; with ``batch_size`` q > 1 in ⌈budget/q⌉ iterations (``_solve_batched``)."""
+        """``budget`` true evaluations; with ``batch_size`` q > 1 in ⌈budget/q⌉ iterations (``_solve_batched``).
+        With ``constraints="pof"``: ``_solve_pof``, which returns a ``Constrained_Res``."""
+        if self.constraints == "pof":
+            return self._solve_pof(aggregation_func, budget, n_init_samples)
         if self.batch_size > 1:
             return self._solve_batched(aggregation_func, budget, n_init_samples)
         problem = self.test_problem
@@ -229,3 +294,47 @@ class MonoSurrogateOptimiser(BODriver):
                 Xsample = np.vstack((Xsample, x))
             done += b
         return self._result(ysample, Xsample, hypervolume_convergence, n_init_samples)
+
+    def _solve_pof(self, aggregation_func, budget, n_init_samples):
+        """``constraints="pof"``: ``_solve_batched``'s loop (``batch_size`` 1 is a batch of one) with one GP on the
+        aggregated values and one per inequality constraint, EI weighted by the probability of feasibility, and
+        ``current_best`` taken over the feasible rows only (see MultiSurrogateOptimiser._solve_pof)."""
+        from ..acquisition import engine_for
+        problem = self.test_problem
+        q, c = self.batch_size, self.n_con
+        weights = np.asarray([1 / problem.n_obj] * problem.n_obj)
+        Xsample, ysample = self._initial_samples(n_init_samples)
+        gsample = self._constraint_values(Xsample)
+        self._update_bounds(ysample, aggregation_func)
+        aggregated_samples = np.asarray([aggregation_func(i, weights) for i in ysample]).flatten()
+        ref_dirs = get_reference_directions("das-dennis", problem.n_obj, n_partitions=100)
+        hypervolume_convergence = []
+        done = 0
+        while done < budget:
+            b = min(q, budget - done)
+            self._update_bounds(ysample, aggregation_func)
+            hypervolume_convergence.append(self._hypervolume(ysample[self._feasible(gsample)]))
+            models = self._fit_many(Xsample, np.column_stack((aggregated_samples, gsample)))
+            eng = engine_for(models, self.device)
+            fant, gfant, picks = aggregated_samples, gsample, []
+            for p in range(b):
+                ffeas = fant[self._feasible(gfant)]
+                if len(ffeas) == 0:
+                    x, _ = self._maximise(models, lambda Xd: eng.feasibility(Xd, c, self.pof_eps), eng=eng)
+                else:
+                    eng.plan_ei(ffeas[np.argmin(ffeas)], 0.0)
+                    eng.plan_constraints(c, self.pof_eps)
+                    x, _ = self._maximise(models, None, eng=eng)
+                picks.append(x)
+                if p + 1 < b:
+                    m = eng.condition(x[None, :])
+                    fant, gfant = np.append(fant, m[0, 0]), np.vstack((gfant, m[:, 1:]))
+            for x in picks:
+                next_y = self._objective_function(problem, x)
+                ysample = np.vstack((ysample, next_y))
+                ref_dir = ref_dirs[np.random.randint(0, len(ref_dirs))]
+                aggregated_samples = np.append(aggregated_samples, aggregation_func(next_y, ref_dir))
+                Xsample = np.vstack((Xsample, x))
+            gsample = np.vstack((gsample, self._constraint_values(np.asarray(picks))))
+            done += b
+        return self._constrained_result(ysample, Xsample, gsample, hypervolume_convergence, n_init_samples)

@@ -733,4 +733,28 @@ hipError_t launch_ei(hipStream_t stream, int kind, int k, const double* mu, cons
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------ probability of feasibility
+// The weight of ei_kernel<2> as a kernel of its own (omb_feasibility, omb_plan_constraints): over c rows of
+// constraint moments, F = (((1·Φ(z_0))·Φ(z_1))…), z_j = (0 − μ_j)/sqrt(σ²_j + pof_eps) — that kernel's form of z and
+// its multiplication order, so EI weighted here has the bits of OMB_EI_CONSTRAINED.  out = acq·F (acq null: F
+// alone); out may be acq, which is why neither is __restrict__.  One thread per candidate, row reads coalesced,
+// (2c + 2)·8 bytes per candidate and nothing else: no LDS, no barrier.
+__global__ __launch_bounds__(kAcqThreads) void pof_scale_kernel(const double* __restrict__ mu,
+                                                                const double* __restrict__ var, int64_t ld, int64_t N,
+                                                                int c, double pof_eps, const double* acq,
+                                                                double* out) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
+    double pof = 1.0;
+    for (int j = 0; j < c; ++j) pof *= ndtr((0.0 - mu[j * ld + i]) / sqrt(var[j * ld + i] + pof_eps));
+    out[i] = (acq ? acq[i] : 1.0) * pof;
+  }
+}
+
+hipError_t launch_pof_scale(hipStream_t stream, int c, const double* mu, const double* var, int64_t ld, int64_t N,
+                            double pof_eps, const double* acq, double* out) {
+  hipLaunchKernelGGL(pof_scale_kernel, dim3(acq_grid(N)), dim3(kAcqThreads), 0, stream, mu, var, ld, N, c, pof_eps,
+                     acq, out);
+  return hipGetLastError();
+}
+
 }  // namespace omb

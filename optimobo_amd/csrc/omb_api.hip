@@ -40,6 +40,11 @@ struct Plan {
   const double* geo = nullptr;  // pf / cache / coords / cells on the device
   const uint16_t* boxes = nullptr;
   bool boxes_kd = false;        // PLAN_EHVI_BOXES set by omb_plan_ehvi_boxes_k: the k-D kernel
+  // omb_plan_constraints: context slots k..k+n_con-1 are constraint models, the acquisition is weighted by their
+  // probability of feasibility (σ² of every one of them is computed: their bits are not in var_mask, which covers
+  // the objectives only, and never in the chain's var_skip)
+  int n_con = 0;
+  double con_eps = 0;
 };
 
 struct omb_ctx {
@@ -274,7 +279,7 @@ unsigned all_objectives(int k) { return k >= 32 ? ~0u : (1u << k) - 1u; }
 // objectives in the plan's var_mask only (the others' slots of the workspace keep whatever they held); all_var (the
 // gradient chain, which reads every σ² afterwards, and OMB_DEBUG_POSTERIOR_ALL_VAR) computes all of them.
 int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t N, int64_t offset, double* vals_out,
-              double* result_dev, bool all_var = false) {
+              double* result_dev, bool all_var = false, double* acq_raw = nullptr) {
   int rc = enter(ctx);
   if (rc) return rc;
   const Plan& pl = ctx->plan;
@@ -282,7 +287,7 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
   if (N < 0) return fail(ctx, OMB_EINVAL, "N=%lld < 0", (long long)N);
   GPArgs args;
   int max_R = 0;
-  if ((rc = gather_gp(ctx, pl.k, &args, &max_R))) return rc;
+  if ((rc = gather_gp(ctx, pl.k + pl.n_con, &args, &max_R))) return rc;
   if (!all_var && !ctx->posterior_all_var) args.var_skip = all_objectives(pl.k) & ~pl.var_mask;
   if (sobol) {
     if (ctx->sob_d == 0) return fail(ctx, OMB_ESTATE, "no Sobol state (call omb_set_sobol)");
@@ -295,18 +300,23 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
   }
   if ((N + 31) / 32 > 0x7fffffffLL) return fail(ctx, OMB_EUNSUP, "N=%lld too large", (long long)N);
   const int k = pl.k;
+  const int K = k + pl.n_con;   // rows of the workspace: the objectives, then the constraint models
   const size_t nd = (size_t)N;
   // EHVI-2D with the arg-max's first pass in its launch (launch_ehvi2d_argmax) when only the pair is wanted; its
   // per-workgroup pairs (≤ kArgmaxMaxBlocks) go to ctx->partials
-  const bool acq_argmax = result_dev && !vals_out && N > 0 && ctx->fused_chain && pl.kind == PLAN_EHVI2D;
-  const size_t doubles = 2 * (size_t)k * nd + nd + (nd + 1) / 2 + (sobol ? nd * args.d : 0);
+  const bool acq_argmax = result_dev && !vals_out && N > 0 && ctx->fused_chain && pl.kind == PLAN_EHVI2D &&
+                          pl.n_con == 0;   // the weight comes between EHVI and the arg-max: the plain path
+  const size_t doubles = 2 * (size_t)K * nd + nd + (nd + 1) / 2 + (sobol ? nd * args.d : 0);
   if ((rc = grow_dev(ctx, &ctx->work, &ctx->work_cap, (doubles ? doubles : 1) * sizeof(double), "chain workspace")))
     return rc;
   double* mu = static_cast<double*>(ctx->work);
-  double* var = mu + (size_t)k * nd;
-  double* vals = vals_out ? vals_out : var + (size_t)k * nd;
-  int32_t* raised = reinterpret_cast<int32_t*>(var + (size_t)k * nd + nd);
-  double* Xs = var + (size_t)k * nd + nd + (nd + 1) / 2;
+  double* var = mu + (size_t)K * nd;
+  double* vals = vals_out ? vals_out : var + (size_t)K * nd;
+  int32_t* raised = reinterpret_cast<int32_t*>(var + (size_t)K * nd + nd);
+  double* Xs = var + (size_t)K * nd + nd + (nd + 1) / 2;
+  // with constraints the caller may want the unweighted acquisition kept (omb_eval_grad): it goes to acq_raw and the
+  // weighted value to vals; otherwise the weight is applied in place
+  double* acq = (pl.n_con && acq_raw) ? acq_raw : vals;
 
   hipEvent_t* ev = nullptr;
   if (ctx->timing && ctx->timing_calls++ % ctx->timing_stride == 0) {
@@ -334,8 +344,8 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
   if (sobol) Xc = Xs;
   if (e == hipSuccess) e = mark(1);
   const double* Ld[OMB_MAX_OBJ];
-  gather_Ld(ctx, k, Ld);
-  if (e == hipSuccess && N > 0) e = posterior_any(ctx, args, Ld, k, max_R, Xc, N, mu, var);
+  gather_Ld(ctx, K, Ld);
+  if (e == hipSuccess && N > 0) e = posterior_any(ctx, args, Ld, K, max_R, Xc, N, mu, var);
   if (e == hipSuccess) e = mark(2);
   if (e == hipSuccess && N > 0) {
     switch (pl.kind) {
@@ -347,28 +357,31 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
           e = launch_ehvi2d_argmax(ctx->stream, mu, var, N, N, pl.geo, pl.P, pl.r[0], pl.r[1], pl.s00, pl.s01, pl.mode,
                                    am);
         } else {
-          e = launch_ehvi2d(ctx->stream, mu, var, N, N, pl.geo, pl.P, pl.r[0], pl.r[1], pl.s00, pl.s01, pl.mode, vals);
+          e = launch_ehvi2d(ctx->stream, mu, var, N, N, pl.geo, pl.P, pl.r[0], pl.r[1], pl.s00, pl.s01, pl.mode, acq);
         }
         break;
       case PLAN_EHVI_MC:
-        e = launch_ehvi_mc(ctx->stream, k, mu, var, N, N, pl.geo, pl.M, pl.r, pl.hv, vals, raised);
+        e = launch_ehvi_mc(ctx->stream, k, mu, var, N, N, pl.geo, pl.M, pl.r, pl.hv, acq, raised);
         break;
       case PLAN_EHVI_BOXES:
-        e = pl.boxes_kd ? launch_boxes_k(ctx, k, mu, var, N, N, pl.geo, pl.C, pl.boxes, pl.B, vals)
-                        : launch_ehvi_boxes(ctx->stream, k, mu, var, N, N, pl.geo, pl.C, pl.boxes, pl.B, vals);
+        e = pl.boxes_kd ? launch_boxes_k(ctx, k, mu, var, N, N, pl.geo, pl.C, pl.boxes, pl.B, acq)
+                        : launch_ehvi_boxes(ctx->stream, k, mu, var, N, N, pl.geo, pl.C, pl.boxes, pl.B, acq);
         break;
       case PLAN_HVPOI:
-        e = launch_hvpoi(ctx->stream, mu, var, N, N, pl.geo, pl.C, vals);
+        e = launch_hvpoi(ctx->stream, mu, var, N, N, pl.geo, pl.C, acq);
         break;
       case PLAN_EXPDEC:
-        e = launch_expdec(ctx->stream, pl.sp, mu, var, N, N, pl.geo, pl.M, vals);
+        e = launch_expdec(ctx->stream, pl.sp, mu, var, N, N, pl.geo, pl.M, acq);
         break;
       case PLAN_EI:
-        e = launch_ei(ctx->stream, pl.ei_kind, k, mu, var, N, N, pl.best, pl.var_eps, pl.pof_eps, vals);
+        e = launch_ei(ctx->stream, pl.ei_kind, k, mu, var, N, N, pl.best, pl.var_eps, pl.pof_eps, acq);
         break;
       default:
         return fail(ctx, OMB_ESTATE, "corrupt plan");
     }
+    if (e == hipSuccess && pl.n_con)
+      e = launch_pof_scale(ctx->stream, pl.n_con, mu + (size_t)k * nd, var + (size_t)k * nd, N, N, pl.con_eps, acq,
+                           vals);
   }
   if (e == hipSuccess) e = mark(3);
   if (e == hipSuccess && result_dev && !acq_argmax)
@@ -815,6 +828,17 @@ int omb_ei_ext(omb_ctx* ctx, int kind, int k, const double* mu_dev, const double
   return OMB_OK;
 }
 
+int omb_feasibility(omb_ctx* ctx, int c, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
+                    double pof_eps, const double* acq_dev, double* out_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if ((rc = check_feasibility(E(ctx), c, mu_dev, var_dev, ld, N, pof_eps, out_dev))) return rc;
+  if (N == 0) return OMB_OK;
+  hipError_t e = launch_pof_scale(ctx->stream, c, mu_dev, var_dev, ld, N, pof_eps, acq_dev, out_dev);
+  if (e != hipSuccess) return hip_fail(ctx, e, "feasibility");
+  return OMB_OK;
+}
+
 int omb_argmax_dev(omb_ctx* ctx, const double* vals_dev, int64_t N, int64_t offset, double* result_dev) {
   int rc = enter(ctx);
   if (rc) return rc;
@@ -1011,6 +1035,16 @@ int omb_plan_ei_ext(omb_ctx* ctx, int kind, int k, double best, double var_eps, 
   return OMB_OK;
 }
 
+int omb_plan_constraints(omb_ctx* ctx, int n_con, double pof_eps) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  // a failed call leaves the plan and its previous constraints as they were
+  if ((rc = check_constraints(E(ctx), ctx->plan.kind == PLAN_NONE ? 0 : ctx->plan.k, n_con, pof_eps))) return rc;
+  ctx->plan.n_con = n_con;
+  ctx->plan.con_eps = n_con ? pof_eps : 0.0;
+  return OMB_OK;
+}
+
 int omb_set_sobol(omb_ctx* ctx, int d, int bits, const uint32_t* sv_host, const uint32_t* shift_host,
                   const double* lo_host, const double* hi_host) {
   int rc = enter(ctx);
@@ -1134,21 +1168,23 @@ int omb_eval_grad(omb_ctx* ctx, const double* Xc_dev, int64_t N, double* vals_de
   if (unsup) return fail(ctx, OMB_EUNSUP, "the %s plan has no analytic gradient", unsup);
   GPArgs args;
   int max_R = 0;
-  if ((rc = gather_gp(ctx, pl.k, &args, &max_R))) return rc;
+  const int k = pl.k, K = pl.k + pl.n_con;   // the constraint models' rows follow the objectives'
+  if ((rc = gather_gp(ctx, K, &args, &max_R))) return rc;
   if (N == 0) return OMB_OK;
   if ((N + 31) / 32 > 0x7fffffffLL) return fail(ctx, OMB_EUNSUP, "N=%lld too large", (long long)N);
-  const int k = pl.k;
-  const size_t aux = 2 * (size_t)k * (size_t)N;
+  // ∂a/∂μ | ∂a/∂σ² (K, N) each, then — with constraints — the unweighted acquisition (N), which a·F does not give back
+  const size_t aux = 2 * (size_t)K * (size_t)N + (pl.n_con ? (size_t)N : 0);
   int64_t Nc = 0;
   int n_max = 0;
-  if ((rc = grad_ws(ctx, args, k, N, aux, &Nc, &n_max))) return rc;
-  // the value: omb_eval's own chain, so vals_dev is bitwise omb_eval's; it leaves μ | σ² (k, N) in ctx->work
-  // (every σ²: the gradient kernels below read them all)
-  if ((rc = run_chain(ctx, Xc_dev, false, 0, N, 0, vals_dev, nullptr, true))) return rc;
-  const double* mu = static_cast<const double*>(ctx->work);
-  const double* var = mu + (size_t)k * (size_t)N;
+  if ((rc = grad_ws(ctx, args, K, N, aux, &Nc, &n_max))) return rc;
   double* dadm = static_cast<double*>(ctx->gws);
-  double* dadv = dadm + (size_t)k * (size_t)N;
+  double* dadv = dadm + (size_t)K * (size_t)N;
+  double* acq_raw = pl.n_con ? dadv + (size_t)K * (size_t)N : nullptr;
+  // the value: omb_eval's own chain, so vals_dev is bitwise omb_eval's; it leaves μ | σ² (K, N) in ctx->work
+  // (every σ²: the gradient kernels below read them all)
+  if ((rc = run_chain(ctx, Xc_dev, false, 0, N, 0, vals_dev, nullptr, true, acq_raw))) return rc;
+  const double* mu = static_cast<const double*>(ctx->work);
+  const double* var = mu + (size_t)K * (size_t)N;
   hipError_t e;
   switch (pl.kind) {
     case PLAN_EHVI2D:
@@ -1164,8 +1200,11 @@ int omb_eval_grad(omb_ctx* ctx, const double* Xc_dev, int64_t N, double* vals_de
     default:
       return fail(ctx, OMB_ESTATE, "corrupt plan");
   }
+  if (e == hipSuccess && pl.n_con)
+    e = launch_pof_grad(ctx->stream, acq_raw, mu + (size_t)k * (size_t)N, var + (size_t)k * (size_t)N, N, N, k,
+                        pl.n_con, pl.con_eps, dadm, dadv);
   if (e != hipSuccess) return hip_fail(ctx, e, "acquisition gradient");
-  return grad_chain(ctx, args, k, n_max, Nc, aux, Xc_dev, N, nullptr, nullptr, dadm, dadv, vals_dev, grad_dev);
+  return grad_chain(ctx, args, K, n_max, Nc, aux, Xc_dev, N, nullptr, nullptr, dadm, dadv, vals_dev, grad_dev);
 }
 
 int omb_timing(omb_ctx* ctx, int enable) {

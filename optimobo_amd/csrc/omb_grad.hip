@@ -184,6 +184,62 @@ hipError_t launch_ei_grad(hipStream_t stream, int kind, int k, const double* mu,
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------ probability of feasibility
+// Product rule of a·F, F = Π_j Φ(z_j) over the c constraint rows (omb_plan_constraints; pof_scale_kernel's z): a is
+// the unweighted acquisition, rows 0..k−1 of dadm / dadv hold its partials and are scaled by F, rows k..k+c−1 get
+//   ∂(aF)/∂μ_j = a Π_{q≠j}Φ(z_q) φ(z_j)(−1/s_j),  ∂(aF)/∂σ²_j = a Π_{q≠j}Φ(z_q) φ(z_j) μ_j/(2 s_j³),  s_j = sqrt(σ²_j + pof_eps).
+// The products leave factor j out instead of dividing F by Φ(z_j): finite where F underflows to 0.  mu / var point at
+// constraint row 0 (pitch ld).  The loops have the constant bound kMaxCon and unroll, so Φ and φ stay in registers.
+constexpr int kMaxCon = OMB_MAX_OBJ - 1;
+__global__ __launch_bounds__(kGradThreads) void pof_grad_kernel(const double* __restrict__ a,
+                                                                const double* __restrict__ mu,
+                                                                const double* __restrict__ var, int64_t ld, int64_t N,
+                                                                int k, int c, double pof_eps,
+                                                                double* __restrict__ dadm, double* __restrict__ dadv) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
+    double P[kMaxCon], cm[kMaxCon], cv[kMaxCon];
+    double F = 1.0;
+#pragma unroll
+    for (int j = 0; j < kMaxCon; ++j) {
+      P[j] = 1.0;
+      cm[j] = 0.0;
+      cv[j] = 0.0;
+      if (j < c) {
+        const double mj = mu[j * ld + i], sj = sqrt(var[j * ld + i] + pof_eps);
+        const double z = (0.0 - mj) / sj, pz = npdf(z);
+        P[j] = ndtr(z);
+        cm[j] = pz * (-1.0 / sj);
+        cv[j] = pz * (mj / (2.0 * sj * sj * sj));
+        F *= P[j];
+      }
+    }
+    for (int o = 0; o < k; ++o) {
+      dadm[o * N + i] *= F;
+      dadv[o * N + i] *= F;
+    }
+    const double ai = a[i];
+#pragma unroll
+    for (int j = 0; j < kMaxCon; ++j) {
+      if (j < c) {
+        double others = ai;
+#pragma unroll
+        for (int q = 0; q < kMaxCon; ++q)
+          if (q != j) others *= P[q];   // P[q] = 1 past c
+        dadm[(k + j) * N + i] = others * cm[j];
+        dadv[(k + j) * N + i] = others * cv[j];
+      }
+    }
+  }
+}
+
+hipError_t launch_pof_grad(hipStream_t stream, const double* a, const double* mu, const double* var, int64_t ld,
+                           int64_t N, int k, int c, double pof_eps, double* dadm, double* dadv) {
+  int64_t nb = (N + kGradThreads - 1) / kGradThreads;
+  const dim3 grid((unsigned)(nb > 65536 ? 65536 : (nb < 1 ? 1 : nb))), block(kGradThreads);
+  hipLaunchKernelGGL(pof_grad_kernel, grid, block, 0, stream, a, mu, var, ld, N, k, c, pof_eps, dadm, dadv);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------ EHVI 2-D
 // With E(a; m, s) = sφ(t) + (a − m)Φ(t), t = (a − m)/s (∂E/∂m = −Φ(t), ∂E/∂s = φ(t), any s ≠ 0), stripe i of
 // ehvi2d_point is A_i·E(y2_i; μ1, σB),  A_i = (y1_{i−1} − y1_i)Φ(t_i) + ψ(y1_{i−1}, y1_{i−1}) − ψ(y1_{i−1}, y1_i), and

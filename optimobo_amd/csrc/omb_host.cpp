@@ -95,6 +95,25 @@ int check_ei(std::string* err, int kind, int k, double var_eps, double pof_eps) 
   return OMB_OK;
 }
 
+static bool finite_nonneg(double v) { return v >= 0.0 && v <= 1.79769313486231570815e308; }
+
+int check_constraints(std::string* err, int plan_k, int n_con, double pof_eps) {
+  if (plan_k < 1) return errf(err, OMB_ESTATE, "no acquisition plan to constrain (call an omb_plan_* function first)");
+  if (n_con < 0) return errf(err, OMB_EINVAL, "n_con=%d < 0", n_con);
+  if (!finite_nonneg(pof_eps)) return errf(err, OMB_EINVAL, "pof_eps=%g must be finite and >= 0", pof_eps);
+  if ((int64_t)plan_k + n_con > OMB_MAX_OBJ)
+    return errf(err, OMB_EUNSUP, "%d objectives + %d constraints above the context's %d models", plan_k, n_con,
+                OMB_MAX_OBJ);
+  return OMB_OK;
+}
+
+int check_feasibility(std::string* err, int c, const void* mu, const void* var, int64_t ld, int64_t N, double pof_eps,
+                      const void* out) {
+  if (c < 1 || c > OMB_MAX_OBJ) return errf(err, OMB_EINVAL, "c=%d outside [1, %d]", c, OMB_MAX_OBJ);
+  if (!finite_nonneg(pof_eps)) return errf(err, OMB_EINVAL, "pof_eps=%g must be finite and >= 0", pof_eps);
+  return check_moments(err, mu, var, ld, N, c, out);
+}
+
 int check_hvpoi(std::string* err, int C) {
   if (C < 1 || 4 * (int64_t)C > kMaxLdsDoubles)
     return errf(err, OMB_EUNSUP, "cell count C=%d outside [1, %d]", C, kMaxLdsDoubles / 4);

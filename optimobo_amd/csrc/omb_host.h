@@ -49,6 +49,12 @@ int check_boxes_k(std::string* err, int k, int C, int64_t B);
 int check_box_list(std::string* err, int k, int C, const uint16_t* boxes, int64_t B);
 int check_ei(std::string* err, int kind, int k, double var_eps, double pof_eps);
 int check_hvpoi(std::string* err, int C);
+// omb_plan_constraints on a plan over plan_k objectives (0: none set): OMB_ESTATE with no plan, OMB_EINVAL for
+// n_con < 0 or a negative / non-finite pof_eps, OMB_EUNSUP for plan_k + n_con > OMB_MAX_OBJ — in that order.
+int check_constraints(std::string* err, int plan_k, int n_con, double pof_eps);
+// omb_feasibility: 1 ≤ c ≤ OMB_MAX_OBJ, pof_eps finite and ≥ 0, then check_moments over the c rows.
+int check_feasibility(std::string* err, int c, const void* mu, const void* var, int64_t ld, int64_t N, double pof_eps,
+                      const void* out);
 // omb_posterior_grad: 1 ≤ n_obj ≤ OMB_MAX_OBJ, N ≥ 0, and with N > 0 no null candidate / output pointer.
 int check_posterior_grad(std::string* err, int n_obj, const void* Xc, int64_t N, const void* mu, const void* var,
                          const void* dmu, const void* dvar);

@@ -113,6 +113,11 @@ hipError_t launch_expdec(hipStream_t stream, const ScalParams& sp, const double*
 hipError_t launch_ei(hipStream_t stream, int kind, int k, const double* mu, const double* var, int64_t ld, int64_t N,
                      double best, double var_eps, double pof_eps, double* out);
 
+// out = acq·F (acq null: F), F the probability of feasibility over c rows of constraint moments (mu, var at row 0 of
+// the constraints, pitch ld); out may be acq (omb_feasibility, omb_plan_constraints)
+hipError_t launch_pof_scale(hipStream_t stream, int c, const double* mu, const double* var, int64_t ld, int64_t N,
+                            double pof_eps, const double* acq, double* out);
+
 // Deterministic arg-max; `partials` must hold kArgmaxMaxBlocks (val, idx) pairs followed by one zeroed ticket word
 // (one_pass: both passes in one launch, the last workgroup to arrive reducing; it leaves the word zeroed again).
 constexpr int kArgmaxMaxBlocks = 1024;
@@ -294,6 +299,10 @@ hipError_t launch_grad_contract(hipStream_t stream, const GradArgs& ga, int kind
 // ∂a/∂μ_o, ∂a/∂σ²_o of the acquisitions (rows o of dadm / dadv, pitch N), arguments as the value launchers'
 hipError_t launch_ei_grad(hipStream_t stream, int kind, int k, const double* mu, const double* var, int64_t ld,
                           int64_t N, double best, double var_eps, double pof_eps, double* dadm, double* dadv);
+// the product rule of a·F over dadm / dadv (k + c rows, pitch N): rows 0..k-1, the plan's partials, scaled by F; rows
+// k.. filled with the constraints' (a: the unweighted acquisition; mu / var: constraint row 0, pitch ld)
+hipError_t launch_pof_grad(hipStream_t stream, const double* a, const double* mu, const double* var, int64_t ld,
+                           int64_t N, int k, int c, double pof_eps, double* dadm, double* dadv);
 hipError_t launch_ehvi2d_grad(hipStream_t stream, const double* mu, const double* var, int64_t ld, int64_t N,
                               const double* pf, int P, double r0, double r1, double s00, double s01, int mode,
                               double* dadm, double* dadv);

@@ -240,6 +240,17 @@ class AcqContext:
                                         float(var_eps), float(pof_eps), _ptr(out)), "omb_ei_ext")
         return out
 
+    def feasibility(self, mu, var, pof_eps=1e-5, acq=None, out=None):
+        """omb_feasibility: the probability of feasibility F = Π_j Φ(−μ_j / sqrt(σ²_j + pof_eps)) over the rows of
+        (mu, var) (c, N) — constraint models, feasible where g ≤ 0 — times ``acq`` (N,) when given (``out`` may be
+        ``acq``)."""
+        c, N = mu.shape
+        out = out if out is not None else torch.empty(N, dtype=torch.float64, device=self.device)
+        self._stream()
+        self._check(self.lib.omb_feasibility(self._h, c, _ptr(mu), _ptr(var), mu.stride(0), N, float(pof_eps),
+                                             _ptr(acq) if acq is not None else None, _ptr(out)), "omb_feasibility")
+        return out
+
     def argmax_dev(self, vals, offset=0, out=None):
         out = out if out is not None else torch.empty(2, dtype=torch.float64, device=self.device)
         self._stream()
@@ -308,6 +319,13 @@ class AcqContext:
     def plan_ei_ext(self, kind, k, best, var_eps=0.0, pof_eps=0.0):
         kid = {"plain": _lib.EI_PLAIN, "pareto": _lib.EI_PARETO, "constrained": _lib.EI_CONSTRAINED}[kind]
         self._plan("omb_plan_ei_ext", kid, int(k), float(best), float(var_eps), float(pof_eps))
+
+    def plan_constraints(self, n_con, pof_eps=1e-5):
+        """omb_plan_constraints: the plan that is set treats objective slots k..k+n_con-1 as constraint models
+        (g ≤ 0 feasible) and weights its acquisition by their probability of feasibility.  Every plan_* call clears
+        this, so it comes after the plan; n_con = 0 clears it too.  A failed call changes nothing."""
+        self._stream()
+        self._check(self.lib.omb_plan_constraints(self._h, int(n_con), float(pof_eps)), "omb_plan_constraints")
 
     def set_sobol(self, d, lo, hi, seed=None, scramble=True, state=None):
         """Device Sobol' engine = scipy qmc.Sobol(d, scramble=scramble, seed=seed) over [lo, hi]."""
