@@ -219,6 +219,24 @@ int omb_ehvi_boxes(omb_ctx* ctx, int k, const double* mu_dev, const double* var_
 int omb_ehvi_boxes_k(omb_ctx* ctx, int k, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
                      const double* coords_dev, int C, const uint16_t* boxes_dev, int B, double* out_dev);
 
+/* Hypervolume improvement of N points over the front behind the same box decomposition — the σ → 0 limit of the exact
+ * EHVI, and what a Thompson batch scores a joint posterior draw with:
+ *   out_dev[i] = HVI(y_i) = Σ_b Π_j (hi_bj − max(y_ij, lo_bj))⁺
+ * y_dev is objective-major like μ everywhere else: row j starts at y_dev + j·ld, point i is column i (ld ≥ N).
+ * coords_dev (k, C) and boxes_dev (B, 2k) are exactly omb_ehvi_boxes_k's (leading −∞ column, uint16 index pairs,
+ * 4-byte aligned).  One lane per point; LDS holds the k·C grid doubles alone, the box list (up to 2^24 boxes) is
+ * streamed in list order.  The sum runs in slices of 1024 boxes, the slices added in slice order, so a point's value
+ * is bitwise the same whatever N, its column or the launch shape (a small batch gives every slice a workgroup row of
+ * its own and adds the stored sums in the same order).  Asynchronous on the context's stream.
+ *   a NaN coordinate: NaN for that point; y_j ≥ r_j (+∞ included): exactly 0; −∞: inf or NaN
+ *   OMB_EINVAL  k outside [2, OMB_MAX_OBJ], N < 0, B < 1, a null pointer, a pointer off its alignment (8 bytes; the
+ *               box list 4), ld < N
+ *   OMB_EUNSUP  C < 2, k·C > 8192 (the grid in 64 KiB of LDS), B > 2^24
+ * in that order; N = 0 returns OMB_OK and writes nothing.  Indices are not checked (the list is on the device); one
+ * past the grid reads the grid's last coordinate. */
+int omb_hvi_boxes(omb_ctx* ctx, int k, const double* y_dev, int64_t ld, int64_t N, const double* coords_dev, int C,
+                  const uint16_t* boxes_dev, int B, double* out_dev);
+
 /* Hypervolume-based PoI of EMO (emo.py:176-228): cells_dev (C, 2, 2) [upper, lower]. */
 int omb_hvpoi(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
               const double* cells_dev, int C, double* out_dev);

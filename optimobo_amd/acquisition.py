@@ -122,6 +122,76 @@ class AcquisitionEngine:
         coords, _, boxes = pareto.box_decomposition(PF, max_point, max_boxes=max_boxes)
         return self.ctx.ehvi_boxes(mu, var, coords, boxes)
 
+    def hvi(self, Y, max_point, PF, max_boxes=1 << 20):
+        """Hypervolume improvement HV(PF ∪ {y}) − HV(PF) of every row of Y (N, k) — host values or a device
+        tensor — over the front PF (2 to 8 objectives): the box sum of omb_hvi_boxes over the decomposition
+        ``ehvi_exact`` uses → device tensor (N,).  ValueError when the decomposition needs more than max_boxes."""
+        coords, _, boxes = pareto.box_decomposition(PF, max_point, max_boxes=max_boxes)
+        Yd = Y if isinstance(Y, torch.Tensor) else self._dev(np.atleast_2d(Y))
+        return self.ctx.hvi_boxes(Yd.to(device=self.device, dtype=torch.float64).T.contiguous(), coords, boxes)
+
+    def thompson_batch(self, q, lower, upper, PF=None, max_point=None, n_candidates=None, seed=0,
+                       max_boxes=1 << 20):
+        """A batch of q proposals by Thompson sampling over the loaded models → (X (q, d), info).
+
+        The candidates are the first ``n_candidates`` points of the device Sobol' sequence seeded by ``seed``
+        (default TuRBO's count min(100·d, 5000); at most the 2^18 of omb_thompson_select).  Every loaded model
+        gives q joint posterior draws over them (one ``posterior_samples`` call per model, z (q, N_c) per model in
+        model order from ``numpy.random.default_rng(seed)``, TuRBO's jitter ladder): the surrogates are
+        independent, so are their draws.  Draw b then nominates one candidate:
+
+        * one loaded model: the candidate with the smallest drawn value (the surrogate is minimised);
+        * k ≥ 2 models and a front ``PF`` with reference point ``max_point``: the candidate whose drawn
+          objective vector has the largest hypervolume improvement over the front (``hvi_boxes`` once over the
+          (k, q·N_c) draws, negated into ``thompson_select``).
+
+        ``thompson_select``'s rules hold either way: the lowest index among equals, no candidate twice.  A draw
+        in which no candidate improves the front has HVI ≡ 0 and so nominates the lowest-index candidate not yet
+        picked — a point of the space-filling sequence: the exploration fallback.  ``info``: ``indices`` (q,),
+        ``values`` (q,) the HVI (or drawn value) of each pick under its draw, ``jitter`` per model, ``zero_draws``
+        the number of draws with HVI ≡ 0 (0 with one model), ``n_candidates``.  OMBError (OMB_ENOTPD) when a
+        covariance cannot be factorised within the ladder; ValueError when the front needs more than max_boxes
+        boxes.  The installed plan and the loaded states are left as they are."""
+        lower = np.asarray(lower, np.float64).reshape(-1)
+        upper = np.asarray(upper, np.float64).reshape(-1)
+        d, k, q = lower.size, self.n_obj, int(q)
+        if k < 1:
+            raise RuntimeError("thompson_batch: no models loaded (call load_models first)")
+        n_c = min(100 * d, 5000) if n_candidates is None else int(n_candidates)
+        n_c = min(n_c, 1 << 18)
+        if not 1 <= q <= n_c:
+            raise ValueError(f"thompson_batch: q={q} outside [1, {n_c}] candidates")
+        geo = None
+        if k > 1:
+            if PF is None or max_point is None:
+                raise ValueError(f"thompson_batch: {k} models need the front PF and its reference point max_point")
+            coords, _, boxes = pareto.box_decomposition(PF, max_point, max_boxes=max_boxes)
+            if coords.shape[0] != k:
+                raise ValueError(f"thompson_batch: front of {coords.shape[0]} objectives for {k} models")
+            geo = (coords, boxes)
+        self.ctx.set_sobol(d, lower, upper, seed=seed)
+        Xc = self.ctx.sobol(0, n_c)
+        rng = np.random.default_rng(seed)
+        draws = torch.empty((k, q, n_c), dtype=torch.float64, device=self.device)
+        jitter = []
+        for o in range(k):
+            Z = self._dev(rng.standard_normal((q, n_c)))
+            _, j = self.ctx.posterior_samples(o, Xc, Z, out=draws[o])
+            jitter.append(j)
+        zero = 0
+        if k == 1:
+            score = draws[0]
+            idx = self.ctx.thompson_select(score)
+            values = score[torch.arange(q, device=self.device), idx].cpu().numpy()
+        else:
+            h = self.ctx.hvi_boxes(draws.reshape(k, q * n_c), *geo).reshape(q, n_c)
+            idx = self.ctx.thompson_select(-h)
+            values = h[torch.arange(q, device=self.device), idx].cpu().numpy()
+            zero = int((h.max(dim=1).values <= 0).sum().item())
+        idx = idx.cpu().numpy()
+        X = Xc[torch.as_tensor(idx, device=self.device)].cpu().numpy()
+        return X, dict(indices=idx, values=values, jitter=jitter, zero_draws=zero, n_candidates=n_c)
+
     def ehvi3d(self, Xc, max_point, PF, cache):
         """util_functions.EHVI_3D (Monte-Carlo form) on every row of Xc, for k = n_obj ≥ 3 objectives (the
         reference calls it for every n_obj != 2): (values (N,), raised (N,) int32)."""

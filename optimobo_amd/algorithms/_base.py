@@ -6,10 +6,13 @@ parego.py:148-298).  What changes is the acquisition maximiser: the reference's 
 ``differential_evolution`` is replaced by the batched device arg-max
 (optimobo_amd.acquisition.AcquisitionEngine.maximise).
 """
+import warnings
+
 import numpy as np
 
 from .. import pareto
 from .. import util_functions
+from .._lib import OMB_ENOTPD, OMBError
 from ..acquisition import engine_for
 from ..gp import GPRegression, Matern52, apply_noise_option, check_noise_option, fit_concurrently
 from ..parallel import agree_host_rng
@@ -21,10 +24,13 @@ class BODriver:
     # MonoSurrogateOptimiser); None: the driver does not take the keyword's "pof"
     _pof_objective_models = None
     pof_eps = 1e-5      # added to the constraint models' σ² inside the probability of feasibility (cParEGO's value)
+    # batch_strategy values the driver takes: the drivers that ignore batch_size take the default alone
+    _batch_strategies = ("believer",)
+    thompson_candidates = None   # candidates of a Thompson batch (None: AcquisitionEngine.thompson_batch's default)
 
     def __init__(self, test_problem, ideal_point=None, max_point=None, mode="reference", n_candidates=1 << 14,
                  refine_rounds=2, seed=None, device=None, polish=True, starts=None, noise=0.0, batch_size=1,
-                 constraints=None):
+                 constraints=None, batch_strategy="believer"):
         self.test_problem = test_problem
         self.max_point = max_point
         self.ideal_point = ideal_point
@@ -60,7 +66,24 @@ class BODriver:
         # supported"): None ignores them, as the reference does; "pof" fits one GP per constraint and weights the
         # acquisition by the probability of feasibility (g <= 0 feasible)
         self.constraints = self._check_constraints_option(constraints)
+        # how a batch is built (not in the reference): "believer" picks one point after another, conditioning the
+        # surrogates on each pick's posterior mean; "thompson" takes q joint posterior draws over one candidate set
+        # and lets every draw nominate its best candidate (AcquisitionEngine.thompson_batch)
+        self.batch_strategy = self._check_batch_strategy(batch_strategy)
+        self.thompson_fallbacks = 0    # Thompson iterations that fell back to the believer batch
         self._iteration = 0
+
+    def _check_batch_strategy(self, batch_strategy):
+        if batch_strategy not in ("believer", "thompson"):
+            raise ValueError(f"batch_strategy must be 'believer' or 'thompson', not {batch_strategy!r}")
+        if batch_strategy not in self._batch_strategies:
+            raise ValueError(f"{type(self).__name__} ignores batch_size and takes batch_strategy='believer' alone "
+                             "(MultiSurrogateOptimiser with an EHVI acquisition and MonoSurrogateOptimiser support "
+                             "'thompson')")
+        if batch_strategy == "thompson" and self.constraints == "pof":
+            raise ValueError("batch_strategy='thompson' does not support constraints='pof' (supported: "
+                             "constraints=None; 'believer' batches take constraints='pof')")
+        return batch_strategy
 
     def _check_constraints_option(self, constraints):
         if constraints is None:
@@ -153,6 +176,29 @@ class BODriver:
         self._iteration += 1
         return eng.maximise(acq_fn, self.test_problem.xl, self.test_problem.xu, n_candidates=self.n_candidates,
                             seed=seed, refine_rounds=self.refine_rounds, polish=self.polish, starts=self.starts)
+
+    def _thompson_picks(self, eng, b, PF=None):
+        """``b`` proposals of one iteration by AcquisitionEngine.thompson_batch on ``eng`` as it stands (seeded as
+        ``_maximise`` seeds a search, so every rank computes the same batch), or None when that iteration has to
+        fall back to the believer batch: the draws' covariance could not be factorised within the jitter ladder
+        (OMB_ENOTPD — near-singular fits can exhaust it) or the front needs more boxes than the budget
+        (pareto.BoxBudgetError).  A fallback warns and is counted in ``thompson_fallbacks``; any other error of the
+        call — a batch larger than the candidate set, say — is the caller's and is raised."""
+        seed = (self.seed if self.seed is not None else np.random.randint(0, 2 ** 31 - 1)) + 7919 * self._iteration
+        self._iteration += 1
+        try:
+            X, _ = eng.thompson_batch(b, self.test_problem.xl, self.test_problem.xu, PF=PF,
+                                      max_point=self.max_point if PF is not None else None,
+                                      n_candidates=self.thompson_candidates, seed=seed,
+                                      max_boxes=getattr(self, "exact_max_boxes", 1 << 20))
+        except (OMBError, pareto.BoxBudgetError) as e:
+            if isinstance(e, OMBError) and e.code != OMB_ENOTPD:
+                raise
+            self.thompson_fallbacks += 1
+            warnings.warn(f"Thompson batch unavailable this iteration ({e}); using the Kriging-believer batch",
+                          RuntimeWarning, stacklevel=3)
+            return None
+        return list(X)
 
     def _result(self, ysample, Xsample, hypervolume_convergence, n_init_samples):
         pf_approx = util_functions.calc_pf(ysample)

@@ -31,6 +31,7 @@ class MultiSurrogateOptimiser(BODriver):
 
     exact_max_boxes = 1 << 17       # boxes of one iteration's exact EHVI at n_obj ≥ 4
     _pof_objective_models = "n_obj"
+    _batch_strategies = ("believer", "thompson")
 
     def _get_cached_samples(self, dimensions, sample_exponent):
         """optimisers.py:121-141 — scrambled Sobol mapped through the normal ppf."""
@@ -88,7 +89,10 @@ class MultiSurrogateOptimiser(BODriver):
         With ``constraints="pof"``: ``_solve_pof``, which returns a ``Constrained_Res``."""
         if self.constraints == "pof":
             return self._solve_pof(budget, n_init_samples, sample_exponent, acquisition_func)
-        if self.batch_size > 1:
+        if self.batch_strategy == "thompson" and acquisition_func is not None:
+            raise ValueError("batch_strategy='thompson' scores draws by hypervolume improvement: it supports the EHVI "
+                             "acquisitions (acquisition_func=None), not a scalarised expected decomposition")
+        if self.batch_size > 1 or self.batch_strategy == "thompson":
             return self._solve_batched(budget, n_init_samples, sample_exponent, acquisition_func)
         problem = self.test_problem
         Xsample, ysample = self._initial_samples(n_init_samples)
@@ -119,7 +123,11 @@ class MultiSurrogateOptimiser(BODriver):
         reference direction) and maximises it; before the next pick the resident GPs are conditioned on the point
         with their own posterior mean as its value (AcquisitionEngine.condition: μ stays, σ² collapses around the
         pick, so the next arg-max moves on).  The picks are then evaluated for real; the next iteration's fit
-        uploads the fitted states again, so no fantasy outlives its batch."""
+        uploads the fitted states again, so no fantasy outlives its batch.
+
+        ``batch_strategy="thompson"`` (EHVI acquisitions): after the fit, one AcquisitionEngine.thompson_batch over
+        the true samples' front proposes all b points at once (``_thompson_picks``); an iteration it cannot serve
+        is built by the believer loop above instead.  It draws no reference direction."""
         from ..acquisition import engine_for
         problem = self.test_problem
         q = self.batch_size
@@ -134,19 +142,23 @@ class MultiSurrogateOptimiser(BODriver):
             hypervolume_convergence.append(self._hypervolume(ysample))
             models = self._fit_many(Xsample, ysample[:, :problem.n_obj])
             eng = engine_for(models, self.device)
-            yfant, picks = ysample[:, :problem.n_obj], []
-            for p in range(b):
-                ref_dir = np.asarray(ref_dirs[np.random.randint(0, len(ref_dirs))])
-                if acquisition_func is None:
-                    fn = "EHVI" if problem.n_obj == 2 else "EHVI_3D"
-                    self._plan_EHVI(eng, fn, self.max_point, pareto.calc_pf(yfant), cached_samples)
-                else:
-                    min_scalar = np.min([acquisition_func(y, ref_dir) for y in yfant])
-                    eng.plan_expected_decomposition(ref_dir, acquisition_func, min_scalar, cached_samples)
-                x, _ = self._maximise(models, None, eng=eng)
-                picks.append(x)
-                if p + 1 < b:
-                    yfant = np.vstack((yfant, eng.condition(x[None, :])))
+            yfant, picks = ysample[:, :problem.n_obj], None
+            if self.batch_strategy == "thompson":
+                picks = self._thompson_picks(eng, b, pareto.calc_pf(yfant))
+            if picks is None:              # the believer batch (also a Thompson iteration's fallback)
+                picks = []
+                for p in range(b):
+                    ref_dir = np.asarray(ref_dirs[np.random.randint(0, len(ref_dirs))])
+                    if acquisition_func is None:
+                        fn = "EHVI" if problem.n_obj == 2 else "EHVI_3D"
+                        self._plan_EHVI(eng, fn, self.max_point, pareto.calc_pf(yfant), cached_samples)
+                    else:
+                        min_scalar = np.min([acquisition_func(y, ref_dir) for y in yfant])
+                        eng.plan_expected_decomposition(ref_dir, acquisition_func, min_scalar, cached_samples)
+                    x, _ = self._maximise(models, None, eng=eng)
+                    picks.append(x)
+                    if p + 1 < b:
+                        yfant = np.vstack((yfant, eng.condition(x[None, :])))
             for x in picks:
                 ysample = np.vstack((ysample, self._objective_function(problem, x)))
                 Xsample = np.vstack((Xsample, x))
@@ -214,6 +226,7 @@ class MonoSurrogateOptimiser(BODriver):
     """One GP on scalarised objectives; EI as the acquisition (optimisers.py:283-527)."""
 
     _pof_objective_models = 1
+    _batch_strategies = ("believer", "thompson")
 
     def _expected_improvement(self, X, model, opt_value, kappa=0.01):
         """optimisers.py:325-344 (σ = sqrt(σ²)); X (d,) → (1,), X (N, d) → (N,)."""
@@ -237,7 +250,7 @@ class MonoSurrogateOptimiser(BODriver):
         With ``constraints="pof"``: ``_solve_pof``, which returns a ``Constrained_Res``."""
         if self.constraints == "pof":
             return self._solve_pof(aggregation_func, budget, n_init_samples)
-        if self.batch_size > 1:
+        if self.batch_size > 1 or self.batch_strategy == "thompson":
             return self._solve_batched(aggregation_func, budget, n_init_samples)
         problem = self.test_problem
         weights = np.asarray([1 / problem.n_obj] * problem.n_obj)
@@ -262,7 +275,9 @@ class MonoSurrogateOptimiser(BODriver):
     def _solve_batched(self, aggregation_func, budget, n_init_samples):
         """Sequential-greedy batches with the Kriging believer (see MultiSurrogateOptimiser._solve_batched): one
         fit per iteration; every pick's ``current_best`` is the minimum over the true and the fantasised
-        aggregated values, and the resident GP is conditioned on the pick with its posterior mean before the next."""
+        aggregated values, and the resident GP is conditioned on the pick with its posterior mean before the next.
+        ``batch_strategy="thompson"``: one AcquisitionEngine.thompson_batch on the single surrogate instead (every
+        draw nominates the candidate with its smallest drawn value), with the believer loop as its fallback."""
         from ..acquisition import engine_for
         problem = self.test_problem
         q = self.batch_size
@@ -279,13 +294,17 @@ class MonoSurrogateOptimiser(BODriver):
             hypervolume_convergence.append(self._hypervolume(ysample))
             model = self._fit(Xsample, aggregated_samples)
             eng = engine_for([model], self.device)
-            fant, picks = aggregated_samples, []
-            for p in range(b):
-                eng.plan_ei(fant[np.argmin(fant)], 0.0)
-                x, _ = self._maximise([model], None, eng=eng)
-                picks.append(x)
-                if p + 1 < b:
-                    fant = np.append(fant, eng.condition(x[None, :])[0, 0])
+            fant, picks = aggregated_samples, None
+            if self.batch_strategy == "thompson":
+                picks = self._thompson_picks(eng, b)
+            if picks is None:              # the believer batch (also a Thompson iteration's fallback)
+                picks = []
+                for p in range(b):
+                    eng.plan_ei(fant[np.argmin(fant)], 0.0)
+                    x, _ = self._maximise([model], None, eng=eng)
+                    picks.append(x)
+                    if p + 1 < b:
+                        fant = np.append(fant, eng.condition(x[None, :])[0, 0])
             for x in picks:
                 next_y = self._objective_function(problem, x)
                 ysample = np.vstack((ysample, next_y))

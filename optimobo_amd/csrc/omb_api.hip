@@ -96,6 +96,9 @@ struct omb_ctx {
   // omb_gp_append: the bordered state (AppendWs)
   void* aws = nullptr;
   size_t aws_cap = 0;
+  // omb_hvi_boxes: the slices' sums of a small batch (hvi_ws_doubles)
+  void* hws = nullptr;
+  size_t hws_cap = 0;
   // device fault word (pinned, mapped host memory): kernels mark it, enter() reports it
   int* fault_host = nullptr;
   int* fault_dev = nullptr;
@@ -449,6 +452,7 @@ int omb_destroy(omb_ctx* ctx) {
   if (ctx->dws) (void)hipFree(ctx->dws);
   if (ctx->gws) (void)hipFree(ctx->gws);
   if (ctx->aws) (void)hipFree(ctx->aws);
+  if (ctx->hws) (void)hipFree(ctx->hws);
   if (ctx->fault_host) (void)hipHostFree(ctx->fault_host);
   if (ctx->fit_host) (void)hipHostFree(ctx->fit_host);
   for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
@@ -780,6 +784,21 @@ int omb_ehvi_boxes_k(omb_ctx* ctx, int k, const double* mu_dev, const double* va
   if (N == 0) return OMB_OK;
   hipError_t e = launch_boxes_k(ctx, k, mu_dev, var_dev, ld, N, coords_dev, C, boxes_dev, B, out_dev);
   if (e != hipSuccess) return hip_fail(ctx, e, "ehvi_boxes_k");
+  return OMB_OK;
+}
+
+int omb_hvi_boxes(omb_ctx* ctx, int k, const double* y_dev, int64_t ld, int64_t N, const double* coords_dev, int C,
+                  const uint16_t* boxes_dev, int B, double* out_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if ((rc = check_hvi_boxes(E(ctx), k, y_dev, ld, N, coords_dev, C, boxes_dev, B, out_dev))) return rc;
+  if (N == 0) return OMB_OK;
+  const int64_t wsd = hvi_ws_doubles(N, B);
+  if (wsd && (rc = grow_dev(ctx, &ctx->hws, &ctx->hws_cap, sizeof(double) * (size_t)wsd, "HVI slice workspace")))
+    return rc;
+  hipError_t e = launch_hvi_boxes(ctx->stream, k, y_dev, ld, N, coords_dev, C, boxes_dev, B, out_dev,
+                                  wsd ? static_cast<double*>(ctx->hws) : nullptr);
+  if (e != hipSuccess) return hip_fail(ctx, e, "hvi_boxes");
   return OMB_OK;
 }
 

@@ -76,6 +76,26 @@ int check_boxes_k(std::string* err, int k, int C, int64_t B) {
   return OMB_OK;
 }
 
+int check_hvi_boxes(std::string* err, int k, const void* y, int64_t ld, int64_t N, const void* coords, int C,
+                    const void* boxes, int64_t B, const void* out) {
+  if (k < 2 || k > OMB_MAX_OBJ)
+    return errf(err, OMB_EINVAL, "hypervolume improvement needs 2 <= k <= %d objectives (k=%d)", OMB_MAX_OBJ, k);
+  if (N < 0) return errf(err, OMB_EINVAL, "N=%lld < 0", (long long)N);
+  if (B < 1) return errf(err, OMB_EINVAL, "empty box list");
+  if (!coords || !boxes) return errf(err, OMB_EINVAL, "null grid/box list");
+  if (N > 0 && (!y || !out)) return errf(err, OMB_EINVAL, "null device pointer");
+  if (((uintptr_t)y | (uintptr_t)coords | (uintptr_t)out) & 7)
+    return errf(err, OMB_EINVAL, "points, grid or output not 8-byte aligned");
+  if ((uintptr_t)boxes & 3) return errf(err, OMB_EINVAL, "box list not 4-byte aligned");
+  if (ld < N) return errf(err, OMB_EINVAL, "ld=%lld < N=%lld", (long long)ld, (long long)N);
+  // the grid alone is staged in the 64 KiB of dynamic LDS; the box list is streamed
+  if (C < 2 || (int64_t)k * C > kMaxLdsDoubles)
+    return errf(err, OMB_EUNSUP, "grid size C=%d outside [2, %d] for k=%d (k*C <= %d)", C, kMaxLdsDoubles / k, k,
+                kMaxLdsDoubles);
+  if (B > kMaxBoxesK) return errf(err, OMB_EUNSUP, "box count B=%lld above %d", (long long)B, kMaxBoxesK);
+  return OMB_OK;
+}
+
 int check_box_list(std::string* err, int k, int C, const uint16_t* boxes, int64_t B) {
   for (int64_t b = 0; b < B; ++b)
     for (int j = 0; j < k; ++j) {

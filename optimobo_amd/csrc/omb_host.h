@@ -45,6 +45,11 @@ int check_boxes(std::string* err, int k, int C, int B);
 // omb_ehvi_boxes_k / omb_plan_ehvi_boxes_k: 2 ≤ k ≤ OMB_MAX_OBJ, 3·k·C + 2·k + 4 ≤ kMaxLdsDoubles, 1 ≤ B ≤ kMaxBoxesK.
 constexpr int kMaxBoxesK = 1 << 24;
 int check_boxes_k(std::string* err, int k, int C, int64_t B);
+// omb_hvi_boxes, in this order: OMB_EINVAL for k outside [2, OMB_MAX_OBJ], N < 0, B < 1, a null grid / box list (and,
+// with N > 0, a null y / out), a pointer off its alignment (8 bytes; the box list 4) or ld < N; OMB_EUNSUP for C < 2,
+// k·C > kMaxLdsDoubles or B > kMaxBoxesK.
+int check_hvi_boxes(std::string* err, int k, const void* y, int64_t ld, int64_t N, const void* coords, int C,
+                    const void* boxes, int64_t B, const void* out);
 // Every box of a host box list (B, 2k): lo index < hi index < C (an index past the grid would be read from LDS).
 int check_box_list(std::string* err, int k, int C, const uint16_t* boxes, int64_t B);
 int check_ei(std::string* err, int kind, int k, double var_eps, double pof_eps);

@@ -1,0 +1,128 @@
+// Hypervolume improvement of points over a box decomposition (omb_hvi_boxes): the σ → 0 limit of the exact EHVI,
+//   HVI(y) = Σ_b Π_j (hi_bj − max(y_j, lo_bj))⁺,
+// over the boxes omb_ehvi_boxes_k takes (grid (k, C) with a leading −∞ column, uint16 index pairs).  No Φ, no φ and
+// no division: a box costs a point 4 VALU operations per objective, so nothing is tabulated per point.
+//
+//   * One lane per point; its K coordinates stay in registers (K a template parameter).
+//   * LDS holds the K·C grid doubles alone, staged once per workgroup.  The box index is wave-uniform: the box's K
+//     32-bit index words come through the scalar cache, and the 2K grid reads go to addresses every lane shares, which
+//     the LDS broadcasts (one pass per 32-lane half, no conflicts).  Grid indices are clamped to the grid, so a bad
+//     list reads a wrong coordinate, never past the staged doubles.
+//   * Every lane walks the boxes in list order, in slices of kHviSlice boxes: a slice's terms are summed from 0 in
+//     list order, and the slices' sums are added in slice order.  The slice boundaries depend on B alone.  A large
+//     batch walks all slices in one launch; a small one (too few workgroups to fill the chip) gives every slice a
+//     workgroup row of its own (blockIdx.y), which stores the slice's sum to a workspace, and hvi_finish_kernel adds
+//     them in slice order.  Both forms perform the same additions in the same order: a point's value depends on its
+//     coordinates, the grid and the box list, not on N, its column, the launch shape or which form ran.  No atomics.
+//   * A NaN coordinate makes the point's value NaN (fmax would drop it); y_j ≥ r_j zeroes every box's factor j, as
+//     every hi_bj ≤ r_j, so the value is exactly 0.
+#include "omb_internal.h"
+
+namespace omb {
+
+constexpr int kHviThreads = 256;
+constexpr int kHviSlice = 1024;           // boxes per slice
+constexpr int64_t kHviSplitBlocks = 512;  // fewer point workgroups than this (2 per CU): one workgroup row per slice
+constexpr int64_t kHviSplitWs = 1 << 23;  // workspace doubles the split form may ask for (64 MiB)
+
+// one slice's sum for the point y: boxes [b0, b1) in list order
+template <int K>
+__device__ __forceinline__ double hvi_slice(const double (&y)[K], const double* grid, int C,
+                                            const uint32_t* __restrict__ boxes, int b0, int b1) {
+#pragma clang fp contract(off)   // the one fused operation is the explicit fma below, in both forms of the kernel
+  double p = 0.0;
+  for (int b = b0; b < b1; ++b) {
+    double t[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const uint32_t w = boxes[(size_t)b * K + j];   // lo | hi << 16, wave-uniform
+      const int il = min((int)(w & 0xffffu), C - 1), ih = min((int)(w >> 16), C - 1);
+      const double lo = grid[j * C + il], hi = grid[j * C + ih];
+      t[j] = fmax(hi - fmax(y[j], lo), 0.0);
+    }
+    double prod = t[0];
+#pragma unroll
+    for (int j = 1; j < K - 1; ++j) prod *= t[j];
+    p = fma(prod, t[K - 1], p);
+  }
+  return p;
+}
+
+// SPLIT: blockIdx.y is the slice, out is the workspace (slices, N).  Otherwise out (N) takes the values.
+template <int K, bool SPLIT>
+__global__ __launch_bounds__(kHviThreads) void hvi_boxes_kernel(const double* __restrict__ y, int64_t ld, int64_t N,
+                                                                const double* __restrict__ coords, int C,
+                                                                const uint32_t* __restrict__ boxes, int B,
+                                                                double* __restrict__ out) {
+  extern __shared__ double hvi_grid[];
+  for (int i = threadIdx.x; i < K * C; i += kHviThreads) hvi_grid[i] = coords[i];
+  __syncthreads();
+  const int S = (B + kHviSlice - 1) / kHviSlice;
+  for (int64_t i = (int64_t)blockIdx.x * kHviThreads + threadIdx.x; i < N; i += (int64_t)gridDim.x * kHviThreads) {
+    double yv[K];
+    bool nan = false;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      yv[j] = y[j * ld + i];
+      nan |= yv[j] != yv[j];
+    }
+    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    if constexpr (SPLIT) {
+      const int s = blockIdx.y;
+      const double p = hvi_slice<K>(yv, hvi_grid, C, boxes, s * kHviSlice, min(B, (s + 1) * kHviSlice));
+      out[(int64_t)s * N + i] = nan ? qnan : p;
+    } else {
+      double total = 0.0;
+      for (int s = 0; s < S; ++s) {
+        const double p = hvi_slice<K>(yv, hvi_grid, C, boxes, s * kHviSlice, min(B, (s + 1) * kHviSlice));
+        total += nan ? qnan : p;
+      }
+      out[i] = total;
+    }
+  }
+}
+
+// out[i] = Σ_s part[s][i] in slice order, from 0: the additions of the unsplit kernel
+__global__ __launch_bounds__(kHviThreads) void hvi_finish_kernel(const double* __restrict__ part, int S, int64_t N,
+                                                                 double* __restrict__ out) {
+  for (int64_t i = (int64_t)blockIdx.x * kHviThreads + threadIdx.x; i < N; i += (int64_t)gridDim.x * kHviThreads) {
+    double total = 0.0;
+    for (int s = 0; s < S; ++s) total += part[(int64_t)s * N + i];
+    out[i] = total;
+  }
+}
+
+int64_t hvi_ws_doubles(int64_t N, int B) {
+  const int64_t S = ((int64_t)B + kHviSlice - 1) / kHviSlice;
+  const int64_t nb = (N + kHviThreads - 1) / kHviThreads;
+  if (S < 2 || N < 1 || nb >= kHviSplitBlocks || S * N > kHviSplitWs) return 0;
+  return S * N;
+}
+
+hipError_t launch_hvi_boxes(hipStream_t stream, int k, const double* y, int64_t ld, int64_t N, const double* coords,
+                            int C, const uint16_t* boxes, int B, double* out, double* ws) {
+  if (N < 1 || B < 1 || (int64_t)k * C > kMaxLdsDoubles || (reinterpret_cast<uintptr_t>(boxes) & 3))
+    return hipErrorInvalidValue;
+  const bool split = ws != nullptr && hvi_ws_doubles(N, B) > 0;
+  const int S = (B + kHviSlice - 1) / kHviSlice;
+  const size_t shm = sizeof(double) * (size_t)k * C;
+  const int64_t nb = (N + kHviThreads - 1) / kHviThreads;
+  const dim3 g((unsigned)(nb > (1 << 20) ? (1 << 20) : nb), split ? (unsigned)S : 1u), b(kHviThreads);
+  const uint32_t* bw = reinterpret_cast<const uint32_t*>(boxes);
+  switch (k) {
+#define OMB_HVI(KV)                                                                                               \
+  case KV:                                                                                                        \
+    if (split) hipLaunchKernelGGL((hvi_boxes_kernel<KV, true>), g, b, shm, stream, y, ld, N, coords, C, bw, B, ws); \
+    else hipLaunchKernelGGL((hvi_boxes_kernel<KV, false>), g, b, shm, stream, y, ld, N, coords, C, bw, B, out);    \
+    break;
+    OMB_HVI(2) OMB_HVI(3) OMB_HVI(4) OMB_HVI(5) OMB_HVI(6) OMB_HVI(7) OMB_HVI(8)
+#undef OMB_HVI
+    default: return hipErrorInvalidValue;
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !split) return e;
+  hipLaunchKernelGGL(hvi_finish_kernel, dim3(g.x), b, 0, stream, ws, S, N, out);
+  return hipGetLastError();
+}
+
+}  // namespace omb

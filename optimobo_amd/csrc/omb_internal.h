@@ -103,6 +103,14 @@ hipError_t launch_ehvi_boxes_kd(hipStream_t stream, int k, const double* mu, con
 hipError_t launch_ehvi_boxes_wave(hipStream_t stream, int k, const double* mu, const double* var, int64_t ld,
                                   int64_t N, const double* coords, int C, const uint16_t* boxes, int B, double* out);
 
+// Hypervolume improvement of N points over the same box lists (omb_hvi.hip, omb_hvi_boxes): one lane per point, the
+// grid alone in LDS (k·C ≤ kMaxLdsDoubles), boxes 4-byte aligned.  ws: hvi_ws_doubles(N, B) device doubles — the
+// slices' sums where a small batch is split over the box list's slices, 0 otherwise; null runs unsplit.  Bitwise
+// the same values either way.
+int64_t hvi_ws_doubles(int64_t N, int B);
+hipError_t launch_hvi_boxes(hipStream_t stream, int k, const double* y, int64_t ld, int64_t N, const double* coords,
+                            int C, const uint16_t* boxes, int B, double* out, double* ws);
+
 hipError_t launch_hvpoi(hipStream_t stream, const double* mu, const double* var, int64_t ld, int64_t N,
                         const double* cells, int C, double* out);
 

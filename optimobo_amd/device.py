@@ -202,6 +202,34 @@ class AcqContext:
                                           coords.shape[1], _ptr(boxes), boxes.shape[0], _ptr(out)), fn)
         return out
 
+    def hvi_boxes(self, y, coords, boxes, out=None):
+        """omb_hvi_boxes: the hypervolume improvement Σ_b Π_j (hi_bj − max(y_j, lo_bj))⁺ of the N points y (k, N)
+        (objective-major, unit column stride) over a box decomposition (optimobo_amd.pareto.box_decomposition)
+        → (N,).  A point's value is bitwise the same wherever it stands in whatever batch."""
+        if not isinstance(y, torch.Tensor) or y.dim() != 2 or y.dtype != torch.float64 or y.device != self.device \
+                or (y.shape[1] > 1 and y.stride(1) != 1):
+            raise ValueError(f"hvi_boxes: y must be a (k, N) fp64 tensor on {self.device} with unit column stride")
+        k, N = y.shape
+        coords = _dev_f64(coords, self.device)
+        if coords.dim() != 2 or coords.shape[0] != k:
+            raise ValueError(f"hvi_boxes: grid {tuple(coords.shape)} for k={k} objectives")
+        if not isinstance(boxes, torch.Tensor):
+            b = np.ascontiguousarray(boxes, dtype=np.uint16)
+            boxes = torch.as_tensor(b.view(np.int16), device=self.device)
+        # a device list is read as it is: (B, 2k) 16-bit indices, or the kernel would walk past its end
+        if boxes.dim() != 2 or boxes.shape[1] != 2 * k or boxes.element_size() != 2 or boxes.is_floating_point() \
+                or boxes.device != self.device or not boxes.is_contiguous():
+            raise ValueError(f"hvi_boxes: the box list must be a contiguous (B, {2 * k}) 16-bit integer tensor on "
+                             f"{self.device}, got {tuple(boxes.shape)} {boxes.dtype} on {boxes.device}")
+        if out is None:
+            out = torch.empty(N, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or out.device != self.device or out.numel() < N or not out.is_contiguous():
+            raise ValueError(f"hvi_boxes: out must be a contiguous fp64 tensor of at least {N} values on {self.device}")
+        self._stream()
+        self._check(self.lib.omb_hvi_boxes(self._h, k, _ptr(y), y.stride(0) if k > 1 else N, N, _ptr(coords),
+                                           coords.shape[1], _ptr(boxes), boxes.shape[0], _ptr(out)), "omb_hvi_boxes")
+        return out
+
     def hvpoi(self, mu, var, cells, out=None):
         N = mu.shape[1]
         cells = _dev_f64(cells, self.device)

@@ -178,6 +178,11 @@ def _boxes_ranks(F, top, budget, memo):
     return out
 
 
+class BoxBudgetError(ValueError):
+    """box_decomposition: the front needs more than max_boxes boxes (a ValueError, as it always was; callers that
+    fall back on it alone — the drivers' Thompson batches — catch this class)."""
+
+
 def _box_decomposition_kd(pf, ref, max_boxes):
     k = ref.size
     pts = pf[np.all(pf < ref, axis=1)] if pf.size else np.zeros((0, k))
@@ -192,8 +197,8 @@ def _box_decomposition_kd(pf, ref, max_boxes):
     try:
         boxes = _boxes_ranks(ranks, top, int(max_boxes), {})
     except _BoxBudget:
-        raise ValueError(f"box_decomposition: a front of {len(ranks)} points in k={k} objectives needs more than "
-                         f"max_boxes={int(max_boxes)} boxes") from None
+        raise BoxBudgetError(f"box_decomposition: a front of {len(ranks)} points in k={k} objectives needs more "
+                             f"than max_boxes={int(max_boxes)} boxes") from None
     coords = np.stack([np.concatenate((g, np.full(C - len(g), g[-1]))) for g in grids])
     return (np.ascontiguousarray(coords), np.array([len(g) for g in grids], np.int32), np.ascontiguousarray(boxes))
 

@@ -120,6 +120,18 @@ def EHVI_3D(X, models, max_point, PF, cache, mode="reference"):
     return vals, raised
 
 
+def hypervolume_improvement(Y, PF, max_point):
+    """Hypervolume improvement HV(PF ∪ {y}) − HV(PF) of objective vectors over the front PF (2 to 8 objectives),
+    as the box sum Σ_b Π_j (hi_bj − max(y_j, lo_bj))⁺ on the GPU (omb_hvi_boxes).  One y (k,): float;
+    a batch Y (N, k): (N,).  ValueError when a k ≥ 4 front needs more than 2^20 boxes."""
+    from .acquisition import AcquisitionEngine, _ENGINES
+    eng = next(iter(_ENGINES.values()), None) or AcquisitionEngine()
+    Y = np.asarray(Y, np.float64)
+    single = Y.ndim == 1
+    out = eng.hvi(np.atleast_2d(Y), max_point, PF).cpu().numpy()
+    return float(out[0]) if single else out
+
+
 def expected_decomposition(X, models, weights, agg_func, agg_function_min, cache):
     """util_functions.py:285-327.  One x: float; batch: (N,)."""
     Xb, single = _batch(X)
