@@ -131,7 +131,10 @@ const char* omb_last_error(const omb_ctx* ctx);
  * omb_debug_set(ctx, OMB_DEBUG_POSTERIOR_MEAN_KERNEL, m) picks where μ of those masked objectives is computed when
  * n_var ≤ 8 and some n_train > 128: 1 (default) in a small kernel of its own (one wavefront per 16 candidates, no LDS
  * ring, no barriers) launched after the posterior kernel, which then covers the unmasked objectives only; 2 the same
- * kernel launched before it; 0 inside the posterior launch, by its mean-only workgroups.  μ is bit-identical. */
+ * kernel launched before it; 0 inside the posterior launch, by its mean-only workgroups.  μ is bit-identical.
+ * omb_debug_set(ctx, OMB_DEBUG_PATHS_LIBCOS, 1) evaluates the sample paths' features (omb_paths_set, omb_paths_eval)
+ * with the device library's cosine instead of the kernel's own reduction (default 0): the baseline the kernel's
+ * cosine is measured against (tools/paths_timing.py); values agree to the cosines' rounding. */
 enum {
   OMB_DEBUG_SPIN_LIMIT = 1,
   OMB_DEBUG_COV_TABLE = 2,
@@ -144,7 +147,8 @@ enum {
   OMB_DEBUG_SYRK_GLDS = 10,
   OMB_DEBUG_BOXES_KD = 11,
   OMB_DEBUG_POSTERIOR_ALL_VAR = 12,
-  OMB_DEBUG_POSTERIOR_MEAN_KERNEL = 13
+  OMB_DEBUG_POSTERIOR_MEAN_KERNEL = 13,
+  OMB_DEBUG_PATHS_LIBCOS = 14
 };
 int omb_debug_set(omb_ctx* ctx, int what, int64_t value);
 
@@ -408,6 +412,35 @@ int omb_posterior_samples(omb_ctx* ctx, int obj, const double* Xc_dev, int64_t N
  * (first NaN, else the lowest index among minima), every earlier pick reading as +inf
  * (the reference sets y_cand[pick, :] = inf).  N ≤ 2^18.  Y is not modified.  Asynchronous. */
 int omb_thompson_select(omb_ctx* ctx, const double* Y_dev, int B, int64_t N, int64_t* idx_dev);
+
+/* ---------------------------------------------------------------------------------------
+ * Posterior sample paths: draws that are functions (pathwise conditioning, Matheron's rule; Wilson et al. 2020,
+ * "Efficiently sampling functions from Gaussian process posteriors"):
+ *     f_s(x) = φ(x)ᵀ w_s + k(x, X) v_s,   φ_i(x) = sqrt(2σ_f²/m)·cos(ω̃_i·(x/ℓ) + b_i),
+ *     v_s = α − K_y⁻¹(Φ(X) w_s + ε_s),    ε_s = sqrt(σ_n² + 1e-8)·z_s.
+ * S paths at N points cost O(N·(m + n)·S); nothing is N × N, nothing is factorised (no OMB_ENOTPD), and the paths can
+ * be evaluated again anywhere.  omb_set_gp, omb_gp_fit_state and a successful omb_gp_append on an objective drop its
+ * paths (omb_paths_eval then returns OMB_ESTATE); plans and GP states are never touched by either call.
+ * The cosine is accurate (below 2 ulp of 1, absolute) for arguments |ω̃_i·(x/ℓ) + b_i| ≤ 2^20; a caller who draws
+ * frequencies keeps them inside that range over the box of x (optimobo_amd.paths.draw_path_inputs does).
+ * n_var ≤ 64 and n_train ≤ OMB_MAX_TRAIN_DENSE; both kernels.
+ * ------------------------------------------------------------------------------------- */
+/* Install S posterior sample paths of objective obj (1 ≤ S ≤ 16, 1 ≤ m ≤ 65536).  HOST pointers, copied
+ * like a plan's geometry (the call synchronises the stream first):
+ *   omega_host (m, d) frequencies of x/ℓ;  phase_host (m);  w_host (m, S) standard normals;
+ *   z_host (n_train, S) standard normals or NULL (ε = 0);  noise = the σ_n² the state was factorised with.
+ * Device: U = Φ(X)·w·sqrt(2σ_f²/m) + sqrt(noise + 1e-8)·z;  V = α − L⁻ᵀ(L⁻¹U)  (dense L⁻¹, existing GEMMs).
+ * Refusals, in this order: OMB_EINVAL for obj, S or m outside its range, a null omega / phase / w, noise negative or
+ * not finite; OMB_ESTATE for an objective that is not set; OMB_EUNSUP for n_var > 64 or n_train >
+ * OMB_MAX_TRAIN_DENSE.  A failed call leaves the objective without paths. */
+int omb_paths_set(omb_ctx* ctx, int obj, int S, int m, const double* omega_host, const double* phase_host,
+                  const double* w_host, const double* z_host, double noise);
+/* out_dev[(o·S + s)·ld + i] = f_{o,s}(Xc_i), objectives 0..n_obj-1 (all with the same S), Xc_dev (N, d), ld ≥ N.
+ * Asynchronous.  N = 0 is OMB_OK and writes nothing.  A value is a function of the point and the installed state
+ * alone: bitwise the same whatever N and the point's position in Xc.
+ * Refusals, in this order: OMB_EINVAL for n_obj outside [1, OMB_MAX_OBJ], N < 0, ld < N, a null pointer with N > 0;
+ * OMB_ESTATE for an objective that is not set, has no paths or another S than objective 0; OMB_EUNSUP as above. */
+int omb_paths_eval(omb_ctx* ctx, int n_obj, const double* Xc_dev, int64_t N, int64_t ld, double* out_dev);
 
 /* ---------------------------------------------------------------------------------------
  * ParEGO / KEEP evolutionary acquisition search (parego.py:223-271, keep.py:240-292): the

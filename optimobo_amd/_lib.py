@@ -32,6 +32,7 @@ DEBUG_SYRK_GLDS = 10
 DEBUG_BOXES_KD = 11
 DEBUG_POSTERIOR_ALL_VAR = 12
 DEBUG_POSTERIOR_MEAN_KERNEL = 13
+DEBUG_PATHS_LIBCOS = 14
 MAX_OBJ, MAX_DIM, MAX_TRAIN, MAX_TRAIN_DENSE = 8, 256, 1024, 16384
 
 _p = ctypes.c_void_p
@@ -92,6 +93,9 @@ SIGNATURES = {
     "omb_cholesky": (_i, [_p, _p, _i64, _i64, _d, ctypes.POINTER(_i)]),
     "omb_posterior_samples": (_i, [_p, _i, _p, _i64, _p, _i, _d, _i, _p, _dp]),
     "omb_thompson_select": (_i, [_p, _p, _i, _i64, _p]),
+    # posterior sample paths (host pointers for the draws)
+    "omb_paths_set": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _d]),
+    "omb_paths_eval": (_i, [_p, _i, _p, _i64, _i64, _p]),
     "omb_ea_search": (_i, [_p, _i, _d, _d, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     # GP fit on the device
     "omb_gp_lml_grad": (_i, [_p, _i, _i, _i, _p, _p, _dp, _d, _d, _dp, _dp, _dp]),

@@ -15,6 +15,7 @@ from . import pareto
 from ._lib import OMB_ENOTPD, OMBError
 from .device import AcqContext
 from .gp import GPState
+from .paths import draw_path_inputs, feature_lengthscale
 from .parallel import global_argmax, shard_range, world
 
 
@@ -37,6 +38,7 @@ class AcquisitionEngine:
         self._resident = {}
         self._stale = set()     # objectives whose device state was conditioned on top of _resident[o]
         self.condition_jitter = 0.0
+        self.paths_floored = 0
         self.n_obj = 0
 
     # ------------------------------------------------------------------ model state
@@ -130,8 +132,43 @@ class AcquisitionEngine:
         Yd = Y if isinstance(Y, torch.Tensor) else self._dev(np.atleast_2d(Y))
         return self.ctx.hvi_boxes(Yd.to(device=self.device, dtype=torch.float64).T.contiguous(), coords, boxes)
 
+    def sample_paths(self, S, n_features=1024, seed=0, noise=None, lower=None, upper=None):
+        """Install S posterior sample paths (1 ≤ S ≤ 16) on every loaded model: draws that are functions
+        (pathwise conditioning on ``n_features`` random Fourier features, AcqContext.paths_set), to be evaluated
+        anywhere, any number of times, with ``path_values`` until the models change.  One
+        ``paths.draw_path_inputs`` + ``paths_set`` per model in model order, all draws from one
+        ``numpy.random.default_rng(seed)``.  ``noise``: the σ_n² of the states' factorisation (default: each loaded
+        state's own, plus the device fit's jitter where it added one).  With the box ``lower`` / ``upper`` the
+        frequencies are kept inside the device cosine's argument range over it; a lengthscale below
+        ``paths.feature_lengthscale``'s floor (a degenerate fit) is raised to it for the features alone, and
+        ``paths_floored`` counts the (model, dimension) pairs that happened to."""
+        if self.n_obj < 1:
+            raise RuntimeError("sample_paths: no models loaded (call load_models first)")
+        rng = np.random.default_rng(seed)
+        self.paths_floored = 0      # (model, dimension) pairs whose lengthscale was below the features' floor
+        for o in range(self.n_obj):
+            st = self._resident[o]
+            info = self.ctx.gp_info[o]
+            ls = np.broadcast_to(np.asarray(st.lengthscale, np.float64), (info["d"],))
+            ls_f = ls if lower is None or upper is None else feature_lengthscale(ls, lower, upper)
+            omega, phase, w, z = draw_path_inputs(st.kernel, info["n"], info["d"], int(S), int(n_features), rng,
+                                                  lower=lower, upper=upper, lengthscale=ls_f)
+            if np.any(ls_f != ls):      # the device scales x by the fitted ℓ: ω̃·(ℓ/ℓ_f)·(x/ℓ) = ω̃·(x/ℓ_f)
+                omega = omega * (ls / ls_f)
+                self.paths_floored += int(np.sum(ls_f != ls))
+            nz = noise if noise is not None else \
+                float(getattr(st, "noise", 0.0)) + float(getattr(st, "jitter", None) or 0.0)
+            self.ctx.paths_set(o, omega, phase, w, z, noise=nz)
+        return self
+
+    def path_values(self, Xc):
+        """The installed sample paths at Xc (N, d) → device tensor (n_obj, S, N)."""
+        Xc = Xc if isinstance(Xc, torch.Tensor) else self._dev(np.atleast_2d(Xc))
+        return self.ctx.paths_eval(Xc, self.n_obj)
+
     def thompson_batch(self, q, lower, upper, PF=None, max_point=None, n_candidates=None, seed=0,
-                       max_boxes=1 << 20):
+                       max_boxes=1 << 20, sampler="joint", n_features=1024, refine_rounds=0, shrink=0.1,
+                       n_refine=4096):
         """A batch of q proposals by Thompson sampling over the loaded models → (X (q, d), info).
 
         The candidates are the first ``n_candidates`` points of the device Sobol' sequence seeded by ``seed``
@@ -151,13 +188,30 @@ class AcquisitionEngine:
         ``values`` (q,) the HVI (or drawn value) of each pick under its draw, ``jitter`` per model, ``zero_draws``
         the number of draws with HVI ≡ 0 (0 with one model), ``n_candidates``.  OMBError (OMB_ENOTPD) when a
         covariance cannot be factorised within the ladder; ValueError when the front needs more than max_boxes
-        boxes.  The installed plan and the loaded states are left as they are."""
+        boxes.  The installed plan and the loaded states are left as they are.
+
+        ``sampler="paths"`` draws functions instead (``sample_paths(q)``, q ≤ 16, ``n_features`` features per model,
+        the draws of ``numpy.random.default_rng(seed)``): nothing is factorised, so OMB_ENOTPD cannot arise, and
+        the candidate set defaults to 2^16 points.  Nomination is the same.  With ``refine_rounds`` > 0 every draw
+        whose HVI is not ≡ 0 is then evaluated again at ``n_refine`` Sobol' points of the box ``shrink``^round times
+        the bounds' size around its nominee (clipped to the bounds), and the nominee moves where its HVI under that
+        draw (one model: its drawn value) strictly improves.  ``info`` gains ``sampler``, ``n_features``,
+        ``refined``, the number of draws each round moved, and ``floored`` (``sample_paths``' ``paths_floored``);
+        ``jitter`` is 0 per model; ``indices`` are round 0's."""
         lower = np.asarray(lower, np.float64).reshape(-1)
         upper = np.asarray(upper, np.float64).reshape(-1)
         d, k, q = lower.size, self.n_obj, int(q)
         if k < 1:
             raise RuntimeError("thompson_batch: no models loaded (call load_models first)")
-        n_c = min(100 * d, 5000) if n_candidates is None else int(n_candidates)
+        if sampler not in ("joint", "paths"):
+            raise ValueError(f"thompson_batch: sampler must be 'joint' or 'paths', not {sampler!r}")
+        paths = sampler == "paths"
+        if paths and q > 16:
+            raise ValueError(f"thompson_batch: sampler='paths' draws at most 16 paths per call (q={q})")
+        if paths:
+            n_c = 1 << 16 if n_candidates is None else int(n_candidates)
+        else:
+            n_c = min(100 * d, 5000) if n_candidates is None else int(n_candidates)
         n_c = min(n_c, 1 << 18)
         if not 1 <= q <= n_c:
             raise ValueError(f"thompson_batch: q={q} outside [1, {n_c}] candidates")
@@ -171,13 +225,18 @@ class AcquisitionEngine:
             geo = (coords, boxes)
         self.ctx.set_sobol(d, lower, upper, seed=seed)
         Xc = self.ctx.sobol(0, n_c)
-        rng = np.random.default_rng(seed)
-        draws = torch.empty((k, q, n_c), dtype=torch.float64, device=self.device)
-        jitter = []
-        for o in range(k):
-            Z = self._dev(rng.standard_normal((q, n_c)))
-            _, j = self.ctx.posterior_samples(o, Xc, Z, out=draws[o])
-            jitter.append(j)
+        if paths:
+            self.sample_paths(q, n_features=n_features, seed=seed, lower=lower, upper=upper)
+            draws = self.ctx.paths_eval(Xc, k)
+            jitter = [0.0] * k
+        else:
+            rng = np.random.default_rng(seed)
+            draws = torch.empty((k, q, n_c), dtype=torch.float64, device=self.device)
+            jitter = []
+            for o in range(k):
+                Z = self._dev(rng.standard_normal((q, n_c)))
+                _, j = self.ctx.posterior_samples(o, Xc, Z, out=draws[o])
+                jitter.append(j)
         zero = 0
         if k == 1:
             score = draws[0]
@@ -190,7 +249,30 @@ class AcquisitionEngine:
             zero = int((h.max(dim=1).values <= 0).sum().item())
         idx = idx.cpu().numpy()
         X = Xc[torch.as_tensor(idx, device=self.device)].cpu().numpy()
-        return X, dict(indices=idx, values=values, jitter=jitter, zero_draws=zero, n_candidates=n_c)
+        info = dict(indices=idx, values=values, jitter=jitter, zero_draws=zero, n_candidates=n_c)
+        if not paths:
+            return X, info
+        live = np.ones(q, bool) if k == 1 else (h.max(dim=1).values > 0).cpu().numpy()
+        refined = []
+        for rnd in range(1, int(refine_rounds) + 1):
+            moved = 0
+            half = shrink ** rnd * (upper - lower) / 2
+            for b in np.flatnonzero(live):
+                self.ctx.set_sobol(d, np.maximum(lower, X[b] - half), np.minimum(upper, X[b] + half),
+                                   seed=seed + 104729 * rnd + int(b))
+                Xr = self.ctx.sobol(0, int(n_refine))
+                vals = self.ctx.paths_eval(Xr, k)[:, b, :]
+                # one model: the smallest drawn value; else the largest HVI under draw b
+                score = -vals[0].contiguous() if k == 1 else self.ctx.hvi_boxes(vals, *geo)
+                v, i = self.ctx.argmax(score)
+                v = -v if k == 1 else v
+                if i >= 0 and (v < values[b] if k == 1 else v > values[b]):
+                    X[b] = Xr[int(i)].cpu().numpy()
+                    values[b] = v
+                    moved += 1
+            refined.append(moved)
+        info.update(sampler="paths", n_features=int(n_features), refined=refined, floored=self.paths_floored)
+        return X, info
 
     def ehvi3d(self, Xc, max_point, PF, cache):
         """util_functions.EHVI_3D (Monte-Carlo form) on every row of Xc, for k = n_obj ≥ 3 objectives (the

@@ -27,10 +27,13 @@ class BODriver:
     # batch_strategy values the driver takes: the drivers that ignore batch_size take the default alone
     _batch_strategies = ("believer",)
     thompson_candidates = None   # candidates of a Thompson batch (None: AcquisitionEngine.thompson_batch's default)
+    # thompson_sampler="paths": random Fourier features per model and refinement rounds around every nominee
+    thompson_features = 1024
+    thompson_refine_rounds = 2
 
     def __init__(self, test_problem, ideal_point=None, max_point=None, mode="reference", n_candidates=1 << 14,
                  refine_rounds=2, seed=None, device=None, polish=True, starts=None, noise=0.0, batch_size=1,
-                 constraints=None, batch_strategy="believer"):
+                 constraints=None, batch_strategy="believer", thompson_sampler="joint"):
         self.test_problem = test_problem
         self.max_point = max_point
         self.ideal_point = ideal_point
@@ -70,6 +73,14 @@ class BODriver:
         # surrogates on each pick's posterior mean; "thompson" takes q joint posterior draws over one candidate set
         # and lets every draw nominate its best candidate (AcquisitionEngine.thompson_batch)
         self.batch_strategy = self._check_batch_strategy(batch_strategy)
+        # how a Thompson batch draws (not in the reference): "joint" draws jointly at the candidates (a covariance and
+        # its Cholesky factor, TuRBO's way); "paths" draws posterior sample paths — functions, evaluated at many more
+        # candidates and again around every nominee (AcquisitionEngine.sample_paths)
+        if thompson_sampler not in ("joint", "paths"):
+            raise ValueError(f"thompson_sampler must be 'joint' or 'paths', not {thompson_sampler!r}")
+        if thompson_sampler == "paths" and self.batch_strategy != "thompson":
+            raise ValueError("thompson_sampler='paths' needs batch_strategy='thompson'")
+        self.thompson_sampler = thompson_sampler
         self.thompson_fallbacks = 0    # Thompson iterations that fell back to the believer batch
         self._iteration = 0
 
@@ -186,11 +197,14 @@ class BODriver:
         call — a batch larger than the candidate set, say — is the caller's and is raised."""
         seed = (self.seed if self.seed is not None else np.random.randint(0, 2 ** 31 - 1)) + 7919 * self._iteration
         self._iteration += 1
+        kw = {}
+        if self.thompson_sampler == "paths":
+            kw = dict(sampler="paths", n_features=self.thompson_features, refine_rounds=self.thompson_refine_rounds)
         try:
             X, _ = eng.thompson_batch(b, self.test_problem.xl, self.test_problem.xu, PF=PF,
                                       max_point=self.max_point if PF is not None else None,
                                       n_candidates=self.thompson_candidates, seed=seed,
-                                      max_boxes=getattr(self, "exact_max_boxes", 1 << 20))
+                                      max_boxes=getattr(self, "exact_max_boxes", 1 << 20), **kw)
         except (OMBError, pareto.BoxBudgetError) as e:
             if isinstance(e, OMBError) and e.code != OMB_ENOTPD:
                 raise

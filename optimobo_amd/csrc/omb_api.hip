@@ -23,6 +23,14 @@ struct ObjState {
   const double* Xraw = nullptr;  // unscaled inputs (n, d) and the host ℓ: what omb_gp_append packs the grown state from
   double ls[OMB_MAX_DIM] = {};
   GPDev dev{};
+  // posterior sample paths over this state (omb_paths_set): path_S = 0 when none are installed.  One allocation:
+  // Of | Wf | Vf | z | F | U | T | G (the last five: omb_paths_set's workspace, sized for 16 paths)
+  int path_S = 0, path_MT = 0;
+  double* pbuf = nullptr;
+  size_t pcap = 0;       // bytes
+  const double* path_Of = nullptr;
+  const double* path_Wf = nullptr;
+  const double* path_Vf = nullptr;
 };
 
 // Acquisition of the fused chain (omb_plan_*), with its geometry resident in ctx->geo.
@@ -118,6 +126,7 @@ struct omb_ctx {
   int chol_single = 0;           // OMB_DEBUG_CHOL_MODE (value & 8): every trailing update its own task
   bool select_seq = false;       // OMB_DEBUG_SELECT_SEQ: the sequential greedy walk for B ≤ 64 too
   bool boxes_kd_wave = false;    // OMB_DEBUG_BOXES_KD: omb_ehvi_boxes_k by one wavefront per candidate where that fits
+  bool paths_libcos = false;     // OMB_DEBUG_PATHS_LIBCOS: the sample paths' features through the library cosine
   bool posterior_all_var = false;  // OMB_DEBUG_POSTERIOR_ALL_VAR: the chain computes σ² of every objective
   int posterior_mean_kernel = kMeanKernelAfter;   // OMB_DEBUG_POSTERIOR_MEAN_KERNEL: masked objectives' μ in a launch of its own
 };
@@ -434,8 +443,10 @@ int omb_destroy(omb_ctx* ctx) {
   if (!ctx) return OMB_OK;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  for (auto& s : ctx->obj)
+  for (auto& s : ctx->obj) {
     if (s.buf) (void)hipFree(s.buf);
+    if (s.pbuf) (void)hipFree(s.pbuf);
+  }
   if (ctx->partials) (void)hipFree(ctx->partials);
   if (ctx->result_dev) (void)hipFree(ctx->result_dev);
   if (ctx->result_host) (void)hipHostFree(ctx->result_host);
@@ -522,6 +533,10 @@ int omb_debug_set(omb_ctx* ctx, int what, int64_t value) {
     ctx->boxes_kd_wave = value != 0;
     return OMB_OK;
   }
+  if (what == OMB_DEBUG_PATHS_LIBCOS) {
+    ctx->paths_libcos = value != 0;
+    return OMB_OK;
+  }
   if (what == OMB_DEBUG_POSTERIOR_ALL_VAR) {
     ctx->posterior_all_var = value != 0;
     return OMB_OK;
@@ -569,6 +584,7 @@ static hipError_t install_gp(omb_ctx* ctx, ObjState& s, double* buf, int kernel,
   const int Q = (R + 3) / 4;
   const int n_pad = kChunkRows * Q;
   const int R_pack = (n <= OMB_MAX_TRAIN) ? R : 0;
+  s.path_S = 0;   // sample paths over the previous state are a silent wrong answer over this one
   double* Xs = buf;
   double* xsq = Xs + (size_t)n_pad * DP;
   double* alpha_p = xsq + n_pad;
@@ -1711,6 +1727,92 @@ int omb_gp_fit_state(omb_ctx* ctx, int obj, int kernel, int n, int d, const doub
   if ((rc = gp_factor(ctx, kernel, n, d, X_dev, y_dev, lengthscale_host, variance, noise, &f))) return rc;
   if (jitter_used) *jitter_used = f.jitter;
   return omb_set_gp(ctx, obj, kernel, n, d, X_dev, lengthscale_host, variance, f.alpha, f.Linv);
+}
+
+// ---------------------------------------------------------------------------------------
+// Posterior sample paths (omb_paths.hip): pathwise conditioning over the installed state.
+static PathsObjInfo paths_info(const ObjState& s) { return PathsObjInfo{s.set ? 1 : 0, s.d, s.n, s.path_S}; }
+
+int omb_paths_set(omb_ctx* ctx, int obj, int S, int m, const double* omega_host, const double* phase_host,
+                  const double* w_host, const double* z_host, double noise) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  PathsObjInfo info{};
+  if (obj >= 0 && obj < OMB_MAX_OBJ) {
+    ctx->obj[obj].path_S = 0;   // a failed call leaves the objective without paths
+    info = paths_info(ctx->obj[obj]);
+  }
+  if ((rc = check_paths_set(E(ctx), obj, S, m, omega_host, phase_host, w_host, noise, &info))) return rc;
+  ObjState& s = ctx->obj[obj];
+  const int n = s.n, d = s.d, DP = s.DP;
+  const size_t nOf = (size_t)paths_of_doubles(m, DP), nWf = (size_t)paths_wf_doubles(m);
+  const size_t nVf = (size_t)paths_vf_doubles(s.R), nS = (size_t)n * kPathsMaxS;
+  const size_t bytes = sizeof(double) * (nOf + nWf + nVf + 5 * nS);
+  void* host = nullptr;
+  // synchronises the stream: queued evaluations may still read the previous paths
+  if ((rc = stage_begin(ctx, sizeof(double) * (nOf + nWf + (size_t)n * S), &host))) return rc;
+  if (bytes > s.pcap) {
+    if (s.pbuf) (void)hipFree(s.pbuf);
+    s.pbuf = nullptr;
+    s.pcap = 0;
+    if (hipMalloc(&s.pbuf, bytes) != hipSuccess)
+      return fail(ctx, OMB_ENOMEM, "hipMalloc(%zu) for the paths of objective %d", bytes, obj);
+    s.pcap = bytes;
+  }
+  double* Of = s.pbuf;
+  double* Wf = Of + nOf;
+  double* Vf = Wf + nWf;
+  double* zd = Vf + nVf;
+  double* F = zd + nS;
+  double* U = F + nS;
+  double* T = U + nS;
+  double* G = T + nS;
+  double* hs = static_cast<double*>(host);
+  paths_pack(m, d, DP, S, omega_host, phase_host, w_host, sqrt(2.0 * s.variance / m), hs, hs + nOf);
+  if (z_host) memcpy(hs + nOf + nWf, z_host, sizeof(double) * (size_t)n * S);
+  hipStream_t st = ctx->stream;
+  OMB_HIP(ctx, hipMemcpyAsync(Of, hs, sizeof(double) * (nOf + nWf), hipMemcpyHostToDevice, st));
+  if (z_host)
+    OMB_HIP(ctx, hipMemcpyAsync(zd, hs + nOf + nWf, sizeof(double) * (size_t)n * S, hipMemcpyHostToDevice, st));
+  // the prior paths at the training inputs (the evaluation kernel without its update term), then
+  // U = Φ(X)·w·sqrt(2σ_f²/m) + sqrt(noise + 1e-8)·z and V = α − L⁻ᵀ(L⁻¹U)
+  PathArgs pa{};
+  pa.o[0] = PathObj{s.dev, Of, Wf, Vf, (m + 15) / 16, 0, S, 0};
+  pa.d = d;
+  pa.DP = DP;
+  OMB_HIP(ctx, launch_paths_eval(st, pa, 1, s.kind, ctx->paths_libcos, s.Xraw, n, n, F));
+  OMB_HIP(ctx, launch_paths_u(st, F, z_host ? zd : nullptr, sqrt(noise + 1e-8), n, S, U));
+  OMB_HIP(ctx, launch_gemm_ltri_nn(st, n, S, 1.0, s.Ld, n, U, S, 0.0, T, S));
+  OMB_HIP(ctx, launch_gemm_tn(st, n, S, n, 1.0, s.Ld, n, T, S, 0.0, G, S));
+  OMB_HIP(ctx, launch_paths_pack_v(st, s.dev.alpha, G, n, S, s.R, Vf));
+  s.path_S = S;
+  s.path_MT = (m + 15) / 16;
+  s.path_Of = Of;
+  s.path_Wf = Wf;
+  s.path_Vf = Vf;
+  return OMB_OK;
+}
+
+int omb_paths_eval(omb_ctx* ctx, int n_obj, const double* Xc_dev, int64_t N, int64_t ld, double* out_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  PathsObjInfo info[OMB_MAX_OBJ];
+  for (int o = 0; o < OMB_MAX_OBJ; ++o) info[o] = paths_info(ctx->obj[o]);
+  if ((rc = check_paths_eval(E(ctx), n_obj, Xc_dev, N, ld, out_dev, info))) return rc;
+  PathArgs pa{};
+  for (int o = 0; o < n_obj; ++o) {
+    const ObjState& s = ctx->obj[o];
+    if (s.d != ctx->obj[0].d) return fail(ctx, OMB_EINVAL, "objectives disagree on n_var (%d vs %d)", s.d, ctx->obj[0].d);
+    if (s.kind != ctx->obj[0].kind) return fail(ctx, OMB_EINVAL, "objectives disagree on kernel kind");
+    pa.o[o] = PathObj{s.dev, s.path_Of, s.path_Wf, s.path_Vf, s.path_MT, s.R, s.path_S, 0};
+  }
+  pa.d = ctx->obj[0].d;
+  pa.DP = ctx->obj[0].DP;
+  if (N == 0) return OMB_OK;
+  if ((N + 63) / 64 > 0x7fffffffLL) return fail(ctx, OMB_EUNSUP, "N=%lld too large", (long long)N);
+  hipError_t e = launch_paths_eval(ctx->stream, pa, n_obj, ctx->obj[0].kind, ctx->paths_libcos, Xc_dev, N, ld, out_dev);
+  if (e != hipSuccess) return hip_fail(ctx, e, "paths_eval");
+  return OMB_OK;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -117,6 +117,67 @@ int check_ei(std::string* err, int kind, int k, double var_eps, double pof_eps) 
 
 static bool finite_nonneg(double v) { return v >= 0.0 && v <= 1.79769313486231570815e308; }
 
+static int check_paths_shape(std::string* err, int o, const PathsObjInfo& s) {
+  if (s.n_var > kPathsMaxDim)
+    return errf(err, OMB_EUNSUP, "objective %d: sample paths need n_var <= %d (n_var=%d)", o, kPathsMaxDim, s.n_var);
+  if (s.n_train > OMB_MAX_TRAIN_DENSE)
+    return errf(err, OMB_EUNSUP, "objective %d: n_train=%d above %d", o, s.n_train, OMB_MAX_TRAIN_DENSE);
+  return OMB_OK;
+}
+
+int check_paths_set(std::string* err, int obj, int S, int m, const void* omega, const void* phase, const void* w,
+                    double noise, const PathsObjInfo* info) {
+  if (obj < 0 || obj >= OMB_MAX_OBJ) return errf(err, OMB_EINVAL, "obj=%d outside [0, %d)", obj, OMB_MAX_OBJ);
+  if (S < 1 || S > kPathsMaxS) return errf(err, OMB_EINVAL, "S=%d paths outside [1, %d]", S, kPathsMaxS);
+  if (m < 1 || m > kPathsMaxFeatures)
+    return errf(err, OMB_EINVAL, "m=%d features outside [1, %d]", m, kPathsMaxFeatures);
+  if (!omega || !phase || !w || !info) return errf(err, OMB_EINVAL, "null frequencies, phases or weights");
+  if (!finite_nonneg(noise)) return errf(err, OMB_EINVAL, "noise=%g must be finite and >= 0", noise);
+  if (!info->set) return errf(err, OMB_ESTATE, "objective %d has no GP state (call omb_set_gp)", obj);
+  return check_paths_shape(err, obj, *info);
+}
+
+int check_paths_eval(std::string* err, int n_obj, const void* Xc, int64_t N, int64_t ld, const void* out,
+                     const PathsObjInfo* info) {
+  if (n_obj < 1 || n_obj > OMB_MAX_OBJ) return errf(err, OMB_EINVAL, "n_obj=%d outside [1, %d]", n_obj, OMB_MAX_OBJ);
+  if (N < 0) return errf(err, OMB_EINVAL, "N=%lld < 0", (long long)N);
+  if (ld < N) return errf(err, OMB_EINVAL, "ld=%lld < N=%lld", (long long)ld, (long long)N);
+  if (!info || (N > 0 && (!Xc || !out))) return errf(err, OMB_EINVAL, "null candidate/output pointer");
+  for (int o = 0; o < n_obj; ++o) {
+    if (!info[o].set) return errf(err, OMB_ESTATE, "objective %d has no GP state (call omb_set_gp)", o);
+    if (info[o].S < 1) return errf(err, OMB_ESTATE, "objective %d has no sample paths (call omb_paths_set)", o);
+    if (info[o].S != info[0].S)
+      return errf(err, OMB_ESTATE, "objectives 0 and %d hold %d and %d paths", o, info[0].S, info[o].S);
+  }
+  for (int o = 0; o < n_obj; ++o) {
+    const int rc = check_paths_shape(err, o, info[o]);
+    if (rc) return rc;
+  }
+  return OMB_OK;
+}
+
+void paths_pack(int m, int d, int DP, int S, const double* omega, const double* phase, const double* w, double scale,
+                double* Of, double* Wf) {
+  const int ksf = paths_ksf(DP);
+  const int64_t MT = (m + 15) / 16;
+  for (int64_t T = 0; T < MT; ++T) {
+    for (int s = 0; s < ksf; ++s)
+      for (int l = 0; l < 64; ++l) {
+        const int64_t i = 16 * T + (l & 15);
+        const int j = 4 * s + (l >> 4);
+        double v = 0.0;
+        if (i < m) v = j < d ? omega[i * d + j] : (j == d ? phase[i] : 0.0);
+        Of[(T * ksf + s) * 64 + l] = v;
+      }
+    for (int e = 0; e < 4; ++e)
+      for (int l = 0; l < 64; ++l) {
+        const int64_t i = 16 * T + 4 * e + (l >> 4);
+        const int p = l & 15;
+        Wf[(4 * T + e) * 64 + l] = (i < m && p < S) ? scale * w[i * S + p] : 0.0;
+      }
+  }
+}
+
 int check_constraints(std::string* err, int plan_k, int n_con, double pof_eps) {
   if (plan_k < 1) return errf(err, OMB_ESTATE, "no acquisition plan to constrain (call an omb_plan_* function first)");
   if (n_con < 0) return errf(err, OMB_EINVAL, "n_con=%d < 0", n_con);

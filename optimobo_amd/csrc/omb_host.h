@@ -68,6 +68,34 @@ int check_eval_grad(std::string* err, const void* Xc, int64_t N, const void* val
 // Candidates per pass of the gradient chain: its workspace holds (n_obj + 2)·n_train doubles per candidate (K*, V
 // and one w per objective) and is kept to 512 MiB; at least 64, at most 2^20 and N (0 for an empty or out-of-range request).
 int64_t grad_chunk(int n_obj, int n_train, int64_t N);
+// Posterior sample paths (omb_paths_set / omb_paths_eval, omb_paths.hip).
+constexpr int kPathsMaxS = 16;            // paths per objective: one MFMA accumulator tile
+constexpr int kPathsMaxFeatures = 65536;  // random Fourier features per objective
+constexpr int kPathsMaxDim = 64;          // n_var: the candidates' fragments stay in registers
+// State of one objective as the checks see it: whether a GP is installed, its shape, and the S of its paths (0: none).
+struct PathsObjInfo {
+  int set, n_var, n_train, S;
+};
+// omb_paths_set, in this order: OMB_EINVAL for obj outside [0, OMB_MAX_OBJ), S outside [1, kPathsMaxS], m outside
+// [1, kPathsMaxFeatures], a null omega / phase / w or a negative or non-finite noise; OMB_ESTATE for an objective
+// without a GP; OMB_EUNSUP for n_var > kPathsMaxDim or n_train > OMB_MAX_TRAIN_DENSE.
+int check_paths_set(std::string* err, int obj, int S, int m, const void* omega, const void* phase, const void* w,
+                    double noise, const PathsObjInfo* info);
+// omb_paths_eval over info[0..n_obj-1] (info: OMB_MAX_OBJ entries), in this order: OMB_EINVAL for n_obj outside
+// [1, OMB_MAX_OBJ], N < 0, ld < N or (N > 0) a null Xc / out; OMB_ESTATE for an objective without a GP or without
+// paths, or with another S than objective 0; OMB_EUNSUP for n_var > kPathsMaxDim or n_train > OMB_MAX_TRAIN_DENSE.
+int check_paths_eval(std::string* err, int n_obj, const void* Xc, int64_t N, int64_t ld, const void* out,
+                     const PathsObjInfo* info);
+// The paths' operands in the A-fragment order of v_mfma_f64_16x16x4_f64 (lane l holds A[l & 15][l >> 4]), zero
+// padded to whole tiles of 16 features and to 16 paths:
+//   Of[(T·ksf + s)·64 + l] = [ω̃_i, b_i, 0 …][4s + (l >> 4)] of feature i = 16T + (l & 15)   (ksf = paths_ksf(DP))
+//   Wf[(4T + e)·64 + l]    = scale · w[16T + 4e + (l >> 4)][l & 15]
+inline int paths_ksf(int DP) { return (DP + 4) / 4; }
+inline int64_t paths_of_doubles(int m, int DP) { return (int64_t)((m + 15) / 16) * paths_ksf(DP) * 64; }
+inline int64_t paths_wf_doubles(int m) { return (int64_t)((m + 15) / 16) * 256; }
+inline int64_t paths_vf_doubles(int R) { return (int64_t)R * 256; }
+void paths_pack(int m, int d, int DP, int S, const double* omega, const double* phase, const double* w, double scale,
+                double* Of, double* Wf);
 // Validates an expected_decomposition request and fills its ScalParams.
 int build_scal(std::string* err, int k, int M, int scal_id, const double* params_host, const double* weights_host,
                const double* ideal_host, const double* max_host, double agg_min, ScalParams* out);

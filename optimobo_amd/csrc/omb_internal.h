@@ -345,6 +345,32 @@ hipError_t launch_append_restride(hipStream_t stream, const AppendWs& ws, int n,
 hipError_t launch_append_point(hipStream_t stream, const AppendWs& ws, int kind, double variance, int c, int j,
                                const double* ynew, double noise, double* mu_out, double* var_out);
 
+// ---------------------------------------------------------------------------------------
+// Posterior sample paths (omb_paths.hip): omb_paths_set, omb_paths_eval.
+struct PathObj {
+  GPDev g;
+  const double* Of;   // [ω̃, b] of the features, A-fragment order (omb_host.h paths_pack)
+  const double* Wf;   // sqrt(2σ_f²/m)·w, A-fragment order, zero padded to 16 paths
+  const double* Vf;   // v = α − L⁻ᵀL⁻¹U, A-fragment order, zero padded (launch_paths_pack_v)
+  int MT;             // feature tiles ⌈m/16⌉
+  int R;              // training-row tiles of the update term (0: the prior paths alone)
+  int S;              // paths
+  int pad_;
+};
+struct PathArgs {
+  PathObj o[OMB_MAX_OBJ];
+  int d, DP;
+};
+// out[(o·S + s)·ld + i] = path s of objective o at Xc_i (N > 0, DP ≤ kMaxFusedDP); libcos: the library cosine
+// in place of the kernel's own (OMB_DEBUG_PATHS_LIBCOS, the baseline it is measured against)
+hipError_t launch_paths_eval(hipStream_t stream, const PathArgs& pa, int n_obj, int kind, bool libcos,
+                             const double* Xc, int64_t N, int64_t ld, double* out);
+// U (n, S) = Fᵀ + sd·z, F (S rows of pitch n), z (n, S) or null
+hipError_t launch_paths_u(hipStream_t stream, const double* F, const double* z, double sd, int n, int S, double* U);
+// Vf (paths_vf_doubles(R)) from α (n) and G = L⁻ᵀL⁻¹U (n, S)
+hipError_t launch_paths_pack_v(hipStream_t stream, const double* alpha, const double* G, int n, int S, int R,
+                               double* Vf);
+
 // Packed-L^-1 size in doubles for R row tiles: Σ_{r<R} 4(r+1)·64 = 128·R·(R+1).
 inline int64_t packed_L_size(int R) { return 128ll * R * (R + 1); }
 // k-step pairs of the training-row A fragments [x/ℓ, ‖x/ℓ‖², 1]: ⌈⌈(DP+2)/4⌉/2⌉

@@ -1,0 +1,229 @@
+// Posterior sample paths on gfx950 (omb_paths_set / omb_paths_eval): pathwise conditioning with random Fourier
+// features (Wilson et al. 2020, "Efficiently sampling functions from Gaussian process posteriors"),
+//     f_s(x) = Σ_i w_is·sqrt(2σ_f²/m)·cos(ω̃_i·(x/ℓ) + b_i)  +  Σ_j k(x, X_j)·v_js.
+// A draw is a function: evaluating S ≤ 16 of them at N points is O(N·(m + n)·S), nothing is N × N, nothing is
+// factorised, and the same paths can be evaluated again anywhere.
+//
+// paths_eval_kernel: a wave owns 16 candidates (a workgroup 4 waves, no LDS traffic between them, no barriers after
+// the table staging, no atomics) and one 16 paths × 16 candidates accumulator of v_mfma_f64_16x16x4_f64 (4 VGPR
+// pairs per lane).
+//   * Features, 16 at a time: the arguments ω̃ᵀ(x/ℓ) + b of a 16 × 16 tile are ⌈(d+1)/4⌉ MFMA k-steps of the
+//     augmented dot product [ω̃_i, b_i]·[x/ℓ, 1] (A fragments packed by the host, omb_host.cpp paths_pack).  The
+//     accumulator's register e holds rows 4e + (lane>>4) — exactly the B fragment of k-step e — so after the cosine
+//     the four values feed acc += Wᵀ-fragment · cos-tile straight from registers.
+//   * Update term, 16 training rows at a time: r² from the training rows' fragments as in kernel_block_mfma_kernel,
+//     the same table-driven Matern / RBF transform, then acc += Vᵀ-fragment · K*-tile.
+// W and V are stored in A-fragment order, zero padded to 16 paths and whole tiles: padded features and rows meet
+// zeros.  A column of the B operand only ever meets its own column of the accumulator and the tile order is fixed
+// (features, then training rows), so a path's value at a point is bitwise the same whatever N, the point's column
+// and the grid.
+#include "omb_internal.h"
+#include "omb_math.h"
+
+namespace omb {
+
+typedef double d4 __attribute__((ext_vector_type(4)));
+typedef double d2 __attribute__((ext_vector_type(2)));
+
+// cos(t) for |t| ≤ 2^20 (kPathsMaxArg): Cody–Waite reduction by π/2 in three constants, then fdlibm's minimax
+// polynomials of sin and cos on [−π/4, π/4].  The first constant keeps 33 bits, so n·P1 is exact for the
+// n < 2^20 of the range and the first fma is exact; the other two fmas round once each (≤ 2^-54 absolute each).
+// The absolute error is below 2 ulp of 1.  Outside the range the reduction's n·P1 is no longer exact and the
+// error grows with |t|/2^20 ulp; NaN and ±inf give NaN.
+__device__ __forceinline__ double cos_cw(double t) {
+  const double n = rint(t * 0.6366197723675814);
+  double r = fma(-n, 0x1.921fb54400000p+0, t);
+  r = fma(-n, 0x1.0b4611a626331p-34, r);
+  r = fma(-n, 0x1.1701b839a2520p-88, r);
+  const int q = (int)n;
+  const double z = r * r;
+  double ps = fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
+  double pc = fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
+  ps = fma(ps, z, 2.75573137070700676789e-06);
+  pc = fma(pc, z, -2.75573143513906633035e-07);
+  ps = fma(ps, z, -1.98412698298579493134e-04);
+  pc = fma(pc, z, 2.48015872894767294178e-05);
+  ps = fma(ps, z, 8.33333333332248946124e-03);
+  pc = fma(pc, z, -1.38888888888741095749e-03);
+  ps = fma(ps, z, -1.66666666666666324348e-01);
+  pc = fma(pc, z, 4.16666666666666019037e-02);
+  const double sn = fma(r * z, ps, r);
+  const double hz = 0.5 * z, w = 1.0 - hz;
+  const double cs = w + (((1.0 - w) - hz) + (z * z) * pc);
+  // quadrant 0: cos r, 1: −sin r, 2: −cos r, 3: sin r
+  const double v = (q & 1) ? sn : cs;
+  return (((q + 1) & 2) != 0) ? -v : v;
+}
+
+template <bool LIBCOS>
+__device__ __forceinline__ double path_cos(double t) {
+  if constexpr (LIBCOS)
+    return cos(t);
+  else
+    return cos_cw(t);
+}
+
+template <int DP, int KIND, bool LIBCOS>
+__global__ __launch_bounds__(256) void paths_eval_kernel(PathArgs pa, const double* __restrict__ Xc, int64_t N,
+                                                         int64_t ld, double* __restrict__ out, ExpCoef ec) {
+  constexpr bool kAug = DP <= 8;
+  constexpr int KSD = kAug ? (DP + 5) / 4 : (DP + 3) / 4;
+  constexpr int KSDP = ((DP + 5) / 4 + 1) / 2;   // = packed_X_pairs(DP)
+  constexpr int KSF = (DP + 4) / 4;              // = paths_ksf(DP): k-steps of [x/ℓ, 1]
+  constexpr bool kTab256 = KIND == OMB_KERNEL_MATERN52;
+  __shared__ double etab[kTab256 ? 256 : 64];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if constexpr (kTab256)
+    etab[tid] = kExp2Tab256[tid];   // 256 threads
+  else if (tid < 64)
+    etab[tid] = kExp2Tab64[tid];
+  const int o = blockIdx.y;
+  const PathObj& po = pa.o[o];
+  const GPDev& g = po.g;
+  const int d = pa.d;
+  const int64_t col = (int64_t)blockIdx.x * 64 + 16 * wave + (lane & 15);
+  const int64_t ci = col < N ? col : N - 1;
+  double csq = 0.0;
+#pragma unroll
+  for (int j = 0; j < DP; ++j) {
+    const double c = (j < d) ? Xc[ci * d + j] / g.ls[j] : 0.0;
+    csq = fma(c, c, csq);
+  }
+  double bfr[KSD];   // the r² operand: [−2·x/ℓ, 1, ‖x/ℓ‖²] (n_var ≤ 8) or x/ℓ
+#pragma unroll
+  for (int s = 0; s < KSD; ++s) {
+    const int j = 4 * s + (lane >> 4);
+    const double c = (j < d) ? Xc[ci * d + j] / g.ls[j] : 0.0;
+    if constexpr (kAug)
+      bfr[s] = (j < d) ? -2.0 * c : (j == d ? 1.0 : (j == d + 1 ? csq : 0.0));
+    else
+      bfr[s] = c;
+  }
+  double bff[KSF];   // the feature operand: [x/ℓ, 1]
+#pragma unroll
+  for (int s = 0; s < KSF; ++s) {
+    const int j = 4 * s + (lane >> 4);
+    const double c = (j < d) ? Xc[ci * d + j] / g.ls[j] : 0.0;
+    bff[s] = (j < d) ? c : (j == d ? 1.0 : 0.0);
+  }
+  const double pm[3] = {g.variance, kSqrt5 * g.variance, kFiveThirds * g.variance};
+  __syncthreads();
+  d4 acc = d4{0.0, 0.0, 0.0, 0.0};
+  // features
+  for (int T = 0; T < po.MT; ++T) {
+    const double* fa = po.Of + (int64_t)T * (KSF * 64) + lane;
+    double a[KSF];
+#pragma unroll
+    for (int s = 0; s < KSF; ++s) a[s] = fa[64 * s];
+    const double* wa = po.Wf + (int64_t)T * 256 + lane;
+    double wv[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) wv[e] = wa[64 * e];
+    d4 cr = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < KSF; ++s) cr = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], bff[s], cr, 0, 0, 0);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(wv[e], path_cos<LIBCOS>(cr[e]), acc, 0, 0, 0);
+  }
+  // update term
+  for (int T = 0; T < po.R; ++T) {
+    const d2* xa = reinterpret_cast<const d2*>(g.Xf + (int64_t)T * (KSDP * 128) + 2 * lane);
+    d2 a[(KSD + 1) / 2];
+#pragma unroll
+    for (int p = 0; p < (KSD + 1) / 2; ++p) a[p] = xa[64 * p];
+    const double* va = po.Vf + (int64_t)T * 256 + lane;
+    double vv[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) vv[e] = va[64 * e];
+    d4 cr = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int s = 0; s < KSD; ++s)
+      cr = __builtin_amdgcn_mfma_f64_16x16x4f64((s & 1) ? a[s >> 1].y : a[s >> 1].x, bfr[s], cr, 0, 0, 0);
+#pragma unroll
+    for (int e = 0; e < 4; e += 2) {
+      const int k0 = 16 * T + 4 * e + (lane >> 4), k1 = k0 + 4;
+      const double r2a = kAug ? cr[e] : fma(-2.0, cr[e], g.xsq[k0] + csq);
+      const double r2b = kAug ? cr[e + 1] : fma(-2.0, cr[e + 1], g.xsq[k1] + csq);
+      double v0, v1;
+      if constexpr (kTab256)
+        matern_r2_tab256_x2(r2a, r2b, pm, ec, etab, v0, v1);
+      else
+        kernel_of_r2_tab_x2<KIND>(r2a, r2b, pm, ec, etab, v0, v1);
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(vv[e], v0, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(vv[e + 1], v1, acc, 0, 0, 0);
+    }
+  }
+  if (col < N) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int s = 4 * e + (lane >> 4);
+      if (s < po.S) out[((int64_t)o * po.S + s) * ld + col] = acc[e];
+    }
+  }
+}
+
+template <int KIND, bool LIBCOS>
+static hipError_t launch_paths_kind(hipStream_t stream, const PathArgs& pa, int n_obj, const double* Xc, int64_t N,
+                                    int64_t ld, double* out) {
+  const dim3 grid((unsigned)((N + 63) / 64), (unsigned)n_obj);
+  switch (pa.DP) {
+#define OMB_PATHS(DPV)                                                                                          \
+  case DPV:                                                                                                     \
+    hipLaunchKernelGGL((paths_eval_kernel<DPV, KIND, LIBCOS>), grid, dim3(256), 0, stream, pa, Xc, N, ld, out,  \
+                       exp_coef());                                                                             \
+    break;
+    OMB_PATHS(2) OMB_PATHS(4) OMB_PATHS(6) OMB_PATHS(8) OMB_PATHS(16) OMB_PATHS(32) OMB_PATHS(64)
+#undef OMB_PATHS
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_paths_eval(hipStream_t stream, const PathArgs& pa, int n_obj, int kind, bool libcos,
+                             const double* Xc, int64_t N, int64_t ld, double* out) {
+  if (kind == OMB_KERNEL_RBF)
+    return libcos ? launch_paths_kind<OMB_KERNEL_RBF, true>(stream, pa, n_obj, Xc, N, ld, out)
+                  : launch_paths_kind<OMB_KERNEL_RBF, false>(stream, pa, n_obj, Xc, N, ld, out);
+  return libcos ? launch_paths_kind<OMB_KERNEL_MATERN52, true>(stream, pa, n_obj, Xc, N, ld, out)
+                : launch_paths_kind<OMB_KERNEL_MATERN52, false>(stream, pa, n_obj, Xc, N, ld, out);
+}
+
+// U (n, S) row-major = F (S rows of pitch n: the prior paths at the training inputs) transposed + sd·z
+__global__ void paths_u_kernel(const double* __restrict__ F, const double* __restrict__ z, double sd, int n, int S,
+                               double* __restrict__ U) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)n * S) return;
+  const int i = (int)(t / S), s = (int)(t % S);
+  const double f = F[(int64_t)s * n + i];
+  U[t] = z ? fma(sd, z[t], f) : f;
+}
+
+hipError_t launch_paths_u(hipStream_t stream, const double* F, const double* z, double sd, int n, int S, double* U) {
+  const int64_t total = (int64_t)n * S;
+  hipLaunchKernelGGL(paths_u_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, F, z, sd, n, S, U);
+  return hipGetLastError();
+}
+
+// Vf: v = α − G (G (n, S) = L⁻ᵀL⁻¹U) as the A operand of the update term, row tile T, k-step e:
+//     Vf[(4T + e)·64 + lane] = v[16T + 4e + (lane>>4)][lane&15], 0 past n rows or S paths
+__global__ void paths_pack_v_kernel(const double* __restrict__ alpha, const double* __restrict__ G, int n, int S,
+                                    int64_t total, double* __restrict__ Vf) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const int lane = (int)(t & 63);
+  const int64_t row = 4 * (t >> 6) + (lane >> 4);
+  const int s = lane & 15;
+  Vf[t] = (row < n && s < S) ? alpha[row] - G[row * S + s] : 0.0;
+}
+
+hipError_t launch_paths_pack_v(hipStream_t stream, const double* alpha, const double* G, int n, int S, int R,
+                               double* Vf) {
+  const int64_t total = paths_vf_doubles(R);
+  hipLaunchKernelGGL(paths_pack_v_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, alpha, G, n,
+                     S, total, Vf);
+  return hipGetLastError();
+}
+
+}  // namespace omb

@@ -41,6 +41,7 @@ class AcqContext:
         self._gp_keep = {}     # device tensors referenced by the packed GP state
         self.gp_info = {}
         self.plan_kind = None  # (omb_plan_* name, mode) of the plan last set through this object
+        self._paths_S = {}     # objective → S of the sample paths last installed through this object
 
     # ------------------------------------------------------------------ plumbing
     def _check(self, rc, what):
@@ -81,14 +82,16 @@ class AcqContext:
         ("posterior_all_var", 0/1) lets the fused chain skip the posterior variance of objectives the planned
         acquisition never reads (default) / compute every objective's (bit-identical values);
         ("posterior_mean_kernel", 0/1/2) computes those objectives' mean inside the posterior launch / in a kernel
-        of its own after it (default) / in that kernel before it (bit-identical values)."""
+        of its own after it (default) / in that kernel before it (bit-identical values); ("paths_libcos", 0/1)
+        evaluates the sample paths' features with the kernel's own cosine (default) / the device library's."""
         code = {"spin_limit": _lib.DEBUG_SPIN_LIMIT, "cov_table": _lib.DEBUG_COV_TABLE,
                 "fused_chain": _lib.DEBUG_FUSED_CHAIN, "argmax_passes": _lib.DEBUG_ARGMAX_PASSES,
                 "chol_mode": _lib.DEBUG_CHOL_MODE, "timing_stride": _lib.DEBUG_TIMING_STRIDE,
                 "cov_fused": _lib.DEBUG_COV_FUSED,
                 "select_seq": _lib.DEBUG_SELECT_SEQ, "syrk_glds": _lib.DEBUG_SYRK_GLDS,
                 "boxes_kd": _lib.DEBUG_BOXES_KD, "posterior_all_var": _lib.DEBUG_POSTERIOR_ALL_VAR,
-                "posterior_mean_kernel": _lib.DEBUG_POSTERIOR_MEAN_KERNEL}[what]
+                "posterior_mean_kernel": _lib.DEBUG_POSTERIOR_MEAN_KERNEL,
+                "paths_libcos": _lib.DEBUG_PATHS_LIBCOS}[what]
         self._check(self.lib.omb_debug_set(self._h, code, int(value)), "omb_debug_set")
 
     # ------------------------------------------------------------------ GP state
@@ -569,6 +572,56 @@ class AcqContext:
         self._stream()
         self._check(self.lib.omb_thompson_select(self._h, _ptr(Y), B, N, _ptr(idx)), "omb_thompson_select")
         return idx
+
+    # ------------------------------------------------------------------ posterior sample paths
+    def paths_set(self, obj, omega, phase, w, z=None, noise=0.0):
+        """Install S posterior sample paths of objective ``obj`` (omb_paths_set): frequencies omega (m, d) of x/ℓ,
+        phases (m,), standard normals w (m, S) and z (n_train, S) (None: ε = 0), ``noise`` the σ_n² the state was
+        factorised with.  Host arrays (optimobo_amd.paths.draw_path_inputs draws them); the paths stand until the
+        objective's state changes."""
+        omega = np.ascontiguousarray(omega, dtype=np.float64)
+        phase = np.ascontiguousarray(phase, dtype=np.float64).reshape(-1)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        info = self.gp_info.get(obj)
+        if omega.ndim != 2 or w.ndim != 2 or phase.shape[0] != omega.shape[0] or w.shape[0] != omega.shape[0]:
+            raise ValueError(f"paths_set: shapes omega{omega.shape} phase{phase.shape} w{w.shape}")
+        m, S = w.shape
+        if info is not None and omega.shape[1] != info["d"]:
+            raise ValueError(f"paths_set: omega has {omega.shape[1]} columns but objective {obj}'s GP has "
+                             f"n_var={info['d']}")
+        if z is not None:
+            z = np.ascontiguousarray(z, dtype=np.float64)
+            if info is not None and z.shape != (info["n"], S):
+                raise ValueError(f"paths_set: z{z.shape} is not (n_train, S) = ({info['n']}, {S})")
+        self._stream()
+        self._paths_S.pop(obj, None)
+        self._check(self.lib.omb_paths_set(self._h, int(obj), S, m, _lib.host_ptr(omega), _lib.host_ptr(phase),
+                                           _lib.host_ptr(w), _lib.host_ptr(z) if z is not None else None,
+                                           float(noise)), "omb_paths_set")
+        self._paths_S[obj] = S
+
+    def paths_eval(self, Xc, n_obj=None, out=None):
+        """The installed paths of objectives 0..n_obj-1 at candidates Xc (N, d) → (n_obj, S, N) (omb_paths_eval).
+        ``out``: a (n_obj, S, ld ≥ N) tensor whose rows are contiguous; columns past N stay untouched."""
+        Xc = _dev_f64(Xc, self.device)
+        self._check_width(Xc)
+        n_obj = n_obj if n_obj is not None else len(self.gp_info)
+        N = Xc.shape[0]
+        if out is None:
+            out = torch.empty((n_obj, self._paths_S.get(0, 1), N), dtype=torch.float64, device=self.device)
+        else:
+            # the kernel writes row (o·S + s) at pitch ld: any other layout would be written out of bounds
+            S = self._paths_S.get(0)
+            if S is None or not isinstance(out, torch.Tensor) or out.dtype != torch.float64 \
+                    or out.device != self.device or out.dim() != 3 or tuple(out.shape[:2]) != (n_obj, S) \
+                    or out.shape[2] < N or (out.shape[2] > 1 and out.stride(2) != 1) \
+                    or out.stride(0) != S * out.stride(1) or out.stride(1) < N:
+                raise ValueError(f"paths_eval: out must be a ({n_obj}, S, ld >= {N}) fp64 tensor on {self.device} with "
+                                 "unit column stride and evenly pitched rows, S the paths installed on objective 0")
+        ld = out.stride(1)
+        self._stream()
+        self._check(self.lib.omb_paths_eval(self._h, int(n_obj), _ptr(Xc), N, int(ld), _ptr(out)), "omb_paths_eval")
+        return out
 
     def ea_search(self, pop, tape, best, lower, upper, mode=0, var_eps=1e-6):
         """ParEGO (mode 0: EI of objective 0) / KEEP (mode 1: μ of objective 1 · EI of objective 0)

@@ -707,6 +707,17 @@ class GPRegression:
         return ctx.posterior_samples(0, torch.as_tensor(Xnew, device=ctx.device),
                                      torch.as_tensor(Z, device=ctx.device), jitter_rel=jitter_rel)
 
+    def posterior_sample_paths(self, Xnew, size=10, n_features=1024, seed=0):
+        """(size, m) device tensor: ``size`` ≤ 16 posterior draws that are functions (pathwise conditioning on
+        ``n_features`` random Fourier features, AcquisitionEngine.sample_paths) evaluated at Xnew.  Nothing is
+        factorised, so any number of points goes; the same seed gives the same functions at any other Xnew."""
+        import torch
+        from .acquisition import engine_for
+        eng = engine_for([self])
+        Xnew = np.atleast_2d(np.asarray(Xnew, np.float64))
+        eng.sample_paths(int(size), n_features=n_features, seed=seed, lower=Xnew.min(0), upper=Xnew.max(0))
+        return eng.path_values(torch.as_tensor(Xnew, device=eng.device))[0]
+
     def posterior_samples_f(self, X, size=10, **kw):
         """GPy GP.posterior_samples_f: (m, 1, size) joint draws of the latent function."""
         Y, _ = self.posterior_samples_device(X, size)

@@ -7,7 +7,9 @@
                     batch_size 4 row, measured again here);
   believer_ehvi     the exact 2-D EHVI (mode "textbook") with the Kriging believer;
   thompson_ehvi     batch_strategy="thompson" at the default candidate count (hypervolume improvement of joint
-                    posterior draws; it takes the EHVI acquisitions only, so believer_ehvi is its counterpart).
+                    posterior draws; it takes the EHVI acquisitions only, so believer_ehvi is its counterpart);
+  thompson_paths    the same with thompson_sampler="paths": posterior sample paths at 2^16 candidates and two
+                    refinement rounds around every nominee (nothing factorised, so no fallback can arise).
 The variants alternate within every seed after one warm-up round; wall clock around a solve that ends in a
 synchronise.  One JSON line per variant: ms per true evaluation (median, min, max over the seeds), its fit /
 proposal split, the last hypervolume entry of every seed, and the Thompson iterations that fell back.
@@ -47,7 +49,9 @@ def main():
 
     variants = {"believer_tch": dict(kw={}, tch=True),
                 "believer_ehvi": dict(kw=dict(mode="textbook"), tch=False),
-                "thompson_ehvi": dict(kw=dict(mode="textbook", batch_strategy="thompson"), tch=False)}
+                "thompson_ehvi": dict(kw=dict(mode="textbook", batch_strategy="thompson"), tch=False),
+                "thompson_paths": dict(kw=dict(mode="textbook", batch_strategy="thompson", thompson_sampler="paths"),
+                                       tch=False)}
 
     def run(name, seed):
         v = variants[name]
