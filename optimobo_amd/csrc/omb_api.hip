@@ -33,7 +33,9 @@ struct ObjState {
   const double* path_Vf = nullptr;
 };
 
-// Acquisition of the fused chain (omb_plan_*), with its geometry resident in ctx->geo.
+// One acquisition request.  A describe_* function validates the scalar arguments and fills everything but geo / boxes;
+// a stand-alone entry then points those at the caller's device arrays, an omb_plan_* entry uploads the host geometry
+// and points them at ctx->geo (the fused chain's plan).  launch_acq / launch_acq_grad run it.
 enum PlanKind { PLAN_NONE = 0, PLAN_EHVI2D, PLAN_EHVI_MC, PLAN_EHVI_BOXES, PLAN_HVPOI, PLAN_EXPDEC, PLAN_EI };
 
 struct Plan {
@@ -55,6 +57,16 @@ struct Plan {
   double con_eps = 0;
 };
 
+// A device buffer that the context owns and grow_dev enlarges on demand.
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;  // bytes
+  template <class T>
+  T* as() const {
+    return static_cast<T*>(p);
+  }
+};
+
 struct omb_ctx {
   int device = 0;
   hipStream_t own_stream = nullptr;
@@ -67,12 +79,10 @@ struct omb_ctx {
   int* info_host = nullptr;       // pinned: the Cholesky status read back by run_cholesky / chol_wait
   // fused chain
   Plan plan;
-  void* geo = nullptr;    // device: plan geometry
-  size_t geo_cap = 0;
+  DevBuf geo;             // plan geometry
   void* stage = nullptr;  // pinned host staging of uploads
   size_t stage_cap = 0;
-  void* work = nullptr;   // device: mu | var | vals | raised | X of the fused chain
-  size_t work_cap = 0;
+  DevBuf work;            // mu | var | vals | raised | X of the fused chain
   void* sob = nullptr;    // device: packed Sobol state (fixed capacity)
   int sob_d = 0, sob_bits = 0;
   // timing of the fused chain: 5 events per chain (level 2) or 2 around the posterior (level 1)
@@ -81,32 +91,16 @@ struct omb_ctx {
   int64_t timing_calls = 0;  // chains since omb_timing
   std::vector<hipEvent_t> ev;
   size_t ev_used = 0;
-  // Thompson sampling: K* | V | μ | σ² | Σ workspace, and Cholesky info + step counters
-  void* tws = nullptr;
-  size_t tws_cap = 0;
-  void* ichol = nullptr;
-  size_t ichol_cap = 0;
-  // Thompson selection: per-sample sorted heads (select_sort_kernel)
-  void* sws = nullptr;
-  size_t sws_cap = 0;
-  // evolutionary search: L0⁻¹ transposed
-  void* ews = nullptr;
-  size_t ews_cap = 0;
-  // GP fit: Ky | L⁻¹ | Ky⁻¹ | scratch workspace
-  void* fws = nullptr;
-  size_t fws_cap = 0;
-  // dense posterior path (n_train > OMB_MAX_TRAIN): K* | V chunk workspace
-  void* dws = nullptr;
-  size_t dws_cap = 0;
-  // gradient chain (omb_posterior_grad / omb_eval_grad): ∂a/∂μ | ∂a/∂σ² | K* | V | w per objective
-  void* gws = nullptr;
-  size_t gws_cap = 0;
-  // omb_gp_append: the bordered state (AppendWs)
-  void* aws = nullptr;
-  size_t aws_cap = 0;
-  // omb_hvi_boxes: the slices' sums of a small batch (hvi_ws_doubles)
-  void* hws = nullptr;
-  size_t hws_cap = 0;
+  // workspaces, each its own allocation (several are live at once: work with gws, tws with ichol)
+  DevBuf tws;    // Thompson sampling: K* | V | μ | σ² | Σ
+  DevBuf ichol;  // Cholesky info + step counters
+  DevBuf sws;    // Thompson selection: per-sample sorted heads (select_sort_kernel)
+  DevBuf ews;    // evolutionary search: L0⁻¹ transposed
+  DevBuf fws;    // GP fit: Ky | L⁻¹ | Ky⁻¹ | scratch
+  DevBuf dws;    // dense posterior path (n_train > OMB_MAX_TRAIN): K* | V chunk
+  DevBuf gws;    // gradient chain (omb_posterior_grad / omb_eval_grad): ∂a/∂μ | ∂a/∂σ² | K* | V | w per objective
+  DevBuf aws;    // omb_gp_append: the bordered state (AppendWs)
+  DevBuf hws;    // omb_hvi_boxes: the slices' sums of a small batch (hvi_ws_doubles)
   // device fault word (pinned, mapped host memory): kernels mark it, enter() reports it
   int* fault_host = nullptr;
   int* fault_dev = nullptr;
@@ -114,20 +108,21 @@ struct omb_ctx {
   // directly (no D2H copy on the per-evaluation path), the blocked path copies into it
   double* fit_host = nullptr;
   double* fit_dev = nullptr;
+  // omb_debug_set's switches (kDebugSwitches): ints, the on/off ones 0 or 1
   int spin_limit = kDefaultSpinLimit;
-  bool cov_table = false;   // OMB_DEBUG_COV_TABLE
-  bool cov_fused = true;    // OMB_DEBUG_COV_FUSED: K(X*, X*) in the covariance SYRK's epilogue
-  bool syrk_glds = true;    // OMB_DEBUG_SYRK_GLDS: the covariance SYRK's direct-to-LDS operand pipeline
+  int cov_table = 0;    // OMB_DEBUG_COV_TABLE
+  int cov_fused = 1;    // OMB_DEBUG_COV_FUSED: K(X*, X*) in the covariance SYRK's epilogue
+  int syrk_glds = 1;    // OMB_DEBUG_SYRK_GLDS: the covariance SYRK's direct-to-LDS operand pipeline
   int fused_chain = 0;  // OMB_DEBUG_FUSED_CHAIN: 0 EHVI-2D then the arg-max's passes, 1 one ticketed launch, 2 EHVI
                         // with the per-workgroup pairs, then the arg-max's second pass
   bool argmax_one_pass = false;  // OMB_DEBUG_ARGMAX_PASSES: 1 (one launch) or 2 (default: measured level)
   int chol_mode = kCholPersistent;   // OMB_DEBUG_CHOL_MODE (value & 3): 1 per-step launches, else persistent
   int chol_acq_rel = 0;          // OMB_DEBUG_CHOL_MODE (value & 4): release / acquire hand-offs
   int chol_single = 0;           // OMB_DEBUG_CHOL_MODE (value & 8): every trailing update its own task
-  bool select_seq = false;       // OMB_DEBUG_SELECT_SEQ: the sequential greedy walk for B ≤ 64 too
-  bool boxes_kd_wave = false;    // OMB_DEBUG_BOXES_KD: omb_ehvi_boxes_k by one wavefront per candidate where that fits
-  bool paths_libcos = false;     // OMB_DEBUG_PATHS_LIBCOS: the sample paths' features through the library cosine
-  bool posterior_all_var = false;  // OMB_DEBUG_POSTERIOR_ALL_VAR: the chain computes σ² of every objective
+  int select_seq = 0;            // OMB_DEBUG_SELECT_SEQ: the sequential greedy walk for B ≤ 64 too
+  int boxes_kd_wave = 0;         // OMB_DEBUG_BOXES_KD: omb_ehvi_boxes_k by one wavefront per candidate where that fits
+  int paths_libcos = 0;          // OMB_DEBUG_PATHS_LIBCOS: the sample paths' features through the library cosine
+  int posterior_all_var = 0;     // OMB_DEBUG_POSTERIOR_ALL_VAR: the chain computes σ² of every objective
   int posterior_mean_kernel = kMeanKernelAfter;   // OMB_DEBUG_POSTERIOR_MEAN_KERNEL: masked objectives' μ in a launch of its own
 };
 
@@ -200,14 +195,14 @@ int gather_gp(omb_ctx* ctx, int n_obj, GPArgs* args, int* max_R) {
 std::string* E(omb_ctx* ctx) { return ctx ? &ctx->err : nullptr; }
 
 // ---- ctx-owned buffers
-int grow_dev(omb_ctx* ctx, void** buf, size_t* cap, size_t bytes, const char* what) {
-  if (bytes <= *cap) return OMB_OK;
+int grow_dev(omb_ctx* ctx, DevBuf& b, size_t bytes, const char* what) {
+  if (bytes <= b.cap) return OMB_OK;
   OMB_HIP(ctx, hipStreamSynchronize(ctx->stream));  // queued kernels may still read the old buffer
-  if (*buf) (void)hipFree(*buf);
-  *buf = nullptr;
-  *cap = 0;
-  if (hipMalloc(buf, bytes) != hipSuccess) return fail(ctx, OMB_ENOMEM, "hipMalloc(%zu) for %s", bytes, what);
-  *cap = bytes;
+  if (b.p) (void)hipFree(b.p);
+  b.p = nullptr;
+  b.cap = 0;
+  if (hipMalloc(&b.p, bytes) != hipSuccess) return fail(ctx, OMB_ENOMEM, "hipMalloc(%zu) for %s", bytes, what);
+  b.cap = bytes;
   return OMB_OK;
 }
 
@@ -226,24 +221,86 @@ int stage_begin(omb_ctx* ctx, size_t bytes, void** host) {
   return OMB_OK;
 }
 
-// Uploads the staged bytes as the plan geometry.
-int stage_to_geo(omb_ctx* ctx, size_t bytes) {
-  int rc = grow_dev(ctx, &ctx->geo, &ctx->geo_cap, bytes, "plan geometry");
+// ---- one description per acquisition: describe_* validates the scalars and fills the Plan (geo / boxes stay unset)
+// bits 0..k-1
+unsigned all_objectives(int k) { return k >= 32 ? ~0u : (1u << k) - 1u; }
+
+int describe_ehvi2d(omb_ctx* ctx, int P, const double* r, double s00, double s01, int mode, Plan* pl) {
+  int rc = check_ehvi2d(E(ctx), P, r, mode);
   if (rc) return rc;
-  OMB_HIP(ctx, hipMemcpyAsync(ctx->geo, ctx->stage, bytes, hipMemcpyHostToDevice, ctx->stream));
+  pl->kind = PLAN_EHVI2D;
+  pl->k = 2;
+  // ehvi2d_kernel / ehvi2d_argmax_kernel: reference mode passes 0 for σ²₁ (σ²₀ serves both objectives)
+  pl->var_mask = mode == OMB_EHVI_REFERENCE ? 1u : 3u;
+  pl->P = P;
+  pl->mode = mode;
+  pl->r[0] = r[0];
+  pl->r[1] = r[1];
+  pl->s00 = s00;
+  pl->s01 = s01;
   return OMB_OK;
 }
 
-int plan_begin(omb_ctx* ctx, size_t bytes, void** host) {
-  int rc = enter(ctx);
+int describe_ehvi_mc(omb_ctx* ctx, int k, int M, const double* r, double hv_pf, Plan* pl) {
+  int rc = check_ehvi_mc(E(ctx), k, M, r);
   if (rc) return rc;
-  ctx->plan = Plan();  // an invalid request leaves no plan behind
-  return bytes ? stage_begin(ctx, bytes, host) : OMB_OK;
+  pl->kind = PLAN_EHVI_MC;
+  pl->k = k;
+  pl->var_mask = 1u;   // ehvi_mc_kernel: σ²₀ for every objective
+  pl->M = M;
+  for (int j = 0; j < k; ++j) pl->r[j] = r[j];
+  pl->hv = hv_pf;
+  return OMB_OK;
 }
 
-// Posterior of objectives 0..n_obj-1 (their state in args.gp, dense L⁻¹ in Ld[o]): the fused kernel
-// when every n_train fits it, else per objective and candidate chunk K block → V = L⁻¹K* (GEMM) →
-// column reduction.
+// kd: omb_ehvi_boxes_k / omb_plan_ehvi_boxes_k (the k-D kernel, any 2 ≤ k ≤ OMB_MAX_OBJ), else k = 2, 3
+int describe_boxes(omb_ctx* ctx, bool kd, int k, int C, int B, Plan* pl) {
+  int rc = kd ? check_boxes_k(E(ctx), k, C, B) : check_boxes(E(ctx), k, C, B);
+  if (rc) return rc;
+  pl->kind = PLAN_EHVI_BOXES;
+  pl->boxes_kd = kd;
+  pl->k = k;
+  pl->var_mask = all_objectives(k);
+  pl->C = C;
+  pl->B = B;
+  return OMB_OK;
+}
+
+int describe_hvpoi(omb_ctx* ctx, int C, Plan* pl) {
+  int rc = check_hvpoi(E(ctx), C);
+  if (rc) return rc;
+  pl->kind = PLAN_HVPOI;
+  pl->k = 2;
+  pl->var_mask = 3u;
+  pl->C = C;
+  return OMB_OK;
+}
+
+int describe_expdec(omb_ctx* ctx, int k, int M, int scal_id, const double* params, const double* weights,
+                    const double* ideal, const double* max_point, double agg_min, Plan* pl) {
+  int rc = build_scal(E(ctx), k, M, scal_id, params, weights, ideal, max_point, agg_min, &pl->sp);
+  if (rc) return rc;
+  pl->kind = PLAN_EXPDEC;
+  pl->k = k;
+  pl->var_mask = 1u;   // expdec_kernel: σ²₀ for every objective
+  pl->M = M;
+  return OMB_OK;
+}
+
+int describe_ei(omb_ctx* ctx, int kind, int k, double best, double var_eps, double pof_eps, Plan* pl) {
+  int rc = check_ei(E(ctx), kind, k, var_eps, pof_eps);
+  if (rc) return rc;
+  pl->kind = PLAN_EI;
+  pl->ei_kind = kind;
+  pl->k = k;
+  // ei_kernel: EI of objective 0; the Pareto kind multiplies by μ₁, the constrained kind reads every σ²
+  pl->var_mask = kind == OMB_EI_CONSTRAINED ? all_objectives(k) : 1u;
+  pl->best = best;
+  pl->var_eps = var_eps;
+  pl->pof_eps = pof_eps;
+  return OMB_OK;
+}
+
 // omb_ehvi_boxes_k's kernel: candidate-blocked, or (OMB_DEBUG_BOXES_KD = 1, where its tables fit) the baseline
 hipError_t launch_boxes_k(omb_ctx* ctx, int k, const double* mu, const double* var, int64_t ld, int64_t N,
                           const double* coords, int C, const uint16_t* boxes, int B, double* out) {
@@ -251,6 +308,99 @@ hipError_t launch_boxes_k(omb_ctx* ctx, int k, const double* mu, const double* v
     return launch_ehvi_boxes_wave(ctx->stream, k, mu, var, ld, N, coords, C, boxes, B, out);
   return launch_ehvi_boxes_kd(ctx->stream, k, mu, var, ld, N, coords, C, boxes, B, out);
 }
+
+// The described acquisition over the moments (k, N) at row pitch ld: the only switch that launches value kernels.
+// raised: Monte-Carlo EHVI's per-candidate flags.  (Every Plan comes from a describe_*: no other kind exists.)
+hipError_t launch_acq(omb_ctx* ctx, const Plan& pl, const double* mu, const double* var, int64_t ld, int64_t N,
+                      double* out, int32_t* raised) {
+  hipStream_t st = ctx->stream;
+  switch (pl.kind) {
+    case PLAN_EHVI2D:
+      return launch_ehvi2d(st, mu, var, ld, N, pl.geo, pl.P, pl.r[0], pl.r[1], pl.s00, pl.s01, pl.mode, out);
+    case PLAN_EHVI_MC:
+      return launch_ehvi_mc(st, pl.k, mu, var, ld, N, pl.geo, pl.M, pl.r, pl.hv, out, raised);
+    case PLAN_EHVI_BOXES:
+      return pl.boxes_kd ? launch_boxes_k(ctx, pl.k, mu, var, ld, N, pl.geo, pl.C, pl.boxes, pl.B, out)
+                         : launch_ehvi_boxes(st, pl.k, mu, var, ld, N, pl.geo, pl.C, pl.boxes, pl.B, out);
+    case PLAN_HVPOI:
+      return launch_hvpoi(st, mu, var, ld, N, pl.geo, pl.C, out);
+    case PLAN_EXPDEC:
+      return launch_expdec(st, pl.sp, mu, var, ld, N, pl.geo, pl.M, out);
+    case PLAN_EI:
+      return launch_ei(st, pl.ei_kind, pl.k, mu, var, ld, N, pl.best, pl.var_eps, pl.pof_eps, out);
+    default:
+      return hipErrorInvalidValue;
+  }
+}
+
+// ∂a/∂μ | ∂a/∂σ² (k, N) of the described acquisition over the moments at row pitch N: the only switch that launches
+// gradient kernels, and the only place that knows which plans have no analytic gradient.  With dadm == nullptr it
+// launches nothing and answers only that question (omb_eval_grad asks before it looks at the GP state).
+int launch_acq_grad(omb_ctx* ctx, const Plan& pl, const double* mu, const double* var, int64_t N, double* dadm,
+                    double* dadv) {
+  hipStream_t st = ctx->stream;
+  const char* unsup = nullptr;
+  hipError_t e = hipSuccess;
+  switch (pl.kind) {
+    case PLAN_EHVI2D:
+      if (pl.mode == OMB_EHVI_SIGMA) unsup = "EHVI-2D in OMB_EHVI_SIGMA mode";
+      else if (dadm)
+        e = launch_ehvi2d_grad(st, mu, var, N, N, pl.geo, pl.P, pl.r[0], pl.r[1], pl.s00, pl.s01, pl.mode, dadm, dadv);
+      break;
+    case PLAN_EHVI_BOXES:
+      if (dadm) e = launch_ehvi_boxes_grad(st, pl.k, mu, var, N, N, pl.geo, pl.C, pl.boxes, pl.B, dadm, dadv);
+      break;
+    case PLAN_EI:
+      if (dadm) e = launch_ei_grad(st, pl.ei_kind, pl.k, mu, var, N, N, pl.best, pl.var_eps, pl.pof_eps, dadm, dadv);
+      break;
+    case PLAN_EHVI_MC: unsup = "Monte-Carlo EHVI"; break;
+    case PLAN_EXPDEC: unsup = "expected decomposition"; break;
+    case PLAN_HVPOI: unsup = "HV-PoI"; break;
+    default:
+      return fail(ctx, OMB_ESTATE, "corrupt plan");
+  }
+  if (unsup) return fail(ctx, OMB_EUNSUP, "the %s plan has no analytic gradient", unsup);
+  if (e != hipSuccess) return hip_fail(ctx, e, "acquisition gradient");
+  return OMB_OK;
+}
+
+// A stand-alone entry's tail, after its checks: the description over the caller's device geometry and moments.
+int run_acq(omb_ctx* ctx, Plan& pl, const double* geo_dev, const uint16_t* boxes_dev, const double* mu,
+            const double* var, int64_t ld, int64_t N, double* out, int32_t* raised, const char* where) {
+  if (N == 0) return OMB_OK;
+  pl.geo = geo_dev;
+  pl.boxes = boxes_dev;
+  hipError_t e = launch_acq(ctx, pl, mu, var, ld, N, out, raised);
+  if (e != hipSuccess) return hip_fail(ctx, e, where);
+  return OMB_OK;
+}
+
+// A plan entry's head: an invalid request leaves no plan behind.
+int plan_enter(omb_ctx* ctx) {
+  int rc = enter(ctx);
+  if (rc == OMB_OK) ctx->plan = Plan();
+  return rc;
+}
+
+// A plan entry's tail, after its checks: the host spans a | b through the pinned staging into ctx->geo, and the
+// description, pointed at them, becomes the context's plan.
+int install_plan(omb_ctx* ctx, Plan& pl, const void* a, size_t abytes, const void* b = nullptr, size_t bbytes = 0) {
+  void* h = nullptr;
+  int rc = stage_begin(ctx, abytes + bbytes, &h);
+  if (rc) return rc;
+  memcpy(h, a, abytes);
+  if (bbytes) memcpy(static_cast<char*>(h) + abytes, b, bbytes);
+  if ((rc = grow_dev(ctx, ctx->geo, abytes + bbytes, "plan geometry"))) return rc;
+  OMB_HIP(ctx, hipMemcpyAsync(ctx->geo.p, h, abytes + bbytes, hipMemcpyHostToDevice, ctx->stream));
+  pl.geo = ctx->geo.as<const double>();
+  if (bbytes) pl.boxes = reinterpret_cast<const uint16_t*>(ctx->geo.as<const char>() + abytes);
+  ctx->plan = pl;
+  return OMB_OK;
+}
+
+// Posterior of objectives 0..n_obj-1 (their state in args.gp, dense L⁻¹ in Ld[o]): the fused kernel
+// when every n_train fits it, else per objective and candidate chunk K block → V = L⁻¹K* (GEMM) →
+// column reduction.
 
 hipError_t posterior_any(omb_ctx* ctx, const GPArgs& args, const double* const* Ld, int n_obj, int max_R,
                          const double* Xc, int64_t N, double* mu, double* var) {
@@ -263,9 +413,9 @@ hipError_t posterior_any(omb_ctx* ctx, const GPArgs& args, const double* const* 
     int64_t Nc = (int64_t)(((size_t)256 << 20) / (16 * (size_t)n));   // K* and V chunks of 128 MiB each
     Nc = Nc < 256 ? 256 : (Nc / 256) * 256;
     if (Nc > N) Nc = N;
-    if (grow_dev(ctx, &ctx->dws, &ctx->dws_cap, sizeof(double) * 2 * (size_t)n * Nc, "dense posterior workspace"))
+    if (grow_dev(ctx, ctx->dws, sizeof(double) * 2 * (size_t)n * Nc, "dense posterior workspace"))
       return hipErrorOutOfMemory;
-    double* Kst = static_cast<double*>(ctx->dws);
+    double* Kst = ctx->dws.as<double>();
     double* V = Kst + (size_t)n * Nc;
     for (int64_t c0 = 0; c0 < N; c0 += Nc) {
       const int64_t nc = (N - c0) < Nc ? (N - c0) : Nc;
@@ -283,9 +433,6 @@ hipError_t posterior_any(omb_ctx* ctx, const GPArgs& args, const double* const* 
 void gather_Ld(omb_ctx* ctx, int n_obj, const double** Ld) {
   for (int o = 0; o < n_obj; ++o) Ld[o] = ctx->obj[o].Ld;
 }
-
-// bits 0..k-1
-unsigned all_objectives(int k) { return k >= 32 ? ~0u : (1u << k) - 1u; }
 
 // The fused chain: [Sobol →] posterior(0..k-1) → planned acquisition → [arg-max].  The posterior computes σ² of the
 // objectives in the plan's var_mask only (the others' slots of the workspace keep whatever they held); all_var (the
@@ -319,9 +466,8 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
   const bool acq_argmax = result_dev && !vals_out && N > 0 && ctx->fused_chain && pl.kind == PLAN_EHVI2D &&
                           pl.n_con == 0;   // the weight comes between EHVI and the arg-max: the plain path
   const size_t doubles = 2 * (size_t)K * nd + nd + (nd + 1) / 2 + (sobol ? nd * args.d : 0);
-  if ((rc = grow_dev(ctx, &ctx->work, &ctx->work_cap, (doubles ? doubles : 1) * sizeof(double), "chain workspace")))
-    return rc;
-  double* mu = static_cast<double*>(ctx->work);
+  if ((rc = grow_dev(ctx, ctx->work, (doubles ? doubles : 1) * sizeof(double), "chain workspace"))) return rc;
+  double* mu = ctx->work.as<double>();
   double* var = mu + (size_t)K * nd;
   double* vals = vals_out ? vals_out : var + (size_t)K * nd;
   int32_t* raised = reinterpret_cast<int32_t*>(var + (size_t)K * nd + nd);
@@ -360,36 +506,13 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
   if (e == hipSuccess && N > 0) e = posterior_any(ctx, args, Ld, K, max_R, Xc, N, mu, var);
   if (e == hipSuccess) e = mark(2);
   if (e == hipSuccess && N > 0) {
-    switch (pl.kind) {
-      case PLAN_EHVI2D:
-        if (acq_argmax) {
-          unsigned* ticket = ctx->fused_chain == 1 ? reinterpret_cast<unsigned*>(ctx->partials + 2 * kArgmaxMaxBlocks)
-                                                   : nullptr;
-          const ArgmaxOut am{ctx->partials, ticket, result_dev, offset};
-          e = launch_ehvi2d_argmax(ctx->stream, mu, var, N, N, pl.geo, pl.P, pl.r[0], pl.r[1], pl.s00, pl.s01, pl.mode,
-                                   am);
-        } else {
-          e = launch_ehvi2d(ctx->stream, mu, var, N, N, pl.geo, pl.P, pl.r[0], pl.r[1], pl.s00, pl.s01, pl.mode, acq);
-        }
-        break;
-      case PLAN_EHVI_MC:
-        e = launch_ehvi_mc(ctx->stream, k, mu, var, N, N, pl.geo, pl.M, pl.r, pl.hv, acq, raised);
-        break;
-      case PLAN_EHVI_BOXES:
-        e = pl.boxes_kd ? launch_boxes_k(ctx, k, mu, var, N, N, pl.geo, pl.C, pl.boxes, pl.B, acq)
-                        : launch_ehvi_boxes(ctx->stream, k, mu, var, N, N, pl.geo, pl.C, pl.boxes, pl.B, acq);
-        break;
-      case PLAN_HVPOI:
-        e = launch_hvpoi(ctx->stream, mu, var, N, N, pl.geo, pl.C, acq);
-        break;
-      case PLAN_EXPDEC:
-        e = launch_expdec(ctx->stream, pl.sp, mu, var, N, N, pl.geo, pl.M, acq);
-        break;
-      case PLAN_EI:
-        e = launch_ei(ctx->stream, pl.ei_kind, k, mu, var, N, N, pl.best, pl.var_eps, pl.pof_eps, acq);
-        break;
-      default:
-        return fail(ctx, OMB_ESTATE, "corrupt plan");
+    if (acq_argmax) {
+      unsigned* ticket = ctx->fused_chain == 1 ? reinterpret_cast<unsigned*>(ctx->partials + 2 * kArgmaxMaxBlocks)
+                                               : nullptr;
+      const ArgmaxOut am{ctx->partials, ticket, result_dev, offset};
+      e = launch_ehvi2d_argmax(ctx->stream, mu, var, N, N, pl.geo, pl.P, pl.r[0], pl.r[1], pl.s00, pl.s01, pl.mode, am);
+    } else {
+      e = launch_acq(ctx, pl, mu, var, N, N, acq, raised);
     }
     if (e == hipSuccess && pl.n_con)
       e = launch_pof_scale(ctx->stream, pl.n_con, mu + (size_t)k * nd, var + (size_t)k * nd, N, N, pl.con_eps, acq,
@@ -451,19 +574,11 @@ int omb_destroy(omb_ctx* ctx) {
   if (ctx->result_dev) (void)hipFree(ctx->result_dev);
   if (ctx->result_host) (void)hipHostFree(ctx->result_host);
   if (ctx->info_host) (void)hipHostFree(ctx->info_host);
-  if (ctx->geo) (void)hipFree(ctx->geo);
+  for (DevBuf* b : {&ctx->geo, &ctx->work, &ctx->tws, &ctx->ichol, &ctx->sws, &ctx->ews, &ctx->fws, &ctx->dws, &ctx->gws,
+                    &ctx->aws, &ctx->hws})
+    if (b->p) (void)hipFree(b->p);
   if (ctx->stage) (void)hipHostFree(ctx->stage);
-  if (ctx->work) (void)hipFree(ctx->work);
   if (ctx->sob) (void)hipFree(ctx->sob);
-  if (ctx->tws) (void)hipFree(ctx->tws);
-  if (ctx->ichol) (void)hipFree(ctx->ichol);
-  if (ctx->sws) (void)hipFree(ctx->sws);
-  if (ctx->ews) (void)hipFree(ctx->ews);
-  if (ctx->fws) (void)hipFree(ctx->fws);
-  if (ctx->dws) (void)hipFree(ctx->dws);
-  if (ctx->gws) (void)hipFree(ctx->gws);
-  if (ctx->aws) (void)hipFree(ctx->aws);
-  if (ctx->hws) (void)hipFree(ctx->hws);
   if (ctx->fault_host) (void)hipHostFree(ctx->fault_host);
   if (ctx->fit_host) (void)hipHostFree(ctx->fit_host);
   for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
@@ -491,61 +606,41 @@ int omb_synchronize(omb_ctx* ctx) {
   return check_fault(ctx);
 }
 
+// omb_debug_set's plain switches: the value goes into the field when it lies in [lo, hi], else the message (one %lld:
+// the value) is the error.  On/off switches have no message: any non-zero value is on.
+struct DebugSwitch {
+  int code;
+  int omb_ctx::*field;
+  int64_t lo, hi;
+  const char* msg;
+};
+static const DebugSwitch kDebugSwitches[] = {
+    {OMB_DEBUG_SPIN_LIMIT, &omb_ctx::spin_limit, 0, 0x7fffffff, "spin limit %lld outside [0, 2^31)"},
+    {OMB_DEBUG_FUSED_CHAIN, &omb_ctx::fused_chain, 0, 2, "fused chain %lld (0, 1 or 2)"},
+    {OMB_DEBUG_TIMING_STRIDE, &omb_ctx::timing_stride, 1, 0x7fffffff, "timing stride %lld < 1"},
+    {OMB_DEBUG_POSTERIOR_MEAN_KERNEL, &omb_ctx::posterior_mean_kernel, 0, 2,
+     "posterior mean kernel %lld (0 off, 1 after the posterior launch, 2 before it)"},
+    {OMB_DEBUG_COV_TABLE, &omb_ctx::cov_table, 0, 1, nullptr},
+    {OMB_DEBUG_COV_FUSED, &omb_ctx::cov_fused, 0, 1, nullptr},
+    {OMB_DEBUG_SYRK_GLDS, &omb_ctx::syrk_glds, 0, 1, nullptr},
+    {OMB_DEBUG_SELECT_SEQ, &omb_ctx::select_seq, 0, 1, nullptr},
+    {OMB_DEBUG_BOXES_KD, &omb_ctx::boxes_kd_wave, 0, 1, nullptr},
+    {OMB_DEBUG_PATHS_LIBCOS, &omb_ctx::paths_libcos, 0, 1, nullptr},
+    {OMB_DEBUG_POSTERIOR_ALL_VAR, &omb_ctx::posterior_all_var, 0, 1, nullptr},
+};
+
 int omb_debug_set(omb_ctx* ctx, int what, int64_t value) {
   if (!ctx) return OMB_EINVAL;
-  if (what == OMB_DEBUG_SPIN_LIMIT) {
-    if (value < 0 || value > 0x7fffffff) return fail(ctx, OMB_EINVAL, "spin limit %lld outside [0, 2^31)", (long long)value);
-    ctx->spin_limit = (int)value;
-    return OMB_OK;
-  }
-  if (what == OMB_DEBUG_FUSED_CHAIN) {
-    if (value < 0 || value > 2) return fail(ctx, OMB_EINVAL, "fused chain %lld (0, 1 or 2)", (long long)value);
-    ctx->fused_chain = (int)value;
+  for (const DebugSwitch& s : kDebugSwitches) {
+    if (s.code != what) continue;
+    if (!s.msg) value = value != 0;
+    else if (value < s.lo || value > s.hi) return fail(ctx, OMB_EINVAL, s.msg, (long long)value);
+    ctx->*s.field = (int)value;
     return OMB_OK;
   }
   if (what == OMB_DEBUG_ARGMAX_PASSES) {
     if (value != 1 && value != 2) return fail(ctx, OMB_EINVAL, "arg-max passes %lld (1 or 2)", (long long)value);
     ctx->argmax_one_pass = value == 1;
-    return OMB_OK;
-  }
-  if (what == OMB_DEBUG_COV_TABLE) {
-    ctx->cov_table = value != 0;
-    return OMB_OK;
-  }
-  if (what == OMB_DEBUG_TIMING_STRIDE) {
-    if (value < 1 || value > 0x7fffffff) return fail(ctx, OMB_EINVAL, "timing stride %lld < 1", (long long)value);
-    ctx->timing_stride = (int)value;
-    return OMB_OK;
-  }
-  if (what == OMB_DEBUG_COV_FUSED) {
-    ctx->cov_fused = value != 0;
-    return OMB_OK;
-  }
-  if (what == OMB_DEBUG_SYRK_GLDS) {
-    ctx->syrk_glds = value != 0;
-    return OMB_OK;
-  }
-  if (what == OMB_DEBUG_SELECT_SEQ) {
-    ctx->select_seq = value != 0;
-    return OMB_OK;
-  }
-  if (what == OMB_DEBUG_BOXES_KD) {
-    ctx->boxes_kd_wave = value != 0;
-    return OMB_OK;
-  }
-  if (what == OMB_DEBUG_PATHS_LIBCOS) {
-    ctx->paths_libcos = value != 0;
-    return OMB_OK;
-  }
-  if (what == OMB_DEBUG_POSTERIOR_ALL_VAR) {
-    ctx->posterior_all_var = value != 0;
-    return OMB_OK;
-  }
-  if (what == OMB_DEBUG_POSTERIOR_MEAN_KERNEL) {
-    if (value < 0 || value > 2)
-      return fail(ctx, OMB_EINVAL, "posterior mean kernel %lld (0 off, 1 after the posterior launch, 2 before it)",
-                  (long long)value);
-    ctx->posterior_mean_kernel = (int)value;
     return OMB_OK;
   }
   if (what == OMB_DEBUG_CHOL_MODE) {
@@ -659,11 +754,10 @@ int omb_gp_append(omb_ctx* ctx, int obj, int q, const double* Xnew_dev, const do
   if ((int64_t)n + q > OMB_MAX_TRAIN_DENSE)
     return fail(ctx, OMB_EUNSUP, "n_train + q = %lld above %d", (long long)n + q, OMB_MAX_TRAIN_DENSE);
   const int m = n + q;
-  if ((rc = grow_dev(ctx, &ctx->aws, &ctx->aws_cap, sizeof(double) * (size_t)append_ws_doubles(m, d, DP),
-                     "append workspace")))
+  if ((rc = grow_dev(ctx, ctx->aws, sizeof(double) * (size_t)append_ws_doubles(m, d, DP), "append workspace")))
     return rc;
   AppendWs ws;
-  append_ws_carve(static_cast<double*>(ctx->aws), m, d, DP, &ws);
+  append_ws_carve(ctx->aws.as<double>(), m, d, DP, &ws);
   hipStream_t st = ctx->stream;
   const auto d2d = hipMemcpyDeviceToDevice;
   // the installed state into the bordered copy; the new rows scaled by the kernel that packs every state's rows
@@ -745,14 +839,11 @@ int omb_ehvi2d(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_
                double* out_dev) {
   int rc = enter(ctx);
   if (rc) return rc;
+  Plan pl;
   if ((rc = check_moments(E(ctx), mu_dev, var_dev, ld, N, 2, out_dev))) return rc;
   if (!pf_sorted_dev) return fail(ctx, OMB_EINVAL, "null Pareto front");
-  if ((rc = check_ehvi2d(E(ctx), P, r_host, mode))) return rc;
-  if (N == 0) return OMB_OK;
-  hipError_t e = launch_ehvi2d(ctx->stream, mu_dev, var_dev, ld, N, pf_sorted_dev, P, r_host[0], r_host[1], s00, s01,
-                               mode, out_dev);
-  if (e != hipSuccess) return hip_fail(ctx, e, "ehvi2d");
-  return OMB_OK;
+  if ((rc = describe_ehvi2d(ctx, P, r_host, s00, s01, mode, &pl))) return rc;
+  return run_acq(ctx, pl, pf_sorted_dev, nullptr, mu_dev, var_dev, ld, N, out_dev, nullptr, "ehvi2d");
 }
 
 int omb_ehvi_mc(omb_ctx* ctx, int k, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
@@ -760,14 +851,11 @@ int omb_ehvi_mc(omb_ctx* ctx, int k, const double* mu_dev, const double* var_dev
                 int32_t* raised_dev) {
   int rc = enter(ctx);
   if (rc) return rc;
-  if ((rc = check_ehvi_mc(E(ctx), k, M, r_host))) return rc;
+  Plan pl;
+  if ((rc = describe_ehvi_mc(ctx, k, M, r_host, hv_pf, &pl))) return rc;
   if ((rc = check_moments(E(ctx), mu_dev, var_dev, ld, N, k, out_dev))) return rc;
   if (!cache_dev) return fail(ctx, OMB_EINVAL, "null cache");
-  if (N == 0) return OMB_OK;
-  hipError_t e = launch_ehvi_mc(ctx->stream, k, mu_dev, var_dev, ld, N, cache_dev, M, r_host, hv_pf, out_dev,
-                                raised_dev);
-  if (e != hipSuccess) return hip_fail(ctx, e, "ehvi_mc");
-  return OMB_OK;
+  return run_acq(ctx, pl, cache_dev, nullptr, mu_dev, var_dev, ld, N, out_dev, raised_dev, "ehvi_mc");
 }
 
 int omb_ehvi3d_mc(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
@@ -776,31 +864,29 @@ int omb_ehvi3d_mc(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int
   return omb_ehvi_mc(ctx, 3, mu_dev, var_dev, ld, N, cache_dev, M, r_host, hv_pf, out_dev, raised_dev);
 }
 
-int omb_ehvi_boxes(omb_ctx* ctx, int k, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
-                   const double* coords_dev, int C, const uint16_t* boxes_dev, int B, double* out_dev) {
+// omb_ehvi_boxes (kd false) and omb_ehvi_boxes_k (kd true, whose kernel reads the box list in 4-byte words)
+static int ehvi_boxes_entry(omb_ctx* ctx, bool kd, int k, const double* mu_dev, const double* var_dev, int64_t ld,
+                            int64_t N, const double* coords_dev, int C, const uint16_t* boxes_dev, int B,
+                            double* out_dev) {
   int rc = enter(ctx);
   if (rc) return rc;
-  if ((rc = check_boxes(E(ctx), k, C, B))) return rc;
+  Plan pl;
+  if ((rc = describe_boxes(ctx, kd, k, C, B, &pl))) return rc;
   if ((rc = check_moments(E(ctx), mu_dev, var_dev, ld, N, k, out_dev))) return rc;
   if (!coords_dev || !boxes_dev) return fail(ctx, OMB_EINVAL, "null grid/box list");
-  if (N == 0) return OMB_OK;
-  hipError_t e = launch_ehvi_boxes(ctx->stream, k, mu_dev, var_dev, ld, N, coords_dev, C, boxes_dev, B, out_dev);
-  if (e != hipSuccess) return hip_fail(ctx, e, "ehvi_boxes");
-  return OMB_OK;
+  if (kd && (reinterpret_cast<uintptr_t>(boxes_dev) & 3)) return fail(ctx, OMB_EINVAL, "box list not 4-byte aligned");
+  return run_acq(ctx, pl, coords_dev, boxes_dev, mu_dev, var_dev, ld, N, out_dev, nullptr,
+                 kd ? "ehvi_boxes_k" : "ehvi_boxes");
+}
+
+int omb_ehvi_boxes(omb_ctx* ctx, int k, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
+                   const double* coords_dev, int C, const uint16_t* boxes_dev, int B, double* out_dev) {
+  return ehvi_boxes_entry(ctx, false, k, mu_dev, var_dev, ld, N, coords_dev, C, boxes_dev, B, out_dev);
 }
 
 int omb_ehvi_boxes_k(omb_ctx* ctx, int k, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
                      const double* coords_dev, int C, const uint16_t* boxes_dev, int B, double* out_dev) {
-  int rc = enter(ctx);
-  if (rc) return rc;
-  if ((rc = check_boxes_k(E(ctx), k, C, B))) return rc;
-  if ((rc = check_moments(E(ctx), mu_dev, var_dev, ld, N, k, out_dev))) return rc;
-  if (!coords_dev || !boxes_dev) return fail(ctx, OMB_EINVAL, "null grid/box list");
-  if (reinterpret_cast<uintptr_t>(boxes_dev) & 3) return fail(ctx, OMB_EINVAL, "box list not 4-byte aligned");
-  if (N == 0) return OMB_OK;
-  hipError_t e = launch_boxes_k(ctx, k, mu_dev, var_dev, ld, N, coords_dev, C, boxes_dev, B, out_dev);
-  if (e != hipSuccess) return hip_fail(ctx, e, "ehvi_boxes_k");
-  return OMB_OK;
+  return ehvi_boxes_entry(ctx, true, k, mu_dev, var_dev, ld, N, coords_dev, C, boxes_dev, B, out_dev);
 }
 
 int omb_hvi_boxes(omb_ctx* ctx, int k, const double* y_dev, int64_t ld, int64_t N, const double* coords_dev, int C,
@@ -810,10 +896,9 @@ int omb_hvi_boxes(omb_ctx* ctx, int k, const double* y_dev, int64_t ld, int64_t 
   if ((rc = check_hvi_boxes(E(ctx), k, y_dev, ld, N, coords_dev, C, boxes_dev, B, out_dev))) return rc;
   if (N == 0) return OMB_OK;
   const int64_t wsd = hvi_ws_doubles(N, B);
-  if (wsd && (rc = grow_dev(ctx, &ctx->hws, &ctx->hws_cap, sizeof(double) * (size_t)wsd, "HVI slice workspace")))
-    return rc;
+  if (wsd && (rc = grow_dev(ctx, ctx->hws, sizeof(double) * (size_t)wsd, "HVI slice workspace"))) return rc;
   hipError_t e = launch_hvi_boxes(ctx->stream, k, y_dev, ld, N, coords_dev, C, boxes_dev, B, out_dev,
-                                  wsd ? static_cast<double*>(ctx->hws) : nullptr);
+                                  wsd ? ctx->hws.as<double>() : nullptr);
   if (e != hipSuccess) return hip_fail(ctx, e, "hvi_boxes");
   return OMB_OK;
 }
@@ -822,13 +907,11 @@ int omb_hvpoi(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_t
               const double* cells_dev, int C, double* out_dev) {
   int rc = enter(ctx);
   if (rc) return rc;
+  Plan pl;
   if ((rc = check_moments(E(ctx), mu_dev, var_dev, ld, N, 2, out_dev))) return rc;
   if (!cells_dev) return fail(ctx, OMB_EINVAL, "null cells");
-  if ((rc = check_hvpoi(E(ctx), C))) return rc;
-  if (N == 0) return OMB_OK;
-  hipError_t e = launch_hvpoi(ctx->stream, mu_dev, var_dev, ld, N, cells_dev, C, out_dev);
-  if (e != hipSuccess) return hip_fail(ctx, e, "hvpoi");
-  return OMB_OK;
+  if ((rc = describe_hvpoi(ctx, C, &pl))) return rc;
+  return run_acq(ctx, pl, cells_dev, nullptr, mu_dev, var_dev, ld, N, out_dev, nullptr, "hvpoi");
 }
 
 int omb_expdec(omb_ctx* ctx, int k, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
@@ -836,14 +919,12 @@ int omb_expdec(omb_ctx* ctx, int k, const double* mu_dev, const double* var_dev,
                const double* ideal_host, const double* max_host, double agg_min, double* out_dev) {
   int rc = enter(ctx);
   if (rc) return rc;
-  ScalParams sp;
-  if ((rc = build_scal(E(ctx), k, M, scal_id, params_host, weights_host, ideal_host, max_host, agg_min, &sp))) return rc;
+  Plan pl;
+  if ((rc = describe_expdec(ctx, k, M, scal_id, params_host, weights_host, ideal_host, max_host, agg_min, &pl)))
+    return rc;
   if ((rc = check_moments(E(ctx), mu_dev, var_dev, ld, N, k, out_dev))) return rc;
   if (!cache_dev) return fail(ctx, OMB_EINVAL, "null cache");
-  if (N == 0) return OMB_OK;
-  hipError_t e = launch_expdec(ctx->stream, sp, mu_dev, var_dev, ld, N, cache_dev, M, out_dev);
-  if (e != hipSuccess) return hip_fail(ctx, e, "expdec");
-  return OMB_OK;
+  return run_acq(ctx, pl, cache_dev, nullptr, mu_dev, var_dev, ld, N, out_dev, nullptr, "expdec");
 }
 
 int omb_ei(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_t N, double best, double var_eps,
@@ -855,12 +936,10 @@ int omb_ei_ext(omb_ctx* ctx, int kind, int k, const double* mu_dev, const double
                double best, double var_eps, double pof_eps, double* out_dev) {
   int rc = enter(ctx);
   if (rc) return rc;
-  if ((rc = check_ei(E(ctx), kind, k, var_eps, pof_eps))) return rc;
+  Plan pl;
+  if ((rc = describe_ei(ctx, kind, k, best, var_eps, pof_eps, &pl))) return rc;
   if ((rc = check_moments(E(ctx), mu_dev, var_dev, ld, N, k, out_dev))) return rc;
-  if (N == 0) return OMB_OK;
-  hipError_t e = launch_ei(ctx->stream, kind, k, mu_dev, var_dev, ld, N, best, var_eps, pof_eps, out_dev);
-  if (e != hipSuccess) return hip_fail(ctx, e, "ei");
-  return OMB_OK;
+  return run_acq(ctx, pl, nullptr, nullptr, mu_dev, var_dev, ld, N, out_dev, nullptr, "ei");
 }
 
 int omb_feasibility(omb_ctx* ctx, int c, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
@@ -898,154 +977,67 @@ int omb_argmax(omb_ctx* ctx, const double* vals_dev, int64_t N, int64_t offset, 
 
 int omb_plan_ehvi2d(omb_ctx* ctx, const double* pf_sorted_host, int P, const double* r_host, double s00, double s01,
                     int mode) {
-  void* h = nullptr;
-  int rc = enter(ctx);
+  int rc = plan_enter(ctx);
   if (rc) return rc;
-  ctx->plan = Plan();
-  if ((rc = check_ehvi2d(E(ctx), P, r_host, mode))) return rc;
-  if (!pf_sorted_host) return fail(ctx, OMB_EINVAL, "null Pareto front");
-  const size_t bytes = sizeof(double) * 2 * (size_t)P;
-  if ((rc = plan_begin(ctx, bytes, &h))) return rc;
-  memcpy(h, pf_sorted_host, bytes);
-  if ((rc = stage_to_geo(ctx, bytes))) return rc;
   Plan pl;
-  pl.kind = PLAN_EHVI2D;
-  pl.k = 2;
-  // ehvi2d_kernel / ehvi2d_argmax_kernel: reference mode passes 0 for σ²₁ (σ²₀ serves both objectives)
-  pl.var_mask = mode == OMB_EHVI_REFERENCE ? 1u : 3u;
-  pl.P = P;
-  pl.mode = mode;
-  pl.r[0] = r_host[0];
-  pl.r[1] = r_host[1];
-  pl.s00 = s00;
-  pl.s01 = s01;
-  pl.geo = static_cast<const double*>(ctx->geo);
-  ctx->plan = pl;
-  return OMB_OK;
+  if ((rc = describe_ehvi2d(ctx, P, r_host, s00, s01, mode, &pl))) return rc;
+  if (!pf_sorted_host) return fail(ctx, OMB_EINVAL, "null Pareto front");
+  return install_plan(ctx, pl, pf_sorted_host, sizeof(double) * 2 * (size_t)P);
 }
 
 int omb_plan_ehvi_mc(omb_ctx* ctx, int k, const double* cache_host, int M, const double* r_host, double hv_pf) {
-  void* h = nullptr;
-  int rc = enter(ctx);
+  int rc = plan_enter(ctx);
   if (rc) return rc;
-  ctx->plan = Plan();
-  if ((rc = check_ehvi_mc(E(ctx), k, M, r_host))) return rc;
-  if (!cache_host) return fail(ctx, OMB_EINVAL, "null cache");
-  const size_t bytes = sizeof(double) * (size_t)k * M;
-  if ((rc = plan_begin(ctx, bytes, &h))) return rc;
-  memcpy(h, cache_host, bytes);
-  if ((rc = stage_to_geo(ctx, bytes))) return rc;
   Plan pl;
-  pl.kind = PLAN_EHVI_MC;
-  pl.k = k;
-  pl.var_mask = 1u;   // ehvi_mc_kernel: σ²₀ for every objective
-  pl.M = M;
-  for (int j = 0; j < k; ++j) pl.r[j] = r_host[j];
-  pl.hv = hv_pf;
-  pl.geo = static_cast<const double*>(ctx->geo);
-  ctx->plan = pl;
-  return OMB_OK;
+  if ((rc = describe_ehvi_mc(ctx, k, M, r_host, hv_pf, &pl))) return rc;
+  if (!cache_host) return fail(ctx, OMB_EINVAL, "null cache");
+  return install_plan(ctx, pl, cache_host, sizeof(double) * (size_t)k * M);
 }
 
 int omb_plan_ehvi3d_mc(omb_ctx* ctx, const double* cache_host, int M, const double* r_host, double hv_pf) {
   return omb_plan_ehvi_mc(ctx, 3, cache_host, M, r_host, hv_pf);
 }
 
-int omb_plan_ehvi_boxes(omb_ctx* ctx, int k, const double* coords_host, int C, const uint16_t* boxes_host, int B) {
-  void* h = nullptr;
-  int rc = enter(ctx);
+// omb_plan_ehvi_boxes (kd false) and omb_plan_ehvi_boxes_k (kd true: its kernel trusts the box indices)
+static int plan_boxes_entry(omb_ctx* ctx, bool kd, int k, const double* coords_host, int C, const uint16_t* boxes_host,
+                            int B) {
+  int rc = plan_enter(ctx);
   if (rc) return rc;
-  ctx->plan = Plan();
-  if ((rc = check_boxes(E(ctx), k, C, B))) return rc;
-  if (!coords_host || !boxes_host) return fail(ctx, OMB_EINVAL, "null grid/box list");
-  const size_t cbytes = sizeof(double) * (size_t)k * C;
-  const size_t bbytes = sizeof(uint16_t) * 2 * (size_t)k * B;
-  if ((rc = plan_begin(ctx, cbytes + bbytes, &h))) return rc;
-  memcpy(h, coords_host, cbytes);
-  memcpy(static_cast<char*>(h) + cbytes, boxes_host, bbytes);
-  if ((rc = stage_to_geo(ctx, cbytes + bbytes))) return rc;
   Plan pl;
-  pl.kind = PLAN_EHVI_BOXES;
-  pl.k = k;
-  pl.var_mask = all_objectives(k);
-  pl.C = C;
-  pl.B = B;
-  pl.geo = static_cast<const double*>(ctx->geo);
-  pl.boxes = reinterpret_cast<const uint16_t*>(static_cast<const char*>(ctx->geo) + cbytes);
-  ctx->plan = pl;
-  return OMB_OK;
+  if ((rc = describe_boxes(ctx, kd, k, C, B, &pl))) return rc;
+  if (!coords_host || !boxes_host) return fail(ctx, OMB_EINVAL, "null grid/box list");
+  if (kd && (rc = check_box_list(E(ctx), k, C, boxes_host, B))) return rc;
+  // the grid's bytes are a multiple of 8: the box list behind it stays 4-byte aligned
+  return install_plan(ctx, pl, coords_host, sizeof(double) * (size_t)k * C, boxes_host,
+                      sizeof(uint16_t) * 2 * (size_t)k * B);
+}
+
+int omb_plan_ehvi_boxes(omb_ctx* ctx, int k, const double* coords_host, int C, const uint16_t* boxes_host, int B) {
+  return plan_boxes_entry(ctx, false, k, coords_host, C, boxes_host, B);
 }
 
 int omb_plan_ehvi_boxes_k(omb_ctx* ctx, int k, const double* coords_host, int C, const uint16_t* boxes_host, int B) {
-  void* h = nullptr;
-  int rc = enter(ctx);
-  if (rc) return rc;
-  ctx->plan = Plan();
-  if ((rc = check_boxes_k(E(ctx), k, C, B))) return rc;
-  if (!coords_host || !boxes_host) return fail(ctx, OMB_EINVAL, "null grid/box list");
-  if ((rc = check_box_list(E(ctx), k, C, boxes_host, B))) return rc;
-  const size_t cbytes = sizeof(double) * (size_t)k * C;     // a multiple of 8: the box list stays 4-byte aligned
-  const size_t bbytes = sizeof(uint16_t) * 2 * (size_t)k * B;
-  if ((rc = plan_begin(ctx, cbytes + bbytes, &h))) return rc;
-  memcpy(h, coords_host, cbytes);
-  memcpy(static_cast<char*>(h) + cbytes, boxes_host, bbytes);
-  if ((rc = stage_to_geo(ctx, cbytes + bbytes))) return rc;
-  Plan pl;
-  pl.kind = PLAN_EHVI_BOXES;
-  pl.boxes_kd = true;
-  pl.k = k;
-  pl.var_mask = all_objectives(k);
-  pl.C = C;
-  pl.B = B;
-  pl.geo = static_cast<const double*>(ctx->geo);
-  pl.boxes = reinterpret_cast<const uint16_t*>(static_cast<const char*>(ctx->geo) + cbytes);
-  ctx->plan = pl;
-  return OMB_OK;
+  return plan_boxes_entry(ctx, true, k, coords_host, C, boxes_host, B);
 }
 
 int omb_plan_hvpoi(omb_ctx* ctx, const double* cells_host, int C) {
-  void* h = nullptr;
-  int rc = enter(ctx);
+  int rc = plan_enter(ctx);
   if (rc) return rc;
-  ctx->plan = Plan();
-  if ((rc = check_hvpoi(E(ctx), C))) return rc;
-  if (!cells_host) return fail(ctx, OMB_EINVAL, "null cells");
-  const size_t bytes = sizeof(double) * 4 * (size_t)C;
-  if ((rc = plan_begin(ctx, bytes, &h))) return rc;
-  memcpy(h, cells_host, bytes);
-  if ((rc = stage_to_geo(ctx, bytes))) return rc;
   Plan pl;
-  pl.kind = PLAN_HVPOI;
-  pl.k = 2;
-  pl.var_mask = 3u;
-  pl.C = C;
-  pl.geo = static_cast<const double*>(ctx->geo);
-  ctx->plan = pl;
-  return OMB_OK;
+  if ((rc = describe_hvpoi(ctx, C, &pl))) return rc;
+  if (!cells_host) return fail(ctx, OMB_EINVAL, "null cells");
+  return install_plan(ctx, pl, cells_host, sizeof(double) * 4 * (size_t)C);
 }
 
 int omb_plan_expdec(omb_ctx* ctx, int k, const double* cache_host, int M, int scal_id, const double* params_host,
                     const double* weights_host, const double* ideal_host, const double* max_host, double agg_min) {
-  void* h = nullptr;
-  int rc = enter(ctx);
+  int rc = plan_enter(ctx);
   if (rc) return rc;
-  ctx->plan = Plan();
-  ScalParams sp;
-  if ((rc = build_scal(E(ctx), k, M, scal_id, params_host, weights_host, ideal_host, max_host, agg_min, &sp))) return rc;
-  if (!cache_host) return fail(ctx, OMB_EINVAL, "null cache");
-  const size_t bytes = sizeof(double) * (size_t)k * M;
-  if ((rc = plan_begin(ctx, bytes, &h))) return rc;
-  memcpy(h, cache_host, bytes);
-  if ((rc = stage_to_geo(ctx, bytes))) return rc;
   Plan pl;
-  pl.kind = PLAN_EXPDEC;
-  pl.k = k;
-  pl.var_mask = 1u;   // expdec_kernel: σ²₀ for every objective
-  pl.M = M;
-  pl.sp = sp;
-  pl.geo = static_cast<const double*>(ctx->geo);
-  ctx->plan = pl;
-  return OMB_OK;
+  if ((rc = describe_expdec(ctx, k, M, scal_id, params_host, weights_host, ideal_host, max_host, agg_min, &pl)))
+    return rc;
+  if (!cache_host) return fail(ctx, OMB_EINVAL, "null cache");
+  return install_plan(ctx, pl, cache_host, sizeof(double) * (size_t)k * M);
 }
 
 int omb_plan_ei(omb_ctx* ctx, double best, double var_eps) {
@@ -1053,20 +1045,11 @@ int omb_plan_ei(omb_ctx* ctx, double best, double var_eps) {
 }
 
 int omb_plan_ei_ext(omb_ctx* ctx, int kind, int k, double best, double var_eps, double pof_eps) {
-  int rc = enter(ctx);
+  int rc = plan_enter(ctx);
   if (rc) return rc;
-  ctx->plan = Plan();
-  if ((rc = check_ei(E(ctx), kind, k, var_eps, pof_eps))) return rc;
   Plan pl;
-  pl.kind = PLAN_EI;
-  pl.ei_kind = kind;
-  pl.k = k;
-  // ei_kernel: EI of objective 0; the Pareto kind multiplies by μ₁, the constrained kind reads every σ²
-  pl.var_mask = kind == OMB_EI_CONSTRAINED ? all_objectives(k) : 1u;
-  pl.best = best;
-  pl.var_eps = var_eps;
-  pl.pof_eps = pof_eps;
-  ctx->plan = pl;
+  if ((rc = describe_ei(ctx, kind, k, best, var_eps, pof_eps, &pl))) return rc;
+  ctx->plan = pl;   // no geometry
   return OMB_OK;
 }
 
@@ -1134,13 +1117,13 @@ static int grad_ws(omb_ctx* ctx, const GPArgs& args, int n_obj, int64_t N, size_
     if (args.gp[o].n > *n_max) *n_max = args.gp[o].n;
   *Nc = grad_chunk(n_obj, *n_max, N);
   const size_t doubles = aux + (size_t)(n_obj + 2) * (size_t)*n_max * (size_t)*Nc;
-  return grow_dev(ctx, &ctx->gws, &ctx->gws_cap, doubles * sizeof(double), "gradient workspace");
+  return grow_dev(ctx, ctx->gws, doubles * sizeof(double), "gradient workspace");
 }
 
 static int grad_chain(omb_ctx* ctx, const GPArgs& args, int n_obj, int n_max, int64_t Nc, size_t aux,
                       const double* Xc, int64_t N, double* dmu, double* dvar, const double* dadm, const double* dadv,
                       const double* vals, double* grad) {
-  double* Kst = static_cast<double*>(ctx->gws) + aux;
+  double* Kst = ctx->gws.as<double>() + aux;
   double* V = Kst + (size_t)n_max * Nc;
   double* W = V + (size_t)n_max * Nc;
   GradArgs ga;
@@ -1195,12 +1178,7 @@ int omb_eval_grad(omb_ctx* ctx, const double* Xc_dev, int64_t N, double* vals_de
   if ((rc = check_eval_grad(E(ctx), Xc_dev, N, vals_dev, grad_dev))) return rc;
   const Plan pl = ctx->plan;
   if (pl.kind == PLAN_NONE) return fail(ctx, OMB_ESTATE, "no acquisition plan (call an omb_plan_* function)");
-  const char* unsup = nullptr;
-  if (pl.kind == PLAN_EHVI_MC) unsup = "Monte-Carlo EHVI";
-  if (pl.kind == PLAN_EXPDEC) unsup = "expected decomposition";
-  if (pl.kind == PLAN_HVPOI) unsup = "HV-PoI";
-  if (pl.kind == PLAN_EHVI2D && pl.mode == OMB_EHVI_SIGMA) unsup = "EHVI-2D in OMB_EHVI_SIGMA mode";
-  if (unsup) return fail(ctx, OMB_EUNSUP, "the %s plan has no analytic gradient", unsup);
+  if ((rc = launch_acq_grad(ctx, pl, nullptr, nullptr, 0, nullptr, nullptr))) return rc;   // a plan without a gradient
   GPArgs args;
   int max_R = 0;
   const int k = pl.k, K = pl.k + pl.n_con;   // the constraint models' rows follow the objectives'
@@ -1212,33 +1190,20 @@ int omb_eval_grad(omb_ctx* ctx, const double* Xc_dev, int64_t N, double* vals_de
   int64_t Nc = 0;
   int n_max = 0;
   if ((rc = grad_ws(ctx, args, K, N, aux, &Nc, &n_max))) return rc;
-  double* dadm = static_cast<double*>(ctx->gws);
+  double* dadm = ctx->gws.as<double>();
   double* dadv = dadm + (size_t)K * (size_t)N;
   double* acq_raw = pl.n_con ? dadv + (size_t)K * (size_t)N : nullptr;
   // the value: omb_eval's own chain, so vals_dev is bitwise omb_eval's; it leaves μ | σ² (K, N) in ctx->work
   // (every σ²: the gradient kernels below read them all)
   if ((rc = run_chain(ctx, Xc_dev, false, 0, N, 0, vals_dev, nullptr, true, acq_raw))) return rc;
-  const double* mu = static_cast<const double*>(ctx->work);
+  const double* mu = ctx->work.as<const double>();
   const double* var = mu + (size_t)K * (size_t)N;
-  hipError_t e;
-  switch (pl.kind) {
-    case PLAN_EHVI2D:
-      e = launch_ehvi2d_grad(ctx->stream, mu, var, N, N, pl.geo, pl.P, pl.r[0], pl.r[1], pl.s00, pl.s01, pl.mode, dadm,
-                             dadv);
-      break;
-    case PLAN_EHVI_BOXES:
-      e = launch_ehvi_boxes_grad(ctx->stream, k, mu, var, N, N, pl.geo, pl.C, pl.boxes, pl.B, dadm, dadv);
-      break;
-    case PLAN_EI:
-      e = launch_ei_grad(ctx->stream, pl.ei_kind, k, mu, var, N, N, pl.best, pl.var_eps, pl.pof_eps, dadm, dadv);
-      break;
-    default:
-      return fail(ctx, OMB_ESTATE, "corrupt plan");
+  if ((rc = launch_acq_grad(ctx, pl, mu, var, N, dadm, dadv))) return rc;
+  if (pl.n_con) {
+    hipError_t e = launch_pof_grad(ctx->stream, acq_raw, mu + (size_t)k * (size_t)N, var + (size_t)k * (size_t)N, N, N,
+                                   k, pl.n_con, pl.con_eps, dadm, dadv);
+    if (e != hipSuccess) return hip_fail(ctx, e, "acquisition gradient");
   }
-  if (e == hipSuccess && pl.n_con)
-    e = launch_pof_grad(ctx->stream, acq_raw, mu + (size_t)k * (size_t)N, var + (size_t)k * (size_t)N, N, N, k,
-                        pl.n_con, pl.con_eps, dadm, dadv);
-  if (e != hipSuccess) return hip_fail(ctx, e, "acquisition gradient");
   return grad_chain(ctx, args, K, n_max, Nc, aux, Xc_dev, N, nullptr, nullptr, dadm, dadv, vals_dev, grad_dev);
 }
 
@@ -1348,10 +1313,10 @@ static hipError_t cov_build(omb_ctx* ctx, const ObjState& s, const double* Xc, i
 // synchronises and reads it.
 // The factorisation workspace: [info int | pad to 16 B | factor workspace (chol_ws_doubles)]
 static int chol_workspace(omb_ctx* ctx, int64_t N, int** dinfo, double** ws) {
-  int rc = grow_dev(ctx, &ctx->ichol, &ctx->ichol_cap, 16 + sizeof(double) * chol_ws_doubles(N), "Cholesky workspace");
+  int rc = grow_dev(ctx, ctx->ichol, 16 + sizeof(double) * chol_ws_doubles(N), "Cholesky workspace");
   if (rc) return rc;
-  *dinfo = static_cast<int*>(ctx->ichol);
-  *ws = reinterpret_cast<double*>(static_cast<char*>(ctx->ichol) + 16);
+  *dinfo = ctx->ichol.as<int>();
+  *ws = reinterpret_cast<double*>(ctx->ichol.as<char>() + 16);
   return OMB_OK;
 }
 
@@ -1393,9 +1358,8 @@ int omb_posterior_cov(omb_ctx* ctx, int obj, const double* Xc_dev, int64_t N, do
   const ObjState& s = ctx->obj[obj];
   const size_t nN = (size_t)s.n * N;
   const size_t cw = (size_t)cand_cov_ws_doubles(N, s.DP);
-  if ((rc = grow_dev(ctx, &ctx->tws, &ctx->tws_cap, sizeof(double) * (2 * nN + N + cw), "covariance workspace")))
-    return rc;
-  double* Kst = static_cast<double*>(ctx->tws);
+  if ((rc = grow_dev(ctx, ctx->tws, sizeof(double) * (2 * nN + N + cw), "covariance workspace"))) return rc;
+  double* Kst = ctx->tws.as<double>();
   double* V = Kst + nN;
   double* var = V + nN;
   double* cws = var + N;
@@ -1438,8 +1402,8 @@ int omb_posterior_samples(omb_ctx* ctx, int obj, const double* Xc_dev, int64_t N
   const size_t cw = (size_t)cand_cov_ws_doubles(N, s.DP);
   const size_t sw = (size_t)chol_samples_ws_doubles(N, B);
   const size_t doubles = 2 * nN + 2 * (size_t)N + (size_t)N * N + (cw > sw ? cw : sw);
-  if ((rc = grow_dev(ctx, &ctx->tws, &ctx->tws_cap, sizeof(double) * doubles, "sampling workspace"))) return rc;
-  double* Kst = static_cast<double*>(ctx->tws);
+  if ((rc = grow_dev(ctx, ctx->tws, sizeof(double) * doubles, "sampling workspace"))) return rc;
+  double* Kst = ctx->tws.as<double>();
   double* V = Kst + nN;
   double* mu = V + nN;
   double* var = mu + N;
@@ -1492,8 +1456,8 @@ int omb_thompson_select(omb_ctx* ctx, const double* Y_dev, int B, int64_t N, int
   if (B > 0 && (!Y_dev || !idx_dev)) return fail(ctx, OMB_EINVAL, "null device pointer");
   if (B == 0) return OMB_OK;
   const size_t sw = (size_t)select_ws_bytes(B, N);
-  if (sw && (rc = grow_dev(ctx, &ctx->sws, &ctx->sws_cap, sw, "selection workspace"))) return rc;
-  hipError_t e = launch_select(ctx->stream, Y_dev, B, N, idx_dev, ctx->sws, ctx->select_seq);
+  if (sw && (rc = grow_dev(ctx, ctx->sws, sw, "selection workspace"))) return rc;
+  hipError_t e = launch_select(ctx->stream, Y_dev, B, N, idx_dev, ctx->sws.p, ctx->select_seq);
   if (e != hipSuccess) return hip_fail(ctx, e, "thompson_select");
   return OMB_OK;
 }
@@ -1524,9 +1488,9 @@ static int gp_factor(omb_ctx* ctx, int kernel, int n, int d, const double* X, co
   const size_t nn = (size_t)n * n;
   const size_t doubles = 3 * nn + 64 * (size_t)n + 2 * (size_t)n + DP +
                          (size_t)gp_grad_blocks(n) * (DP + 1) + DP + 5 + (size_t)cand_cov_ws_doubles(n, DP);
-  int rc = grow_dev(ctx, &ctx->fws, &ctx->fws_cap, sizeof(double) * doubles, "GP fit workspace");
+  int rc = grow_dev(ctx, ctx->fws, sizeof(double) * doubles, "GP fit workspace");
   if (rc) return rc;
-  double* p = static_cast<double*>(ctx->fws);
+  double* p = ctx->fws.as<double>();
   f->Ky = p; p += nn;
   f->Linv = p; p += nn;
   f->Kinv = p; p += nn;
@@ -1835,8 +1799,7 @@ int omb_ea_search(omb_ctx* ctx, int mode, double best, double var_eps, const dou
   if (!(var_eps >= 0.0)) return fail(ctx, OMB_EINVAL, "var_eps=%g must be >= 0", var_eps);
   if (!pop_dev || !lower_dev || !upper_dev || !out_dev || (iters > 0 && (!sel_dev || !cross_dev || !beta_dev || !mut_dev)))
     return fail(ctx, OMB_EINVAL, "null device pointer");
-  if ((rc = grow_dev(ctx, &ctx->ews, &ctx->ews_cap, sizeof(double) * (size_t)s0.n * s0.n, "search workspace")))
-    return rc;
+  if ((rc = grow_dev(ctx, ctx->ews, sizeof(double) * (size_t)s0.n * s0.n, "search workspace"))) return rc;
   EASearch es{};
   es.g0 = s0.dev;
   es.g1 = (mode == OMB_EA_PARETO_EI) ? ctx->obj[1].dev : s0.dev;
@@ -1856,7 +1819,7 @@ int omb_ea_search(omb_ctx* ctx, int mode, double best, double var_eps, const dou
   es.lower = lower_dev;
   es.upper = upper_dev;
   es.out = out_dev;
-  hipError_t e = launch_ea_search(ctx->stream, es, static_cast<double*>(ctx->ews));
+  hipError_t e = launch_ea_search(ctx->stream, es, ctx->ews.as<double>());
   if (e != hipSuccess) return hip_fail(ctx, e, "ea_search");
   return OMB_OK;
 }

@@ -12,6 +12,11 @@ import torch
 from . import _lib
 
 
+_KERNEL_IDS = {"matern52": _lib.KERNEL_MATERN52, "rbf": _lib.KERNEL_RBF}
+_EHVI_MODES = {"reference": _lib.EHVI_REFERENCE, "textbook": _lib.EHVI_TEXTBOOK, "sigma": _lib.EHVI_SIGMA}
+_EI_KINDS = {"plain": _lib.EI_PLAIN, "pareto": _lib.EI_PARETO, "constrained": _lib.EI_CONSTRAINED}
+
+
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
@@ -55,6 +60,15 @@ class AcqContext:
             self._check(self.lib.omb_set_stream(self._h, ctypes.c_void_p(s)), "omb_set_stream")
             self._cur_stream = s
 
+    def _out(self, out, shape, dtype=torch.float64):
+        return out if out is not None else torch.empty(shape, dtype=dtype, device=self.device)
+
+    def _boxes_dev(self, boxes):
+        if isinstance(boxes, torch.Tensor):
+            return boxes
+        # uint16 indices < 32768 travel as int16 (torch has no uint16 on every build)
+        return torch.as_tensor(np.ascontiguousarray(boxes, dtype=np.uint16).view(np.int16), device=self.device)
+
     def close(self):
         if getattr(self, "_h", None):
             self.lib.omb_destroy(self._h)
@@ -84,14 +98,9 @@ class AcqContext:
         ("posterior_mean_kernel", 0/1/2) computes those objectives' mean inside the posterior launch / in a kernel
         of its own after it (default) / in that kernel before it (bit-identical values); ("paths_libcos", 0/1)
         evaluates the sample paths' features with the kernel's own cosine (default) / the device library's."""
-        code = {"spin_limit": _lib.DEBUG_SPIN_LIMIT, "cov_table": _lib.DEBUG_COV_TABLE,
-                "fused_chain": _lib.DEBUG_FUSED_CHAIN, "argmax_passes": _lib.DEBUG_ARGMAX_PASSES,
-                "chol_mode": _lib.DEBUG_CHOL_MODE, "timing_stride": _lib.DEBUG_TIMING_STRIDE,
-                "cov_fused": _lib.DEBUG_COV_FUSED,
-                "select_seq": _lib.DEBUG_SELECT_SEQ, "syrk_glds": _lib.DEBUG_SYRK_GLDS,
-                "boxes_kd": _lib.DEBUG_BOXES_KD, "posterior_all_var": _lib.DEBUG_POSTERIOR_ALL_VAR,
-                "posterior_mean_kernel": _lib.DEBUG_POSTERIOR_MEAN_KERNEL,
-                "paths_libcos": _lib.DEBUG_PATHS_LIBCOS}[what]
+        code = getattr(_lib, "DEBUG_" + str(what).upper(), None)
+        if code is None:
+            raise KeyError(what)
         self._check(self.lib.omb_debug_set(self._h, code, int(value)), "omb_debug_set")
 
     # ------------------------------------------------------------------ GP state
@@ -105,10 +114,9 @@ class AcqContext:
         if Linv.shape != (n, n) or alpha.shape[0] != n:
             raise ValueError(f"set_gp: shapes X{tuple(X.shape)} alpha{tuple(alpha.shape)} Linv{tuple(Linv.shape)}")
         ls = np.broadcast_to(np.asarray(lengthscale, np.float64), (d,))
-        kid = {"matern52": _lib.KERNEL_MATERN52, "rbf": _lib.KERNEL_RBF}[kernel]
         self._stream()
-        self._check(self.lib.omb_set_gp(self._h, obj, kid, n, d, _ptr(X), _lib.darr(ls), float(variance),
-                                        _ptr(alpha), _ptr(Linv)), "omb_set_gp")
+        self._check(self.lib.omb_set_gp(self._h, obj, _KERNEL_IDS[kernel], n, d, _ptr(X), _lib.darr(ls),
+                                        float(variance), _ptr(alpha), _ptr(Linv)), "omb_set_gp")
         self._gp_keep[obj] = (X, alpha, Linv)
         self.gp_info[obj] = dict(n=n, d=d, variance=float(variance), kernel=kernel)
 
@@ -132,7 +140,7 @@ class AcqContext:
         self._check_width(Xc, obj)
         n = self.gp_info[obj]["n"]
         N = Xc.shape[0]
-        K = out if out is not None else torch.empty((n, N), dtype=torch.float64, device=self.device)
+        K = self._out(out, (n, N))
         self._stream()
         self._check(self.lib.omb_kernel_block(self._h, obj, _ptr(Xc), N, _ptr(K)), "omb_kernel_block")
         return K
@@ -143,11 +151,7 @@ class AcqContext:
         self._check_width(Xc)
         n_obj = n_obj if n_obj is not None else len(self.gp_info)
         N = Xc.shape[0]
-        if out is None:
-            mu = torch.empty((n_obj, N), dtype=torch.float64, device=self.device)
-            var = torch.empty_like(mu)
-        else:
-            mu, var = out
+        mu, var = out if out is not None else (self._out(None, (n_obj, N)), self._out(None, (n_obj, N)))
         self._stream()
         self._check(self.lib.omb_posterior(self._h, n_obj, _ptr(Xc), N, _ptr(mu), _ptr(var)), "omb_posterior")
         return mu, var
@@ -156,11 +160,11 @@ class AcqContext:
     def ehvi2d(self, mu, var, pf_sorted, r, s00, s01, mode="reference", out=None):
         N = mu.shape[1]
         pf = _dev_f64(pf_sorted, self.device)
-        out = out if out is not None else torch.empty(N, dtype=torch.float64, device=self.device)
-        m = {"reference": _lib.EHVI_REFERENCE, "textbook": _lib.EHVI_TEXTBOOK, "sigma": _lib.EHVI_SIGMA}[mode]
+        out = self._out(out, N)
         self._stream()
         self._check(self.lib.omb_ehvi2d(self._h, _ptr(mu), _ptr(var), mu.stride(0), N, _ptr(pf), pf.shape[0],
-                                        _lib.darr(r), float(s00), float(s01), m, _ptr(out)), "omb_ehvi2d")
+                                        _lib.darr(r), float(s00), float(s01), _EHVI_MODES[mode], _ptr(out)),
+                    "omb_ehvi2d")
         return out
 
     def ehvi_mc(self, mu, var, cache, r, hv_pf, out=None, raised=None):
@@ -170,8 +174,8 @@ class AcqContext:
         cache = _dev_f64(cache, self.device)
         if cache.dim() != 2 or not 2 <= cache.shape[1] <= mu.shape[0] or len(r) != cache.shape[1]:
             raise ValueError(f"ehvi_mc: cache {tuple(cache.shape)}, r of {len(r)}, mu {tuple(mu.shape)} disagree on k")
-        out = out if out is not None else torch.empty(N, dtype=torch.float64, device=self.device)
-        raised = raised if raised is not None else torch.empty(N, dtype=torch.int32, device=self.device)
+        out = self._out(out, N)
+        raised = self._out(raised, N, torch.int32)
         self._stream()
         self._check(self.lib.omb_ehvi_mc(self._h, cache.shape[1], _ptr(mu), _ptr(var), mu.stride(0), N, _ptr(cache),
                                          cache.shape[0], _lib.darr(r), float(hv_pf), _ptr(out), _ptr(raised)),
@@ -181,8 +185,8 @@ class AcqContext:
     def ehvi3d_mc(self, mu, var, cache, r, hv_pf, out=None, raised=None):
         N = mu.shape[1]
         cache = _dev_f64(cache, self.device)
-        out = out if out is not None else torch.empty(N, dtype=torch.float64, device=self.device)
-        raised = raised if raised is not None else torch.empty(N, dtype=torch.int32, device=self.device)
+        out = self._out(out, N)
+        raised = self._out(raised, N, torch.int32)
         self._stream()
         self._check(self.lib.omb_ehvi3d_mc(self._h, _ptr(mu), _ptr(var), mu.stride(0), N, _ptr(cache), cache.shape[0],
                                            _lib.darr(r), float(hv_pf), _ptr(out), _ptr(raised)), "omb_ehvi3d_mc")
@@ -193,11 +197,8 @@ class AcqContext:
         entry by k; True / False force omb_ehvi_boxes_k (any 2 ≤ k ≤ 8) / omb_ehvi_boxes (k ≤ 3)."""
         k, N = mu.shape
         coords = _dev_f64(coords, self.device)
-        if not isinstance(boxes, torch.Tensor):
-            # uint16 indices < 32768 travel as int16 (torch has no uint16 on every build)
-            b = np.ascontiguousarray(boxes, dtype=np.uint16)
-            boxes = torch.as_tensor(b.view(np.int16), device=self.device)
-        out = out if out is not None else torch.empty(N, dtype=torch.float64, device=self.device)
+        boxes = self._boxes_dev(boxes)
+        out = self._out(out, N)
         self._stream()
         # k = 2, 3: one wavefront per candidate; k >= 4: the candidate-blocked k-D kernel (omb_ehvi_boxes_k)
         fn = "omb_ehvi_boxes_k" if (k > 3 if kd is None else kd) else "omb_ehvi_boxes"
@@ -216,16 +217,14 @@ class AcqContext:
         coords = _dev_f64(coords, self.device)
         if coords.dim() != 2 or coords.shape[0] != k:
             raise ValueError(f"hvi_boxes: grid {tuple(coords.shape)} for k={k} objectives")
-        if not isinstance(boxes, torch.Tensor):
-            b = np.ascontiguousarray(boxes, dtype=np.uint16)
-            boxes = torch.as_tensor(b.view(np.int16), device=self.device)
+        boxes = self._boxes_dev(boxes)
         # a device list is read as it is: (B, 2k) 16-bit indices, or the kernel would walk past its end
         if boxes.dim() != 2 or boxes.shape[1] != 2 * k or boxes.element_size() != 2 or boxes.is_floating_point() \
                 or boxes.device != self.device or not boxes.is_contiguous():
             raise ValueError(f"hvi_boxes: the box list must be a contiguous (B, {2 * k}) 16-bit integer tensor on "
                              f"{self.device}, got {tuple(boxes.shape)} {boxes.dtype} on {boxes.device}")
         if out is None:
-            out = torch.empty(N, dtype=torch.float64, device=self.device)
+            out = self._out(None, N)
         elif out.dtype != torch.float64 or out.device != self.device or out.numel() < N or not out.is_contiguous():
             raise ValueError(f"hvi_boxes: out must be a contiguous fp64 tensor of at least {N} values on {self.device}")
         self._stream()
@@ -236,7 +235,7 @@ class AcqContext:
     def hvpoi(self, mu, var, cells, out=None):
         N = mu.shape[1]
         cells = _dev_f64(cells, self.device)
-        out = out if out is not None else torch.empty(N, dtype=torch.float64, device=self.device)
+        out = self._out(out, N)
         self._stream()
         self._check(self.lib.omb_hvpoi(self._h, _ptr(mu), _ptr(var), mu.stride(0), N, _ptr(cells), cells.shape[0],
                                        _ptr(out)), "omb_hvpoi")
@@ -245,7 +244,7 @@ class AcqContext:
     def expdec(self, mu, var, cache, scal_id, params, weights, ideal, max_point, agg_min, out=None):
         k, N = mu.shape
         cache = _dev_f64(cache, self.device)
-        out = out if out is not None else torch.empty(N, dtype=torch.float64, device=self.device)
+        out = self._out(out, N)
         self._stream()
         self._check(self.lib.omb_expdec(self._h, k, _ptr(mu), _ptr(var), mu.stride(0), N, _ptr(cache), cache.shape[0],
                                         int(scal_id), _lib.darr(params), _lib.darr(weights), _lib.darr(ideal),
@@ -256,7 +255,7 @@ class AcqContext:
         mu = mu.reshape(-1)
         var = var.reshape(-1)
         N = mu.shape[0]
-        out = out if out is not None else torch.empty(N, dtype=torch.float64, device=self.device)
+        out = self._out(out, N)
         self._stream()
         self._check(self.lib.omb_ei(self._h, _ptr(mu), _ptr(var), N, float(best), float(var_eps), _ptr(out)), "omb_ei")
         return out
@@ -264,11 +263,10 @@ class AcqContext:
     def ei_ext(self, kind, mu, var, best, var_eps=0.0, pof_eps=0.0, out=None):
         """EI family over rows 0..k-1 of (mu, var): kind "plain" | "pareto" (KEEP) | "constrained" (cParEGO)."""
         k, N = mu.shape
-        kid = {"plain": _lib.EI_PLAIN, "pareto": _lib.EI_PARETO, "constrained": _lib.EI_CONSTRAINED}[kind]
-        out = out if out is not None else torch.empty(N, dtype=torch.float64, device=self.device)
+        out = self._out(out, N)
         self._stream()
-        self._check(self.lib.omb_ei_ext(self._h, kid, k, _ptr(mu), _ptr(var), mu.stride(0), N, float(best),
-                                        float(var_eps), float(pof_eps), _ptr(out)), "omb_ei_ext")
+        self._check(self.lib.omb_ei_ext(self._h, _EI_KINDS[kind], k, _ptr(mu), _ptr(var), mu.stride(0), N,
+                                        float(best), float(var_eps), float(pof_eps), _ptr(out)), "omb_ei_ext")
         return out
 
     def feasibility(self, mu, var, pof_eps=1e-5, acq=None, out=None):
@@ -276,14 +274,14 @@ class AcqContext:
         (mu, var) (c, N) — constraint models, feasible where g ≤ 0 — times ``acq`` (N,) when given (``out`` may be
         ``acq``)."""
         c, N = mu.shape
-        out = out if out is not None else torch.empty(N, dtype=torch.float64, device=self.device)
+        out = self._out(out, N)
         self._stream()
         self._check(self.lib.omb_feasibility(self._h, c, _ptr(mu), _ptr(var), mu.stride(0), N, float(pof_eps),
                                              _ptr(acq) if acq is not None else None, _ptr(out)), "omb_feasibility")
         return out
 
     def argmax_dev(self, vals, offset=0, out=None):
-        out = out if out is not None else torch.empty(2, dtype=torch.float64, device=self.device)
+        out = self._out(out, 2)
         self._stream()
         self._check(self.lib.omb_argmax_dev(self._h, _ptr(vals), vals.numel(), int(offset), _ptr(out)), "omb_argmax_dev")
         return out
@@ -315,8 +313,8 @@ class AcqContext:
 
     def plan_ehvi2d(self, pf_sorted, r, s00, s01, mode="reference"):
         pf = np.ascontiguousarray(pf_sorted, dtype=np.float64).reshape(-1, 2)
-        m = {"reference": _lib.EHVI_REFERENCE, "textbook": _lib.EHVI_TEXTBOOK, "sigma": _lib.EHVI_SIGMA}[mode]
-        self._plan("omb_plan_ehvi2d", _lib.host_ptr(pf), pf.shape[0], _lib.darr(r), float(s00), float(s01), m, mode=mode)
+        self._plan("omb_plan_ehvi2d", _lib.host_ptr(pf), pf.shape[0], _lib.darr(r), float(s00), float(s01),
+                   _EHVI_MODES[mode], mode=mode)
 
     def plan_ehvi_mc(self, cache, r, hv_pf):
         """EHVI_3D's Monte-Carlo form for k = cache.shape[1] objectives (cache (M, k), r (k,))."""
@@ -348,8 +346,7 @@ class AcqContext:
         self._plan("omb_plan_ei", float(best), float(var_eps))
 
     def plan_ei_ext(self, kind, k, best, var_eps=0.0, pof_eps=0.0):
-        kid = {"plain": _lib.EI_PLAIN, "pareto": _lib.EI_PARETO, "constrained": _lib.EI_CONSTRAINED}[kind]
-        self._plan("omb_plan_ei_ext", kid, int(k), float(best), float(var_eps), float(pof_eps))
+        self._plan("omb_plan_ei_ext", _EI_KINDS[kind], int(k), float(best), float(var_eps), float(pof_eps))
 
     def plan_constraints(self, n_con, pof_eps=1e-5):
         """omb_plan_constraints: the plan that is set treats objective slots k..k+n_con-1 as constraint models
@@ -370,7 +367,7 @@ class AcqContext:
         self.sobol_dim = d
 
     def sobol(self, start, N, out=None):
-        out = out if out is not None else torch.empty((N, self.sobol_dim), dtype=torch.float64, device=self.device)
+        out = self._out(out, (N, self.sobol_dim))
         self._stream()
         self._check(self.lib.omb_sobol(self._h, int(start), int(N), _ptr(out)), "omb_sobol")
         return out
@@ -379,7 +376,7 @@ class AcqContext:
         Xc = _dev_f64(Xc, self.device)
         self._check_width(Xc)
         N = Xc.shape[0]
-        out = out if out is not None else torch.empty(N, dtype=torch.float64, device=self.device)
+        out = self._out(out, N)
         self._stream()
         self._check(self.lib.omb_eval(self._h, _ptr(Xc), N, _ptr(out)), "omb_eval")
         return out
@@ -415,14 +412,14 @@ class AcqContext:
     def eval_argmax(self, Xc, offset=0, out=None):
         Xc = _dev_f64(Xc, self.device)
         self._check_width(Xc)
-        out = out if out is not None else torch.empty(2, dtype=torch.float64, device=self.device)
+        out = self._out(out, 2)
         self._stream()
         self._check(self.lib.omb_eval_argmax(self._h, _ptr(Xc), Xc.shape[0], int(offset), _ptr(out)),
                     "omb_eval_argmax")
         return out
 
     def eval_argmax_sobol(self, start, N, out=None):
-        out = out if out is not None else torch.empty(2, dtype=torch.float64, device=self.device)
+        out = self._out(out, 2)
         self._stream()
         self._check(self.lib.omb_eval_argmax_sobol(self._h, int(start), int(N), _ptr(out)), "omb_eval_argmax_sobol")
         return out
@@ -439,7 +436,7 @@ class AcqContext:
         if y.shape[0] != n:
             raise ValueError(f"gp_lml_grad: y has {y.shape[0]} values for {n} inputs")
         ls = np.broadcast_to(np.asarray(lengthscale, np.float64), (d,))
-        kid = {"matern52": _lib.KERNEL_MATERN52, "rbf": _lib.KERNEL_RBF}[kernel]
+        kid = _KERNEL_IDS[kernel]
         lml, jit = ctypes.c_double(), ctypes.c_double()
         grad = (ctypes.c_double * (d + 2 if noise_grad else d + 1))()
         name = "omb_gp_lml_grad_noise" if noise_grad else "omb_gp_lml_grad"
@@ -461,7 +458,7 @@ class AcqContext:
             raise ValueError("gp_lml_grad_batch: every y needs one value per input row")
         ls = np.ascontiguousarray(np.broadcast_to(np.asarray(lengthscales, np.float64), (k, d)))
         var = np.ascontiguousarray(np.asarray(variances, np.float64).reshape(k))
-        kid = {"matern52": _lib.KERNEL_MATERN52, "rbf": _lib.KERNEL_RBF}[kernel]
+        kid = _KERNEL_IDS[kernel]
         yptr = (ctypes.c_void_p * k)(*[y.data_ptr() for y in ys])
         lml = np.zeros(k)
         grad = np.zeros((k, d + 2 if noise_grad else d + 1))
@@ -488,7 +485,7 @@ class AcqContext:
         y = _dev_f64(y, self.device).reshape(-1)
         n, d = X.shape
         ls = np.broadcast_to(np.asarray(lengthscale, np.float64), (d,))
-        kid = {"matern52": _lib.KERNEL_MATERN52, "rbf": _lib.KERNEL_RBF}[kernel]
+        kid = _KERNEL_IDS[kernel]
         jit = ctypes.c_double()
         self._stream()
         self._check(self.lib.omb_gp_fit_state(self._h, int(obj), kid, n, d, _ptr(X), _ptr(y), _lib.darr(ls),
@@ -528,8 +525,7 @@ class AcqContext:
         Xc = _dev_f64(Xc, self.device)
         self._check_width(Xc, obj)
         N = Xc.shape[0]
-        mu, cov = out if out is not None else (torch.empty(N, dtype=torch.float64, device=self.device),
-                                               torch.empty((N, N), dtype=torch.float64, device=self.device))
+        mu, cov = out if out is not None else (self._out(None, N), self._out(None, (N, N)))
         self._stream()
         self._check(self.lib.omb_posterior_cov(self._h, int(obj), _ptr(Xc), N, _ptr(mu), _ptr(cov)),
                     "omb_posterior_cov")
@@ -556,7 +552,7 @@ class AcqContext:
         B = Zt.shape[0]
         if Zt.dim() != 2 or Zt.shape[1] != N:
             raise ValueError(f"Zt must be (B, {N}), got {tuple(Zt.shape)}")
-        Y = out if out is not None else torch.empty((B, N), dtype=torch.float64, device=self.device)
+        Y = self._out(out, (B, N))
         used = ctypes.c_double()
         self._stream()
         self._check(self.lib.omb_posterior_samples(self._h, int(obj), _ptr(Xc), N, _ptr(Zt), B, float(jitter_rel),
@@ -568,7 +564,7 @@ class AcqContext:
         """TuRBO's greedy per-sample arg-min over Y (B, N) → indices (B,) int64 (device)."""
         Y = _dev_f64(Y, self.device)
         B, N = Y.shape
-        idx = out if out is not None else torch.empty(B, dtype=torch.int64, device=self.device)
+        idx = self._out(out, B, torch.int64)
         self._stream()
         self._check(self.lib.omb_thompson_select(self._h, _ptr(Y), B, N, _ptr(idx)), "omb_thompson_select")
         return idx
@@ -608,7 +604,7 @@ class AcqContext:
         n_obj = n_obj if n_obj is not None else len(self.gp_info)
         N = Xc.shape[0]
         if out is None:
-            out = torch.empty((n_obj, self._paths_S.get(0, 1), N), dtype=torch.float64, device=self.device)
+            out = self._out(None, (n_obj, self._paths_S.get(0, 1), N))
         else:
             # the kernel writes row (o·S + s) at pitch ld: any other layout would be written out of bounds
             S = self._paths_S.get(0)
