@@ -277,6 +277,36 @@ int omb_ei_ext(omb_ctx* ctx, int kind, int k, const double* mu_dev, const double
 int omb_feasibility(omb_ctx* ctx, int c, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
                     double pof_eps, const double* acq_dev /* may be NULL */, double* out_dev);
 
+/* ---- Log-space acquisitions (Ament et al. 2023).  The linear values above are exactly 0.0 in fp64 where the
+ * improvement lies more than ~38 σ away (Φ and φ underflow; EI's h(γ) = γΦ(γ) + φ(γ) is 0.0 at γ = −39): over such a
+ * region the arg-max returns the lowest index and every gradient is 0.  The logarithms below are finite there and
+ * keep their slope.  All three are written on
+ *   log h(t):  the direct log above t = −1;  −t²/2 − log√(2π) + log T(t) below, T = h/φ = 1 + t·R(t),
+ *              R = Φ/φ = sqrt(π/2)·erfcx(−t/√2);  the asymptotic series of T in 1/t² below t = −30
+ *   log Φ(t):  log1p(−Φ(−t)) above 0;  the direct log down to −1;  −t²/2 + log(erfcx(−t/√2)/2) below
+ * and agree with a 60-digit reference to a few 1e-16 of max(1, |value|).  Edge rules: a NaN moment gives
+ * NaN for that candidate only; −inf and NaN never win the arg-max.  Asynchronous. */
+/* log EI over omb_ei_ext's arguments, σ and γ formed exactly as there:
+ *   OMB_EI_PLAIN        log σ + log h(γ)
+ *   OMB_EI_CONSTRAINED  … + Σ_{c=1}^{k-1} log Φ(−μc / sqrt(σ²c + pof_eps))    (bitwise omb_log_feasibility over PLAIN)
+ * σ = 0 gives −inf (the log of omb_ei's 0), σ² + var_eps < 0 NaN.  Checks, in this order: omb_ei_ext's on
+ * (kind, k, var_eps, pof_eps); OMB_EUNSUP for OMB_EI_PARETO (μ₁·EI has no logarithm where μ₁ ≤ 0); omb_ei_ext's on
+ * the pointers, ld and N. */
+int omb_log_ei(omb_ctx* ctx, int kind, int k, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
+               double best, double var_eps, double pof_eps, double* out_dev);
+/* log of the exact EHVI: arguments, checks and limits are omb_ehvi_boxes_k's (2 ≤ k ≤ OMB_MAX_OBJ, boxes 4-byte
+ * aligned).  With lh = log h((coordinate − μ_j)/σ_j):
+ *   L_b = Σ_j [lh_hi + log(1 − e^(lh_lo − lh_hi))],   out = Σ_j log σ_j + logsumexp_b L_b
+ * (a lower index at the −∞ column contributes lh_hi alone).  The sum over boxes has one fixed order and no atomics:
+ * a candidate's value does not depend on N or its column.  σ²_j ≤ 0 gives NaN (the linear kernel: NaN below 0; at
+ * exactly 0 the log form is −inf + inf — take the log of omb_hvi_boxes, the σ → 0 limit). */
+int omb_log_ehvi_boxes(omb_ctx* ctx, int k, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
+                       const double* coords_dev, int C, const uint16_t* boxes_dev, int B, double* out_dev);
+/* out = acq + log F over omb_feasibility's arguments and checks (acq_dev NULL: out = log F; out_dev may be acq_dev):
+ * log F = ((0 + log Φ(z_0)) + log Φ(z_1)) + …, z_j and the order over j as there.  Finite where F is 0.0. */
+int omb_log_feasibility(omb_ctx* ctx, int c, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
+                        double pof_eps, const double* acq_dev /* may be NULL */, double* out_dev);
+
 /* Arg-max over vals_dev (N): lowest index among maxima, NaN and -inf never win
  * (replaces scipy differential_evolution(lambda x: -acq(x)), optimisers.py:87,118).
  * result_dev (2 doubles, device): {best value, best index + offset (as double)};
@@ -332,6 +362,21 @@ int omb_plan_ei_ext(omb_ctx* ctx, int kind, int k, double best, double var_eps, 
  * σ²_j + pof_eps < 0 gives NaN there as well. */
 int omb_plan_constraints(omb_ctx* ctx, int n_con, double pof_eps);
 
+/* The plan that is set returns the logarithm of its acquisition (on = 1) or the acquisition itself (on = 0, what
+ * every omb_plan_* call starts with: a new plan clears the flag).  Plans with a log form: omb_plan_ei,
+ * omb_plan_ei_ext with OMB_EI_PLAIN or OMB_EI_CONSTRAINED (omb_log_ei's value), omb_plan_ehvi_boxes and
+ * omb_plan_ehvi_boxes_k (omb_log_ehvi_boxes' value, one kernel for both).  It may come before or after
+ * omb_plan_constraints; with both, the chain adds log F (omb_log_feasibility) in place of the multiplication by F.
+ * The posterior's variance mask is the linear plan's.  Errors, in this order, each leaving the plan as it was:
+ * OMB_ESTATE with no plan; OMB_EINVAL for `on` outside {0, 1}; OMB_EUNSUP, naming the plan, for Pareto EI, EHVI-2D
+ * (any mode), Monte-Carlo EHVI, HV-PoI and expected decomposition.
+ * omb_eval_grad on a log plan: log EI (plain or constrained, with or without omb_plan_constraints) is analytic —
+ *   ∂/∂μ = −ρ/(σ + 1e-10),  ∂/∂σ² = (1/σ − ρ·γ/(σ + 1e-10))/(2σ),  ρ = Φ(γ)/h(γ) = R/T for γ < 0,
+ *   a constraint row: ∂ log Φ(z)/∂z = φ(z)/Φ(z) = 1/R(z) times ∂z/∂μ, ∂z/∂σ² —
+ * finite and non-zero where the linear gradient is 0; the NaN-row rule is kept.  The log exact EHVI returns
+ * OMB_EUNSUP, writes nothing and leaves the plan set. */
+int omb_plan_log(omb_ctx* ctx, int on);
+
 /* Scrambled Sobol' candidates generated on the device (replaces the host-side sampling that
  * feeds the maximiser; same sequence as scipy.stats.qmc.Sobol, which the reference uses for
  * its MC cache at optimisers.py:121-141).  sv_host (d, bits) and shift_host (d) are the
@@ -372,7 +417,8 @@ int omb_posterior_grad(omb_ctx* ctx, int n_obj, const double* Xc_dev, int64_t N,
  * OMB_EHVI_TEXTBOOK), omb_plan_ehvi_boxes, omb_plan_ehvi_boxes_k.  The Monte-Carlo EHVI, expected-decomposition
  * and HV-PoI plans (piecewise in the candidate) and EHVI-2D's OMB_EHVI_SIGMA mode return OMB_EUNSUP, write
  * nothing and leave the plan set; no plan is OMB_ESTATE, as for omb_eval.  Where the value is NaN, every gradient
- * entry of that candidate is NaN; no other candidate is affected. */
+ * entry of that candidate is NaN; no other candidate is affected.  Under omb_plan_log: see there (log EI is
+ * differentiated, the log exact EHVI is OMB_EUNSUP). */
 int omb_eval_grad(omb_ctx* ctx, const double* Xc_dev, int64_t N, double* vals_dev, double* grad_dev);
 
 /* Device timing of the fused chain (HIP events on the context's stream), up to 4096 chains.

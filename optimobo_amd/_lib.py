@@ -65,6 +65,10 @@ SIGNATURES = {
     "omb_ei": (_i, [_p, _p, _p, _i64, _d, _d, _p]),
     "omb_ei_ext": (_i, [_p, _i, _i, _p, _p, _i64, _i64, _d, _d, _d, _p]),
     "omb_feasibility": (_i, [_p, _i, _p, _p, _i64, _i64, _d, _p, _p]),
+    # log-space acquisitions
+    "omb_log_ei": (_i, [_p, _i, _i, _p, _p, _i64, _i64, _d, _d, _d, _p]),
+    "omb_log_ehvi_boxes": (_i, [_p, _i, _p, _p, _i64, _i64, _p, _i, _p, _i, _p]),
+    "omb_log_feasibility": (_i, [_p, _i, _p, _p, _i64, _i64, _d, _p, _p]),
     "omb_argmax_dev": (_i, [_p, _p, _i64, _i64, _p]),
     "omb_argmax": (_i, [_p, _p, _i64, _i64, _dp, ctypes.POINTER(_i64)]),
     # fused chain (host pointers for plan geometry)
@@ -78,6 +82,7 @@ SIGNATURES = {
     "omb_plan_ei": (_i, [_p, _d, _d]),
     "omb_plan_ei_ext": (_i, [_p, _i, _i, _d, _d, _d]),
     "omb_plan_constraints": (_i, [_p, _i, _d]),
+    "omb_plan_log": (_i, [_p, _i]),
     "omb_set_sobol": (_i, [_p, _i, _i, _p, _p, _dp, _dp]),
     "omb_sobol": (_i, [_p, _i64, _i64, _p]),
     "omb_eval": (_i, [_p, _p, _i64, _p]),

@@ -315,6 +315,30 @@ class AcquisitionEngine:
         mu, var = self.posterior(Xc)
         return self.ctx.feasibility(mu[self.n_obj - n_con:], var[self.n_obj - n_con:], float(pof_eps))
 
+    # log-space forms: finite, with a slope, where the values above are exactly 0.0 (AcqContext.log_ei, …)
+    def log_ei(self, Xc, best, var_eps=0.0):
+        mu, var = self.posterior(Xc)
+        return self.ctx.log_ei(mu[:1], var[:1], float(best), float(var_eps))
+
+    def log_constrained_ei(self, Xc, best, var_eps=0.0, pof_eps=1e-5):
+        """log of ``constrained_ei``; models = [aggregate, constraint_1, ...]."""
+        mu, var = self.posterior(Xc)
+        return self.ctx.log_ei(mu, var, float(best), float(var_eps), float(pof_eps), kind="constrained")
+
+    def log_ehvi_exact(self, Xc, max_point, PF, max_boxes=1 << 20):
+        """log of ``ehvi_exact`` (2 to 8 objectives)."""
+        mu, var = self.posterior(Xc)
+        coords, _, boxes = pareto.box_decomposition(PF, max_point, max_boxes=max_boxes)
+        return self.ctx.log_ehvi_boxes(mu, var, coords, boxes)
+
+    def log_feasibility(self, Xc, n_con, pof_eps=1e-5):
+        """log of ``feasibility``: finite where every candidate's probability of feasibility is 0.0."""
+        n_con = int(n_con)
+        if not 1 <= n_con <= self.n_obj:
+            raise ValueError(f"log_feasibility: n_con={n_con} outside [1, {self.n_obj}] loaded models")
+        mu, var = self.posterior(Xc)
+        return self.ctx.log_feasibility(mu[self.n_obj - n_con:], var[self.n_obj - n_con:], float(pof_eps))
+
     # ------------------------------------------------------------------ plans (fused chain)
     # One plan per BO iteration; each candidate batch is then a single omb_eval_argmax_sobol
     # (Sobol generation → posterior → acquisition → arg-max on the device).
@@ -354,6 +378,13 @@ class AcquisitionEngine:
         without constraints.  ``condition`` appends to every loaded model, so a believer batch conditions the
         constraint GPs on the fantasy points as well (their σ² shrinks there, their μ stays)."""
         self.ctx.plan_constraints(int(n_con), float(pof_eps))
+
+    def plan_log(self, on=True):
+        """The plan just set returns the logarithm of its acquisition (``plan_ei``, ``plan_constrained_ei``,
+        ``plan_ehvi_exact``; OMBError OMB_EUNSUP for the others) and ``plan_constraints`` adds log F.  Before or
+        after ``plan_constraints``; every plan starts linear.  ``maximise`` and the polishes work on the sign-free
+        value as they are; ``has_gradient`` is False for the log exact EHVI, so ``polish="auto"`` takes the stencil."""
+        self.ctx.plan_log(on)
 
     # ------------------------------------------------------------------ maximiser
     def score(self, acq_fn, X):

@@ -33,7 +33,7 @@ class BODriver:
 
     def __init__(self, test_problem, ideal_point=None, max_point=None, mode="reference", n_candidates=1 << 14,
                  refine_rounds=2, seed=None, device=None, polish=True, starts=None, noise=0.0, batch_size=1,
-                 constraints=None, batch_strategy="believer", thompson_sampler="joint"):
+                 constraints=None, batch_strategy="believer", thompson_sampler="joint", log_acquisition=False):
         self.test_problem = test_problem
         self.max_point = max_point
         self.ideal_point = ideal_point
@@ -81,7 +81,11 @@ class BODriver:
         if thompson_sampler == "paths" and self.batch_strategy != "thompson":
             raise ValueError("thompson_sampler='paths' needs batch_strategy='thompson'")
         self.thompson_sampler = thompson_sampler
-        self.thompson_fallbacks = 0    # Thompson iterations that fell back to the believer batch
+        # maximise the logarithm of the acquisition (not in the reference): EI and the exact EHVI are exactly 0.0 in
+        # fp64 over most of a late-run box, where their logarithms still rank the candidates and have a slope
+        # (AcquisitionEngine.plan_log).  False is the linear path, call for call.
+        self.log_acquisition = self._check_log_acquisition(log_acquisition)
+        self.thompson_fallbacks = 0   # Thompson iterations that fell back to the believer batch
         self._iteration = 0
 
     def _check_batch_strategy(self, batch_strategy):
@@ -95,6 +99,23 @@ class BODriver:
             raise ValueError("batch_strategy='thompson' does not support constraints='pof' (supported: "
                              "constraints=None; 'believer' batches take constraints='pof')")
         return batch_strategy
+
+    # log_acquisition=True: MonoSurrogateOptimiser (EI) and MultiSurrogateOptimiser in textbook mode (exact EHVI)
+    _log_acquisition_modes = None
+
+    def _check_log_acquisition(self, log_acquisition):
+        if not isinstance(log_acquisition, (bool, np.bool_)):
+            raise ValueError(f"log_acquisition must be True or False, not {log_acquisition!r}")
+        if not log_acquisition:
+            return False
+        modes = self._log_acquisition_modes
+        if modes is None:
+            raise ValueError(f"{type(self).__name__} does not support log_acquisition=True (MonoSurrogateOptimiser's "
+                             "EI and MultiSurrogateOptimiser's exact EHVI in mode='textbook' have a log form)")
+        if self.mode not in modes:
+            raise ValueError(f"log_acquisition=True needs mode in {modes} on {type(self).__name__} (mode={self.mode!r} "
+                             "plans an acquisition without a log form)")
+        return True
 
     def _check_constraints_option(self, constraints):
         if constraints is None:

@@ -32,6 +32,7 @@ class MultiSurrogateOptimiser(BODriver):
     exact_max_boxes = 1 << 17       # boxes of one iteration's exact EHVI at n_obj ≥ 4
     _pof_objective_models = "n_obj"
     _batch_strategies = ("believer", "thompson")
+    _log_acquisition_modes = ("textbook",)     # the exact EHVI over boxes; reference mode plans EHVI-2D / Monte-Carlo
 
     def _get_cached_samples(self, dimensions, sample_exponent):
         """optimisers.py:121-141 — scrambled Sobol mapped through the normal ppf."""
@@ -48,10 +49,16 @@ class MultiSurrogateOptimiser(BODriver):
     def _plan_EHVI(self, eng, function, max_point, pf, cache):
         """The EHVI plan of one proposal on ``eng``: 2-D, Monte-Carlo or exact, as mode and n_obj ask."""
         mc = function == "EHVI_3D" or self.n_obj >= 3          # optimisers.py:245-248: EHVI_3D for n_obj != 2
-        if mc and self.mode == "textbook" and self.n_obj <= 3:
+        if self.log_acquisition and self.n_obj <= 3:
+            # log_acquisition (textbook mode): the box form at k = 2 as well — EHVI-2D's stripes have no log kernel
+            eng.plan_ehvi_exact(max_point, pf)
+            eng.plan_log()
+        elif mc and self.mode == "textbook" and self.n_obj <= 3:
             eng.plan_ehvi_exact(max_point, pf)          # exact EHVI in place of the MC estimate (k = 2, 3)
         elif mc and self.mode == "textbook":
-            self._plan_exact_kd(eng, max_point, pf, cache)   # exact for 4 ≤ k ≤ 8 while the box budget allows
+            # exact for 4 ≤ k ≤ 8 while the box budget allows; an iteration on the Monte-Carlo fallback stays linear
+            if self._plan_exact_kd(eng, max_point, pf, cache) and self.log_acquisition:
+                eng.plan_log()
         elif mc:
             eng.plan_ehvi3d(max_point, pf, cache)       # the reference's Monte-Carlo form, any k ≥ 3
         else:
@@ -59,10 +66,10 @@ class MultiSurrogateOptimiser(BODriver):
 
     def _plan_exact_kd(self, eng, max_point, pf, cache):
         """Plans the exact EHVI at n_obj ≥ 4; when the box budget or the kernel's grid limit rules it out, the
-        Monte-Carlo plan stands in, after one RuntimeWarning per optimiser."""
+        Monte-Carlo plan stands in, after one RuntimeWarning per optimiser.  True when the exact plan is set."""
         try:
             eng.plan_ehvi_exact(max_point, pf, max_boxes=self.exact_max_boxes)
-            return
+            return True
         except ValueError as e:                          # box_decomposition: over the box budget
             reason = str(e)
         except OMBError as e:                            # omb_plan_ehvi_boxes_k: grid or box count past the kernel's
@@ -74,6 +81,7 @@ class MultiSurrogateOptimiser(BODriver):
             warnings.warn(f"exact EHVI unavailable at n_obj={self.n_obj} ({reason}); using the Monte-Carlo "
                           "estimate of the reference", RuntimeWarning, stacklevel=3)
         eng.plan_ehvi3d(max_point, pf, cache)
+        return False
 
     def _get_proposed_scalarisation(self, function, models, min_val, scalar_func, ref_dir, cache):
         """optimisers.py:62-88 on the device: returns (x, −value, ref_dir)."""
@@ -86,7 +94,12 @@ class MultiSurrogateOptimiser(BODriver):
     def solve(self, budget=100, n_init_samples=5, sample_exponent=5, acquisition_func=None):
         """``budget`` true evaluations.  With ``batch_size`` q > 1 they come in ⌈budget/q⌉ iterations of q proposals
         (the last one truncated), one ``hypervolume_convergence`` entry per iteration: see ``_solve_batched``.
-        With ``constraints="pof"``: ``_solve_pof``, which returns a ``Constrained_Res``."""
+        With ``constraints="pof"``: ``_solve_pof``, which returns a ``Constrained_Res``.
+        With ``log_acquisition=True`` (textbook mode, ``acquisition_func`` None) every pick maximises the logarithm
+        of the exact EHVI (plus log F under ``constraints="pof"``; log F alone while no row is feasible)."""
+        if self.log_acquisition and acquisition_func is not None:
+            raise ValueError("log_acquisition=True takes the exact EHVI (acquisition_func=None): the expected "
+                             "decomposition has no log form")
         if self.constraints == "pof":
             return self._solve_pof(budget, n_init_samples, sample_exponent, acquisition_func)
         if self.batch_strategy == "thompson" and acquisition_func is not None:
@@ -200,7 +213,8 @@ class MultiSurrogateOptimiser(BODriver):
                 ref_dir = np.asarray(ref_dirs[np.random.randint(0, len(ref_dirs))])
                 yfeas = yfant[self._feasible(gfant)]
                 if len(yfeas) == 0:
-                    x, _ = self._maximise(models, lambda Xd: eng.feasibility(Xd, c, self.pof_eps), eng=eng)
+                    pof = eng.log_feasibility if self.log_acquisition else eng.feasibility
+                    x, _ = self._maximise(models, lambda Xd: pof(Xd, c, self.pof_eps), eng=eng)
                 else:
                     if acquisition_func is None:
                         fn = "EHVI" if k == 2 else "EHVI_3D"
@@ -208,7 +222,7 @@ class MultiSurrogateOptimiser(BODriver):
                     else:
                         min_scalar = np.min([acquisition_func(y, ref_dir) for y in yfeas])
                         eng.plan_expected_decomposition(ref_dir, acquisition_func, min_scalar, cached_samples)
-                    eng.plan_constraints(c, self.pof_eps)
+                    eng.plan_constraints(c, self.pof_eps)     # a log plan (_plan_EHVI) keeps its flag: log F is added
                     x, _ = self._maximise(models, None, eng=eng)
                 picks.append(x)
                 if p + 1 < b:
@@ -227,6 +241,13 @@ class MonoSurrogateOptimiser(BODriver):
 
     _pof_objective_models = 1
     _batch_strategies = ("believer", "thompson")
+    _log_acquisition_modes = ("reference", "textbook")     # EI either way
+
+    def _plan_ei(self, eng, best):
+        """EI against ``best`` on ``eng``; its logarithm with ``log_acquisition``."""
+        eng.plan_ei(best, 0.0)
+        if self.log_acquisition:
+            eng.plan_log()
 
     def _expected_improvement(self, X, model, opt_value, kappa=0.01):
         """optimisers.py:325-344 (σ = sqrt(σ²)); X (d,) → (1,), X (N, d) → (N,)."""
@@ -238,7 +259,7 @@ class MonoSurrogateOptimiser(BODriver):
     def _get_proposed(self, function, models, current_best):
         from ..acquisition import engine_for
         eng = engine_for([models], self.device)
-        eng.plan_ei(current_best, 0.0)
+        self._plan_ei(eng, current_best)
         x, v = self._maximise([models], None)
         return x, -v
 
@@ -300,7 +321,7 @@ class MonoSurrogateOptimiser(BODriver):
             if picks is None:              # the believer batch (also a Thompson iteration's fallback)
                 picks = []
                 for p in range(b):
-                    eng.plan_ei(fant[np.argmin(fant)], 0.0)
+                    self._plan_ei(eng, fant[np.argmin(fant)])
                     x, _ = self._maximise([model], None, eng=eng)
                     picks.append(x)
                     if p + 1 < b:
@@ -339,9 +360,10 @@ class MonoSurrogateOptimiser(BODriver):
             for p in range(b):
                 ffeas = fant[self._feasible(gfant)]
                 if len(ffeas) == 0:
-                    x, _ = self._maximise(models, lambda Xd: eng.feasibility(Xd, c, self.pof_eps), eng=eng)
+                    pof = eng.log_feasibility if self.log_acquisition else eng.feasibility
+                    x, _ = self._maximise(models, lambda Xd: pof(Xd, c, self.pof_eps), eng=eng)
                 else:
-                    eng.plan_ei(ffeas[np.argmin(ffeas)], 0.0)
+                    self._plan_ei(eng, ffeas[np.argmin(ffeas)])
                     eng.plan_constraints(c, self.pof_eps)
                     x, _ = self._maximise(models, None, eng=eng)
                 picks.append(x)

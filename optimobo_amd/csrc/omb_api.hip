@@ -55,6 +55,9 @@ struct Plan {
   // the objectives only, and never in the chain's var_skip)
   int n_con = 0;
   double con_eps = 0;
+  // omb_plan_log: the value is the logarithm of the acquisition (PLAN_EI plain / constrained, PLAN_EHVI_BOXES), and the
+  // constraints' weight is added as log F.  var_mask is the linear plan's.
+  bool log = false;
 };
 
 // A device buffer that the context owns and grow_dev enlarges on demand.
@@ -320,6 +323,7 @@ hipError_t launch_acq(omb_ctx* ctx, const Plan& pl, const double* mu, const doub
     case PLAN_EHVI_MC:
       return launch_ehvi_mc(st, pl.k, mu, var, ld, N, pl.geo, pl.M, pl.r, pl.hv, out, raised);
     case PLAN_EHVI_BOXES:
+      if (pl.log) return launch_log_ehvi_boxes(st, pl.k, mu, var, ld, N, pl.geo, pl.C, pl.boxes, pl.B, out);
       return pl.boxes_kd ? launch_boxes_k(ctx, pl.k, mu, var, ld, N, pl.geo, pl.C, pl.boxes, pl.B, out)
                          : launch_ehvi_boxes(st, pl.k, mu, var, ld, N, pl.geo, pl.C, pl.boxes, pl.B, out);
     case PLAN_HVPOI:
@@ -327,6 +331,7 @@ hipError_t launch_acq(omb_ctx* ctx, const Plan& pl, const double* mu, const doub
     case PLAN_EXPDEC:
       return launch_expdec(st, pl.sp, mu, var, ld, N, pl.geo, pl.M, out);
     case PLAN_EI:
+      if (pl.log) return launch_log_ei(st, pl.ei_kind, pl.k, mu, var, ld, N, pl.best, pl.var_eps, pl.pof_eps, out);
       return launch_ei(st, pl.ei_kind, pl.k, mu, var, ld, N, pl.best, pl.var_eps, pl.pof_eps, out);
     default:
       return hipErrorInvalidValue;
@@ -348,10 +353,14 @@ int launch_acq_grad(omb_ctx* ctx, const Plan& pl, const double* mu, const double
         e = launch_ehvi2d_grad(st, mu, var, N, N, pl.geo, pl.P, pl.r[0], pl.r[1], pl.s00, pl.s01, pl.mode, dadm, dadv);
       break;
     case PLAN_EHVI_BOXES:
-      if (dadm) e = launch_ehvi_boxes_grad(st, pl.k, mu, var, N, N, pl.geo, pl.C, pl.boxes, pl.B, dadm, dadv);
+      if (pl.log) unsup = "log exact EHVI";   // a box-sum gradient in log space: not yet
+      else if (dadm) e = launch_ehvi_boxes_grad(st, pl.k, mu, var, N, N, pl.geo, pl.C, pl.boxes, pl.B, dadm, dadv);
       break;
     case PLAN_EI:
-      if (dadm) e = launch_ei_grad(st, pl.ei_kind, pl.k, mu, var, N, N, pl.best, pl.var_eps, pl.pof_eps, dadm, dadv);
+      if (dadm && pl.log)
+        e = launch_log_ei_grad(st, pl.ei_kind, pl.k, mu, var, N, N, pl.best, pl.var_eps, pl.pof_eps, dadm, dadv);
+      else if (dadm)
+        e = launch_ei_grad(st, pl.ei_kind, pl.k, mu, var, N, N, pl.best, pl.var_eps, pl.pof_eps, dadm, dadv);
       break;
     case PLAN_EHVI_MC: unsup = "Monte-Carlo EHVI"; break;
     case PLAN_EXPDEC: unsup = "expected decomposition"; break;
@@ -515,8 +524,8 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
       e = launch_acq(ctx, pl, mu, var, N, N, acq, raised);
     }
     if (e == hipSuccess && pl.n_con)
-      e = launch_pof_scale(ctx->stream, pl.n_con, mu + (size_t)k * nd, var + (size_t)k * nd, N, N, pl.con_eps, acq,
-                           vals);
+      e = (pl.log ? launch_log_pof : launch_pof_scale)(ctx->stream, pl.n_con, mu + (size_t)k * nd,
+                                                       var + (size_t)k * nd, N, N, pl.con_eps, acq, vals);
   }
   if (e == hipSuccess) e = mark(3);
   if (e == hipSuccess && result_dev && !acq_argmax)
@@ -867,16 +876,17 @@ int omb_ehvi3d_mc(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int
 // omb_ehvi_boxes (kd false) and omb_ehvi_boxes_k (kd true, whose kernel reads the box list in 4-byte words)
 static int ehvi_boxes_entry(omb_ctx* ctx, bool kd, int k, const double* mu_dev, const double* var_dev, int64_t ld,
                             int64_t N, const double* coords_dev, int C, const uint16_t* boxes_dev, int B,
-                            double* out_dev) {
+                            double* out_dev, bool log = false) {
   int rc = enter(ctx);
   if (rc) return rc;
   Plan pl;
   if ((rc = describe_boxes(ctx, kd, k, C, B, &pl))) return rc;
+  pl.log = log;
   if ((rc = check_moments(E(ctx), mu_dev, var_dev, ld, N, k, out_dev))) return rc;
   if (!coords_dev || !boxes_dev) return fail(ctx, OMB_EINVAL, "null grid/box list");
   if (kd && (reinterpret_cast<uintptr_t>(boxes_dev) & 3)) return fail(ctx, OMB_EINVAL, "box list not 4-byte aligned");
   return run_acq(ctx, pl, coords_dev, boxes_dev, mu_dev, var_dev, ld, N, out_dev, nullptr,
-                 kd ? "ehvi_boxes_k" : "ehvi_boxes");
+                 log ? "log_ehvi_boxes" : (kd ? "ehvi_boxes_k" : "ehvi_boxes"));
 }
 
 int omb_ehvi_boxes(omb_ctx* ctx, int k, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
@@ -887,6 +897,11 @@ int omb_ehvi_boxes(omb_ctx* ctx, int k, const double* mu_dev, const double* var_
 int omb_ehvi_boxes_k(omb_ctx* ctx, int k, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
                      const double* coords_dev, int C, const uint16_t* boxes_dev, int B, double* out_dev) {
   return ehvi_boxes_entry(ctx, true, k, mu_dev, var_dev, ld, N, coords_dev, C, boxes_dev, B, out_dev);
+}
+
+int omb_log_ehvi_boxes(omb_ctx* ctx, int k, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
+                       const double* coords_dev, int C, const uint16_t* boxes_dev, int B, double* out_dev) {
+  return ehvi_boxes_entry(ctx, true, k, mu_dev, var_dev, ld, N, coords_dev, C, boxes_dev, B, out_dev, true);
 }
 
 int omb_hvi_boxes(omb_ctx* ctx, int k, const double* y_dev, int64_t ld, int64_t N, const double* coords_dev, int C,
@@ -950,6 +965,29 @@ int omb_feasibility(omb_ctx* ctx, int c, const double* mu_dev, const double* var
   if (N == 0) return OMB_OK;
   hipError_t e = launch_pof_scale(ctx->stream, c, mu_dev, var_dev, ld, N, pof_eps, acq_dev, out_dev);
   if (e != hipSuccess) return hip_fail(ctx, e, "feasibility");
+  return OMB_OK;
+}
+
+int omb_log_ei(omb_ctx* ctx, int kind, int k, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
+               double best, double var_eps, double pof_eps, double* out_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  Plan pl;
+  if ((rc = check_log_ei(E(ctx), kind, k, var_eps, pof_eps))) return rc;
+  if ((rc = describe_ei(ctx, kind, k, best, var_eps, pof_eps, &pl))) return rc;
+  pl.log = true;
+  if ((rc = check_moments(E(ctx), mu_dev, var_dev, ld, N, k, out_dev))) return rc;
+  return run_acq(ctx, pl, nullptr, nullptr, mu_dev, var_dev, ld, N, out_dev, nullptr, "log_ei");
+}
+
+int omb_log_feasibility(omb_ctx* ctx, int c, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
+                        double pof_eps, const double* acq_dev, double* out_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if ((rc = check_feasibility(E(ctx), c, mu_dev, var_dev, ld, N, pof_eps, out_dev))) return rc;
+  if (N == 0) return OMB_OK;
+  hipError_t e = launch_log_pof(ctx->stream, c, mu_dev, var_dev, ld, N, pof_eps, acq_dev, out_dev);
+  if (e != hipSuccess) return hip_fail(ctx, e, "log_feasibility");
   return OMB_OK;
 }
 
@@ -1060,6 +1098,29 @@ int omb_plan_constraints(omb_ctx* ctx, int n_con, double pof_eps) {
   if ((rc = check_constraints(E(ctx), ctx->plan.kind == PLAN_NONE ? 0 : ctx->plan.k, n_con, pof_eps))) return rc;
   ctx->plan.n_con = n_con;
   ctx->plan.con_eps = n_con ? pof_eps : 0.0;
+  return OMB_OK;
+}
+
+// The plan kinds without a log form, by name (null: the plan has one).
+static const char* log_refused(const Plan& pl) {
+  switch (pl.kind) {
+    case PLAN_EI: return pl.ei_kind == OMB_EI_PARETO ? "Pareto EI" : nullptr;
+    case PLAN_EHVI_BOXES: return nullptr;
+    case PLAN_EHVI2D: return "EHVI-2D";
+    case PLAN_EHVI_MC: return "Monte-Carlo EHVI";
+    case PLAN_HVPOI: return "HV-PoI";
+    case PLAN_EXPDEC: return "expected decomposition";
+    default: return "unknown";
+  }
+}
+
+int omb_plan_log(omb_ctx* ctx, int on) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  // a failed call leaves the plan and its flag as they were
+  const bool has = ctx->plan.kind != PLAN_NONE;
+  if ((rc = check_plan_log(E(ctx), has, on, has ? log_refused(ctx->plan) : nullptr))) return rc;
+  ctx->plan.log = on != 0;
   return OMB_OK;
 }
 
@@ -1200,8 +1261,11 @@ int omb_eval_grad(omb_ctx* ctx, const double* Xc_dev, int64_t N, double* vals_de
   const double* var = mu + (size_t)K * (size_t)N;
   if ((rc = launch_acq_grad(ctx, pl, mu, var, N, dadm, dadv))) return rc;
   if (pl.n_con) {
-    hipError_t e = launch_pof_grad(ctx->stream, acq_raw, mu + (size_t)k * (size_t)N, var + (size_t)k * (size_t)N, N, N,
-                                   k, pl.n_con, pl.con_eps, dadm, dadv);
+    // a log plan adds log F: the objectives' rows stay, the constraints' rows get ∂ log F
+    hipError_t e = pl.log ? launch_log_pof_grad(ctx->stream, mu + (size_t)k * (size_t)N, var + (size_t)k * (size_t)N,
+                                                N, N, k, pl.n_con, pl.con_eps, dadm, dadv)
+                          : launch_pof_grad(ctx->stream, acq_raw, mu + (size_t)k * (size_t)N,
+                                            var + (size_t)k * (size_t)N, N, N, k, pl.n_con, pl.con_eps, dadm, dadv);
     if (e != hipSuccess) return hip_fail(ctx, e, "acquisition gradient");
   }
   return grad_chain(ctx, args, K, n_max, Nc, aux, Xc_dev, N, nullptr, nullptr, dadm, dadv, vals_dev, grad_dev);

@@ -188,6 +188,20 @@ int check_constraints(std::string* err, int plan_k, int n_con, double pof_eps) {
   return OMB_OK;
 }
 
+int check_plan_log(std::string* err, int has_plan, int on, const char* refused) {
+  if (!has_plan) return errf(err, OMB_ESTATE, "no acquisition plan to take the log of (call an omb_plan_* function first)");
+  if (on != 0 && on != 1) return errf(err, OMB_EINVAL, "on=%d outside {0, 1}", on);
+  if (refused) return errf(err, OMB_EUNSUP, "the %s plan has no log form", refused);
+  return OMB_OK;
+}
+
+int check_log_ei(std::string* err, int kind, int k, double var_eps, double pof_eps) {
+  int rc = check_ei(err, kind, k, var_eps, pof_eps);
+  if (rc) return rc;
+  if (kind == OMB_EI_PARETO) return errf(err, OMB_EUNSUP, "Pareto EI (mu_1 * EI) has no log form");
+  return OMB_OK;
+}
+
 int check_feasibility(std::string* err, int c, const void* mu, const void* var, int64_t ld, int64_t N, double pof_eps,
                       const void* out) {
   if (c < 1 || c > OMB_MAX_OBJ) return errf(err, OMB_EINVAL, "c=%d outside [1, %d]", c, OMB_MAX_OBJ);

@@ -57,6 +57,11 @@ int check_hvpoi(std::string* err, int C);
 // omb_plan_constraints on a plan over plan_k objectives (0: none set): OMB_ESTATE with no plan, OMB_EINVAL for
 // n_con < 0 or a negative / non-finite pof_eps, OMB_EUNSUP for plan_k + n_con > OMB_MAX_OBJ — in that order.
 int check_constraints(std::string* err, int plan_k, int n_con, double pof_eps);
+// omb_plan_log, in this order: OMB_ESTATE with no plan (has_plan 0), OMB_EINVAL for `on` outside {0, 1}, OMB_EUNSUP
+// naming the plan when it has no log form (refused: its name; null for a plan that has one).
+int check_plan_log(std::string* err, int has_plan, int on, const char* refused);
+// omb_log_ei: check_ei, then OMB_EUNSUP for OMB_EI_PARETO (μ₁·EI has no logarithm where μ₁ ≤ 0).
+int check_log_ei(std::string* err, int kind, int k, double var_eps, double pof_eps);
 // omb_feasibility: 1 ≤ c ≤ OMB_MAX_OBJ, pof_eps finite and ≥ 0, then check_moments over the c rows.
 int check_feasibility(std::string* err, int c, const void* mu, const void* var, int64_t ld, int64_t N, double pof_eps,
                       const void* out);

@@ -126,6 +126,25 @@ hipError_t launch_ei(hipStream_t stream, int kind, int k, const double* mu, cons
 hipError_t launch_pof_scale(hipStream_t stream, int c, const double* mu, const double* var, int64_t ld, int64_t N,
                             double pof_eps, const double* acq, double* out);
 
+// Log-space acquisitions (omb_logacq.hip; Plan::log, omb_log_ei / omb_log_ehvi_boxes / omb_log_feasibility):
+//   launch_log_ei          log EI for OMB_EI_PLAIN / OMB_EI_CONSTRAINED over launch_ei's arguments
+//   launch_log_pof         out = acq + log F (acq null: log F) over launch_pof_scale's arguments; out may be acq
+//   launch_log_ehvi_boxes  log of the exact EHVI, 2 ≤ k ≤ OMB_MAX_OBJ, within check_boxes_k's limits (boxes 4-byte
+//                          aligned): the one kernel behind both box plans
+//   launch_log_ei_grad     ∂ log EI / ∂μ, ∂σ² into rows 0..k-1 of dadm / dadv (pitch N)
+//   launch_log_pof_grad    rows k..k+c-1 of dadm / dadv: ∂ log F / ∂μ_j, ∂σ²_j (the objectives' rows stay: the weight
+//                          is a sum in log space)
+hipError_t launch_log_ei(hipStream_t stream, int kind, int k, const double* mu, const double* var, int64_t ld,
+                         int64_t N, double best, double var_eps, double pof_eps, double* out);
+hipError_t launch_log_pof(hipStream_t stream, int c, const double* mu, const double* var, int64_t ld, int64_t N,
+                          double pof_eps, const double* acq, double* out);
+hipError_t launch_log_ehvi_boxes(hipStream_t stream, int k, const double* mu, const double* var, int64_t ld, int64_t N,
+                                 const double* coords, int C, const uint16_t* boxes, int B, double* out);
+hipError_t launch_log_ei_grad(hipStream_t stream, int kind, int k, const double* mu, const double* var, int64_t ld,
+                              int64_t N, double best, double var_eps, double pof_eps, double* dadm, double* dadv);
+hipError_t launch_log_pof_grad(hipStream_t stream, const double* mu, const double* var, int64_t ld, int64_t N, int k,
+                               int c, double pof_eps, double* dadm, double* dadv);
+
 // Deterministic arg-max; `partials` must hold kArgmaxMaxBlocks (val, idx) pairs followed by one zeroed ticket word
 // (one_pass: both passes in one launch, the last workgroup to arrive reducing; it leaves the word zeroed again).
 constexpr int kArgmaxMaxBlocks = 1024;

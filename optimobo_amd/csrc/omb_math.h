@@ -31,6 +31,57 @@ __device__ __forceinline__ double npdf(double t) {
   return exp(-(t * t) / 2.0) / kSqrt2Pi;
 }
 
+// ---- log-space forms (omb_logacq.hip, the log gradients of omb_grad.hip).  Unfused like ndtr / npdf: the chain and
+// the stand-alone entries inline them into different kernels and must agree bitwise.
+constexpr double kLogSqrt2Pi = 0.91893853320467274178;   // log sqrt(2π)
+constexpr double kSqrtPi_2 = 1.25331413731550025121;     // sqrt(π/2)
+constexpr double kLn2 = 0.69314718055994530942;
+
+// The two ratios of the lower tail, t < 0:  R(t) = Φ(t)/φ(t) = sqrt(π/2)·erfcx(−t/√2) (the Mills ratio at −t) and
+// T(t) = h(t)/φ(t) = 1 + t·R(t), h(t) = tΦ(t) + φ(t).  Below −30 the sum 1 + tR cancels to fewer digits than the
+// asymptotic series keeps (w = 1/t²; the first term left out, 13!!·w⁷, is 2.5e-13 of T at t = −30, which is 6e-16
+// of |log h| = 457 there, and falls as t⁻¹²), and R = (T − 1)/t.
+struct TailRatios {
+  double R, T;
+};
+__device__ __forceinline__ TailRatios tail_ratios(double t) {
+#pragma clang fp contract(off)
+  TailRatios o;
+  if (t > -30.0) {
+    o.R = kSqrtPi_2 * erfcx(-(t * kSqrt1_2));
+    o.T = 1.0 + t * o.R;
+  } else {
+    const double w = 1.0 / (t * t);
+    o.T = w * (1.0 - 3.0 * w * (1.0 - 5.0 * w * (1.0 - 7.0 * w * (1.0 - 9.0 * w * (1.0 - 11.0 * w)))));
+    o.R = (o.T - 1.0) / t;
+  }
+  return o;
+}
+
+// log Φ(t): log1p(−Φ(−t)) above 0, log of cephes' Φ down to −1, −t²/2 + log(erfcx(−t/√2)/2) below (finite where Φ
+// underflows: −723 at t = −38).  −inf at t = −inf, NaN stays NaN.
+__device__ __forceinline__ double log_ndtr(double t) {
+#pragma clang fp contract(off)
+  if (t > 0.0) return log1p(-(0.5 * erfc(t * kSqrt1_2)));
+  if (!(t <= -1.0)) return log(ndtr(t));
+  return -(t * t) / 2.0 + log(0.5 * erfcx(-(t * kSqrt1_2)));
+}
+
+// log h(t), h(t) = tΦ(t) + φ(t) (EI = σ·h(γ)): the direct logarithm above −1; below it
+// −t²/2 − log√(2π) + log T(t) (tail_ratios), finite where h underflows (0.0 at t = −39 in the direct form).
+// −inf at t = −inf, +inf at t = +inf, NaN stays NaN.
+__device__ __forceinline__ double log_h(double t) {
+#pragma clang fp contract(off)
+  if (!(t <= -1.0)) return log(t * ndtr(t) + npdf(t));
+  return (-(t * t) / 2.0 - kLogSqrt2Pi) + log(tail_ratios(t).T);
+}
+
+// log(1 − e^d) for d ≤ 0 (Mächler's split at −ln 2): −inf at d = 0, 0 at d = −inf, NaN stays NaN.
+__device__ __forceinline__ double log1mexp(double d) {
+#pragma clang fp contract(off)
+  return d > -kLn2 ? log(-expm1(d)) : log1p(-exp(d));
+}
+
 // util_functions.py:130-133  ψ(a,b,m,s) = s·φ((b−m)/s) + (a−m)·Φ((b−m)/s), given t=(b−m)/s.
 __device__ __forceinline__ double psi_t(double a, double m, double s, double t, double pdf_t, double cdf_t) {
   (void)t;

@@ -46,6 +46,7 @@ class AcqContext:
         self._gp_keep = {}     # device tensors referenced by the packed GP state
         self.gp_info = {}
         self.plan_kind = None  # (omb_plan_* name, mode) of the plan last set through this object
+        self.plan_is_log = False   # plan_log's flag on that plan
         self._paths_S = {}     # objective → S of the sample paths last installed through this object
 
     # ------------------------------------------------------------------ plumbing
@@ -280,6 +281,42 @@ class AcqContext:
                                              _ptr(acq) if acq is not None else None, _ptr(out)), "omb_feasibility")
         return out
 
+    # log-space forms: finite where the linear values above are exactly 0.0 (include/optimobo_hip.h)
+    def log_ei(self, mu, var, best, var_eps=0.0, pof_eps=0.0, kind="plain", out=None):
+        """omb_log_ei: log EI over rows 0..k-1 of (mu, var) — kind "plain" (k = 1; 1-D moments are taken as one
+        row) or "constrained" (rows 1.. are constraint models); "pareto" has no logarithm (OMB_EUNSUP)."""
+        if mu.dim() == 1:
+            mu, var = mu.reshape(1, -1), var.reshape(1, -1)
+        k, N = mu.shape
+        out = self._out(out, N)
+        self._stream()
+        self._check(self.lib.omb_log_ei(self._h, _EI_KINDS[kind], k, _ptr(mu), _ptr(var), mu.stride(0), N,
+                                        float(best), float(var_eps), float(pof_eps), _ptr(out)), "omb_log_ei")
+        return out
+
+    def log_ehvi_boxes(self, mu, var, coords, boxes, out=None):
+        """omb_log_ehvi_boxes: the logarithm of ``ehvi_boxes`` (2 ≤ k ≤ 8; one kernel for every k)."""
+        k, N = mu.shape
+        coords = _dev_f64(coords, self.device)
+        boxes = self._boxes_dev(boxes)
+        out = self._out(out, N)
+        self._stream()
+        self._check(self.lib.omb_log_ehvi_boxes(self._h, k, _ptr(mu), _ptr(var), mu.stride(0), N, _ptr(coords),
+                                                coords.shape[1], _ptr(boxes), boxes.shape[0], _ptr(out)),
+                    "omb_log_ehvi_boxes")
+        return out
+
+    def log_feasibility(self, mu, var, pof_eps=1e-5, acq=None, out=None):
+        """omb_log_feasibility: log F = Σ_j log Φ(−μ_j / sqrt(σ²_j + pof_eps)) over the rows of (mu, var) (c, N),
+        plus ``acq`` (N,) — a log acquisition — when given (``out`` may be ``acq``)."""
+        c, N = mu.shape
+        out = self._out(out, N)
+        self._stream()
+        self._check(self.lib.omb_log_feasibility(self._h, c, _ptr(mu), _ptr(var), mu.stride(0), N, float(pof_eps),
+                                                 _ptr(acq) if acq is not None else None, _ptr(out)),
+                    "omb_log_feasibility")
+        return out
+
     def argmax_dev(self, vals, offset=0, out=None):
         out = self._out(out, 2)
         self._stream()
@@ -298,6 +335,7 @@ class AcqContext:
     def _plan(self, fn, *args, mode=None):
         self._stream()
         self.plan_kind = None          # a failed plan call leaves no plan
+        self.plan_is_log = False       # every plan starts linear (omb_plan_log's flag is cleared)
         self._check(getattr(self.lib, fn)(self._h, *args), fn)
         self.plan_kind = (fn, mode)
 
@@ -309,6 +347,8 @@ class AcqContext:
         if self.plan_kind is None:
             return False
         fn, mode = self.plan_kind
+        if self.plan_is_log and fn in ("omb_plan_ehvi_boxes", "omb_plan_ehvi_boxes_k"):
+            return False               # the log exact EHVI has no analytic gradient yet (log EI has)
         return fn in self._GRAD_PLANS and mode != "sigma"
 
     def plan_ehvi2d(self, pf_sorted, r, s00, s01, mode="reference"):
@@ -354,6 +394,15 @@ class AcqContext:
         this, so it comes after the plan; n_con = 0 clears it too.  A failed call changes nothing."""
         self._stream()
         self._check(self.lib.omb_plan_constraints(self._h, int(n_con), float(pof_eps)), "omb_plan_constraints")
+
+    def plan_log(self, on=True):
+        """omb_plan_log: the plan that is set returns the logarithm of its acquisition (EI plain / constrained, exact
+        EHVI over boxes; OMB_EUNSUP for the others), and ``plan_constraints`` adds log F in place of multiplying by
+        F.  Every plan_* call clears it; it may come before or after ``plan_constraints``.  A failed call changes
+        nothing."""
+        self._stream()
+        self._check(self.lib.omb_plan_log(self._h, int(on)), "omb_plan_log")
+        self.plan_is_log = bool(on)
 
     def set_sobol(self, d, lo, hi, seed=None, scramble=True, state=None):
         """Device Sobol' engine = scipy qmc.Sobol(d, scramble=scramble, seed=seed) over [lo, hi]."""
