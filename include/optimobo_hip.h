@@ -307,6 +307,18 @@ int omb_log_ehvi_boxes(omb_ctx* ctx, int k, const double* mu_dev, const double* 
 int omb_log_feasibility(omb_ctx* ctx, int c, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
                         double pof_eps, const double* acq_dev /* may be NULL */, double* out_dev);
 
+/* Max-value entropy search (MES, Wang & Jegelka 2017; over k objectives MESMO, Belakaria et al. 2019), everything
+ * minimised.  ystar_dev (k, S): the minimum of objective j under posterior sample s (omb_paths_min).  With
+ * σ_j = sqrt(σ²_j) and γ_js = (μ_j − y*_js)/σ_j:
+ *   out = Σ_j [ (Σ_s a(γ_js)) / S ],   a(γ) = γφ(γ)/(2Φ(γ)) − log Φ(γ)   (≥ 0, decreasing in γ),
+ * both sums in index order, unfused; a on the tail ratios Φ/φ and h/φ below 0, finite where Φ underflows.
+ * α over k posterior rows (row j at mu_dev + j·ld).  1 ≤ k ≤ OMB_MAX_OBJ, 1 ≤ S ≤ 64.
+ * OMB_EINVAL: k or S outside its range, N < 0, a null pointer with N > 0, ld < N with k > 1.  N = 0: OMB_OK, nothing
+ * written.  ystar is not inspected (it is on the device): a NaN y* gives NaN.  σ²_j ≤ 0 or a NaN moment gives NaN for
+ * that candidate only.  Asynchronous. */
+int omb_mes(omb_ctx* ctx, int k, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
+            const double* ystar_dev, int S, double* out_dev);
+
 /* Arg-max over vals_dev (N): lowest index among maxima, NaN and -inf never win
  * (replaces scipy differential_evolution(lambda x: -acq(x)), optimisers.py:87,118).
  * result_dev (2 doubles, device): {best value, best index + offset (as double)};
@@ -349,6 +361,12 @@ int omb_plan_ei(omb_ctx* ctx, double best, double var_eps);
 /* EI family over objectives 0..k-1: as omb_ei_ext. */
 int omb_plan_ei_ext(omb_ctx* ctx, int kind, int k, double best, double var_eps, double pof_eps);
 
+/* omb_mes as a plan of the fused chain over objectives 0..k-1 (σ² of every one of them is read); ystar_host (k, S) is
+ * checked: a non-finite entry is OMB_EINVAL and leaves no plan.  omb_eval_grad is analytic on it:
+ *   ∂α/∂μ_j = (1/S) Σ_s a'(γ_js)/σ_j,  ∂α/∂σ²_j = (1/S) Σ_s a'(γ_js)·(−γ_js)/(2σ²_j),  a'(γ) = −(q/2)(1 + γ² + γq),
+ * q = φ/Φ.  omb_plan_constraints applies as to every plan; omb_plan_log answers OMB_EUNSUP. */
+int omb_plan_mes(omb_ctx* ctx, int k, int S, const double* ystar_host);
+
 /* Inequality constraints on the plan that is set (g ≤ 0 feasible).  From here on omb_eval, omb_eval_argmax,
  * omb_eval_argmax_sobol and omb_eval_grad also compute the posterior (μ and σ²) of context slots k..k+n_con−1 — the
  * constraint models, set like objectives with omb_set_gp / omb_gp_fit_state — and multiply the acquisition by their
@@ -369,7 +387,7 @@ int omb_plan_constraints(omb_ctx* ctx, int n_con, double pof_eps);
  * omb_plan_constraints; with both, the chain adds log F (omb_log_feasibility) in place of the multiplication by F.
  * The posterior's variance mask is the linear plan's.  Errors, in this order, each leaving the plan as it was:
  * OMB_ESTATE with no plan; OMB_EINVAL for `on` outside {0, 1}; OMB_EUNSUP, naming the plan, for Pareto EI, EHVI-2D
- * (any mode), Monte-Carlo EHVI, HV-PoI and expected decomposition.
+ * (any mode), Monte-Carlo EHVI, HV-PoI, expected decomposition and max-value entropy search.
  * omb_eval_grad on a log plan: log EI (plain or constrained, with or without omb_plan_constraints) is analytic —
  *   ∂/∂μ = −ρ/(σ + 1e-10),  ∂/∂σ² = (1/σ − ρ·γ/(σ + 1e-10))/(2σ),  ρ = Φ(γ)/h(γ) = R/T for γ < 0,
  *   a constraint row: ∂ log Φ(z)/∂z = φ(z)/Φ(z) = 1/R(z) times ∂z/∂μ, ∂z/∂σ² —
@@ -487,6 +505,13 @@ int omb_paths_set(omb_ctx* ctx, int obj, int S, int m, const double* omega_host,
  * Refusals, in this order: OMB_EINVAL for n_obj outside [1, OMB_MAX_OBJ], N < 0, ld < N, a null pointer with N > 0;
  * OMB_ESTATE for an objective that is not set, has no paths or another S than objective 0; OMB_EUNSUP as above. */
 int omb_paths_eval(omb_ctx* ctx, int n_obj, const double* Xc_dev, int64_t N, int64_t ld, double* out_dev);
+/* res_dev[(o·S + s)·2 + {0, 1}] = { min_i f_{o,s}(Xc_i), the lowest such i + offset (as double) }, objectives
+ * 0..n_obj-1: omb_paths_eval's tile loop with the minimum taken in its epilogue, so the (n_obj·S, N) matrix never
+ * exists.  The value is bitwise the minimum of omb_paths_eval's row.  Every comparison is "smaller value, else lower
+ * index" (no atomics): the pair does not depend on the launch grid.  NaN never wins; N = 0 or an all-NaN row gives
+ * {+inf, −1}.  Asynchronous; the context's partials buffer is grown on demand (a grow synchronises first).  Limits
+ * and refusals are omb_paths_eval's, in its order (res_dev takes out_dev's place and may not be NULL even at N = 0). */
+int omb_paths_min(omb_ctx* ctx, int n_obj, const double* Xc_dev, int64_t N, int64_t offset, double* res_dev);
 
 /* ---------------------------------------------------------------------------------------
  * ParEGO / KEEP evolutionary acquisition search (parego.py:223-271, keep.py:240-292): the

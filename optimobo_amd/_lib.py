@@ -69,6 +69,8 @@ SIGNATURES = {
     "omb_log_ei": (_i, [_p, _i, _i, _p, _p, _i64, _i64, _d, _d, _d, _p]),
     "omb_log_ehvi_boxes": (_i, [_p, _i, _p, _p, _i64, _i64, _p, _i, _p, _i, _p]),
     "omb_log_feasibility": (_i, [_p, _i, _p, _p, _i64, _i64, _d, _p, _p]),
+    # max-value entropy search
+    "omb_mes": (_i, [_p, _i, _p, _p, _i64, _i64, _p, _i, _p]),
     "omb_argmax_dev": (_i, [_p, _p, _i64, _i64, _p]),
     "omb_argmax": (_i, [_p, _p, _i64, _i64, _dp, ctypes.POINTER(_i64)]),
     # fused chain (host pointers for plan geometry)
@@ -81,6 +83,7 @@ SIGNATURES = {
     "omb_plan_expdec": (_i, [_p, _i, _p, _i, _i, _dp, _dp, _dp, _dp, _d]),
     "omb_plan_ei": (_i, [_p, _d, _d]),
     "omb_plan_ei_ext": (_i, [_p, _i, _i, _d, _d, _d]),
+    "omb_plan_mes": (_i, [_p, _i, _i, _p]),
     "omb_plan_constraints": (_i, [_p, _i, _d]),
     "omb_plan_log": (_i, [_p, _i]),
     "omb_set_sobol": (_i, [_p, _i, _i, _p, _p, _dp, _dp]),
@@ -101,6 +104,7 @@ SIGNATURES = {
     # posterior sample paths (host pointers for the draws)
     "omb_paths_set": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _d]),
     "omb_paths_eval": (_i, [_p, _i, _p, _i64, _i64, _p]),
+    "omb_paths_min": (_i, [_p, _i, _p, _i64, _i64, _p]),
     "omb_ea_search": (_i, [_p, _i, _d, _d, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     # GP fit on the device
     "omb_gp_lml_grad": (_i, [_p, _i, _i, _i, _p, _p, _dp, _d, _d, _dp, _dp, _dp]),

@@ -39,6 +39,7 @@ class AcquisitionEngine:
         self._stale = set()     # objectives whose device state was conditioned on top of _resident[o]
         self.condition_jitter = 0.0
         self.paths_floored = 0
+        self.ystar = None       # sample_minima's last result (n_obj, S)
         self.n_obj = 0
 
     # ------------------------------------------------------------------ model state
@@ -165,6 +166,73 @@ class AcquisitionEngine:
         """The installed sample paths at Xc (N, d) → device tensor (n_obj, S, N)."""
         Xc = Xc if isinstance(Xc, torch.Tensor) else self._dev(np.atleast_2d(Xc))
         return self.ctx.paths_eval(Xc, self.n_obj)
+
+    def sample_minima(self, S, lower, upper, n_candidates=1 << 16, seed=0, n_features=1024, refine_rounds=0, shrink=0.1,
+                      n_refine=4096):
+        """The minimum of S fresh posterior sample paths of every loaded model over the box → ``ystar`` (n_obj, S) as
+        numpy, kept on the engine for ``mes`` / ``plan_mes`` (max-value entropy search).
+
+        ``sample_paths(S, n_features, seed, lower=…, upper=…)`` (1 ≤ S ≤ 16: one path install), then
+        ``AcqContext.paths_min`` — the minimum is taken in the evaluation kernel, the (n_obj, S, N) matrix is never
+        stored — over the first ``n_candidates`` points of the device Sobol' sequence seeded by ``seed``, and once
+        more over the resident training inputs, so that each sampled minimum is at or below its path's value at every
+        observed x.  With ``refine_rounds`` > 0, ``thompson_batch``'s refinement: round r evaluates ``n_refine``
+        Sobol' points of the box ``shrink``^r times the bounds' size around each path's minimiser (clipped to the
+        bounds; one ``paths_min`` per round, objective and path — the boxes differ) and keeps a smaller value.  The
+        installed plan and the Sobol' state of the context are overwritten; the paths stay installed."""
+        S = int(S)
+        if not 1 <= S <= 16:
+            raise ValueError(f"sample_minima: S={S} outside [1, 16] (one path install)")
+        lower = np.asarray(lower, np.float64).reshape(-1)
+        upper = np.asarray(upper, np.float64).reshape(-1)
+        d, k = lower.size, self.n_obj
+        self.sample_paths(S, n_features=n_features, seed=seed, lower=lower, upper=upper)
+        self.ctx.set_sobol(d, lower, upper, seed=seed)
+        Xc = self.ctx.sobol(0, int(n_candidates))
+        val, idx = self.ctx.paths_min(Xc, k)
+        Xbest = Xc[idx.clamp(min=0).reshape(-1)].reshape(k, S, d)
+        shared = all(np.array_equal(self._resident[o].X, self._resident[0].X) for o in range(1, k))
+        for o in range(k):      # one call when the models share their inputs (the drivers' case), else one per model
+            if o == 0 or not shared:
+                Xt = self._dev(self._resident[o].X)
+                vt, it = self.ctx.paths_min(Xt, k)
+            better = vt[o] < val[o]
+            val[o] = torch.where(better, vt[o], val[o])
+            Xbest[o] = torch.where(better[:, None], Xt[it[o].clamp(min=0)], Xbest[o])
+        ystar, Xbest = val.cpu().numpy(), Xbest.cpu().numpy()
+        for rnd in range(1, int(refine_rounds) + 1):
+            half = shrink ** rnd * (upper - lower) / 2
+            for o in range(k):
+                for s in range(S):
+                    self.ctx.set_sobol(d, np.maximum(lower, Xbest[o, s] - half), np.minimum(upper, Xbest[o, s] + half),
+                                       seed=seed + 104729 * rnd + o * S + s)
+                    Xr = self.ctx.sobol(0, int(n_refine))
+                    vr, ir = self.ctx.paths_min(Xr, k)
+                    v = float(vr[o, s])
+                    if v < ystar[o, s]:
+                        ystar[o, s] = v
+                        Xbest[o, s] = Xr[int(ir[o, s])].cpu().numpy()
+        self.ystar = ystar
+        return ystar
+
+    def _ystar(self, ystar, what):
+        if ystar is None:
+            if self.ystar is None:
+                raise RuntimeError(f"{what}: no sampled minima (call sample_minima first, or pass ystar)")
+            ystar = self.ystar
+        return np.atleast_2d(np.asarray(ystar, np.float64))
+
+    def mes(self, Xc, ystar=None):
+        """Max-value entropy search (MESMO over several models) on every row of Xc under the sampled minima
+        ``ystar`` (k, S) of the first k loaded models (None: the last ``sample_minima`` result)."""
+        ystar = self._ystar(ystar, "mes")
+        mu, var = self.posterior(Xc)
+        k = ystar.shape[0]
+        return self.ctx.mes(mu[:k], var[:k], ystar)
+
+    def plan_mes(self, ystar=None):
+        """``mes`` as the fused chain's plan (None: the last ``sample_minima`` result); ``has_gradient`` is True."""
+        self.ctx.plan_mes(self._ystar(ystar, "plan_mes"))
 
     def thompson_batch(self, q, lower, upper, PF=None, max_point=None, n_candidates=None, seed=0,
                        max_boxes=1 << 20, sampler="joint", n_features=1024, refine_rounds=0, shrink=0.1,

@@ -33,7 +33,8 @@ class BODriver:
 
     def __init__(self, test_problem, ideal_point=None, max_point=None, mode="reference", n_candidates=1 << 14,
                  refine_rounds=2, seed=None, device=None, polish=True, starts=None, noise=0.0, batch_size=1,
-                 constraints=None, batch_strategy="believer", thompson_sampler="joint", log_acquisition=False):
+                 constraints=None, batch_strategy="believer", thompson_sampler="joint", log_acquisition=False,
+                 acquisition=None, mes_samples=8, mes_candidates=1 << 16):
         self.test_problem = test_problem
         self.max_point = max_point
         self.ideal_point = ideal_point
@@ -85,8 +86,14 @@ class BODriver:
         # fp64 over most of a late-run box, where their logarithms still rank the candidates and have a slope
         # (AcquisitionEngine.plan_log).  False is the linear path, call for call.
         self.log_acquisition = self._check_log_acquisition(log_acquisition)
+        # the acquisition of every pick (not in the reference): None is the driver's own (EHVI / expected decomposition
+        # / EI), call for call; "mes" is max-value entropy search — MESMO over MultiSurrogateOptimiser's objectives, MES
+        # on MonoSurrogateOptimiser's scalarised surrogate — from ``mes_samples`` posterior sample paths per pick, each
+        # minimised over ``mes_candidates`` Sobol' points and the training inputs (AcquisitionEngine.sample_minima)
+        self.acquisition = self._check_acquisition(acquisition, mes_samples, mes_candidates)
         self.thompson_fallbacks = 0   # Thompson iterations that fell back to the believer batch
         self._iteration = 0
+        self._mes_picks = 0
 
     def _check_batch_strategy(self, batch_strategy):
         if batch_strategy not in ("believer", "thompson"):
@@ -116,6 +123,45 @@ class BODriver:
             raise ValueError(f"log_acquisition=True needs mode in {modes} on {type(self).__name__} (mode={self.mode!r} "
                              "plans an acquisition without a log form)")
         return True
+
+    # acquisition="mes": MultiSurrogateOptimiser (acquisition_func=None) and MonoSurrogateOptimiser
+    _acquisitions = ()
+    mes_features = 1024          # random Fourier features per model of a pick's sample paths
+
+    def _check_acquisition(self, acquisition, mes_samples, mes_candidates):
+        self.mes_samples, self.mes_candidates = mes_samples, mes_candidates
+        if acquisition is None:
+            return None
+        if acquisition != "mes":
+            raise ValueError(f"acquisition must be None or 'mes', not {acquisition!r}")
+        if acquisition not in self._acquisitions:
+            raise ValueError(f"{type(self).__name__} does not support acquisition='mes' (MultiSurrogateOptimiser and "
+                             "MonoSurrogateOptimiser do)")
+        if self.batch_strategy == "thompson":
+            raise ValueError("acquisition='mes' does not support batch_strategy='thompson' (a Thompson batch maximises "
+                             "no acquisition; 'believer' batches take it)")
+        if self.log_acquisition:
+            raise ValueError("acquisition='mes' does not support log_acquisition=True (max-value entropy search has no "
+                             "log form)")
+        if self.n_vars > 64:
+            raise ValueError(f"acquisition='mes' samples posterior paths, which need n_var <= 64 (n_var={self.n_vars})")
+        if isinstance(mes_samples, bool) or not isinstance(mes_samples, (int, np.integer)) or not 1 <= mes_samples <= 16:
+            raise ValueError(f"mes_samples must be an integer in [1, 16], not {mes_samples!r}")
+        if isinstance(mes_candidates, bool) or not isinstance(mes_candidates, (int, np.integer)) or mes_candidates < 1:
+            raise ValueError(f"mes_candidates must be an integer >= 1, not {mes_candidates!r}")
+        self.mes_samples, self.mes_candidates = int(mes_samples), int(mes_candidates)
+        return "mes"
+
+    def _plan_mes(self, eng, k):
+        """The MES plan of one pick on ``eng`` over its first ``k`` models: fresh sample paths (a seed of their own
+        per pick, derived as ``_maximise`` derives a search's), their minima, the plan.  ``eng.condition`` drops the
+        paths, so a believer batch samples again for every pick, from the conditioned state."""
+        base = self.seed if self.seed is not None else np.random.randint(0, 2 ** 31 - 1)
+        self._mes_picks += 1
+        ystar = eng.sample_minima(self.mes_samples, self.test_problem.xl, self.test_problem.xu,
+                                  n_candidates=self.mes_candidates, seed=base + 15485863 + 7919 * self._mes_picks,
+                                  n_features=self.mes_features)
+        eng.plan_mes(ystar[:k])
 
     def _check_constraints_option(self, constraints):
         if constraints is None:

@@ -36,13 +36,14 @@ struct ObjState {
 // One acquisition request.  A describe_* function validates the scalar arguments and fills everything but geo / boxes;
 // a stand-alone entry then points those at the caller's device arrays, an omb_plan_* entry uploads the host geometry
 // and points them at ctx->geo (the fused chain's plan).  launch_acq / launch_acq_grad run it.
-enum PlanKind { PLAN_NONE = 0, PLAN_EHVI2D, PLAN_EHVI_MC, PLAN_EHVI_BOXES, PLAN_HVPOI, PLAN_EXPDEC, PLAN_EI };
+enum PlanKind { PLAN_NONE = 0, PLAN_EHVI2D, PLAN_EHVI_MC, PLAN_EHVI_BOXES, PLAN_HVPOI, PLAN_EXPDEC, PLAN_EI, PLAN_MES };
 
 struct Plan {
   int kind = PLAN_NONE;
   int k = 0;                    // objectives the acquisition reads (posterior of 0..k-1)
   unsigned var_mask = 0;        // bit o: the plan's kernel loads σ² of objective o (the others' is never computed)
   int P = 0, M = 0, C = 0, B = 0, mode = 0;
+  int S = 0;                    // PLAN_MES: sampled minima per objective (geo: ystar (k, S))
   double r[OMB_MAX_OBJ] = {};
   double s00 = 0, s01 = 0, hv = 0, best = 0, var_eps = 0, pof_eps = 0;
   int ei_kind = OMB_EI_PLAIN;
@@ -104,6 +105,7 @@ struct omb_ctx {
   DevBuf gws;    // gradient chain (omb_posterior_grad / omb_eval_grad): ∂a/∂μ | ∂a/∂σ² | K* | V | w per objective
   DevBuf aws;    // omb_gp_append: the bordered state (AppendWs)
   DevBuf hws;    // omb_hvi_boxes: the slices' sums of a small batch (hvi_ws_doubles)
+  DevBuf pws;    // omb_paths_min: the first launch's per-workgroup (value, index) pairs
   // device fault word (pinned, mapped host memory): kernels mark it, enter() reports it
   int* fault_host = nullptr;
   int* fault_dev = nullptr;
@@ -304,6 +306,18 @@ int describe_ei(omb_ctx* ctx, int kind, int k, double best, double var_eps, doub
   return OMB_OK;
 }
 
+// omb_mes / omb_plan_mes (the stand-alone entry's y* is on the device and is not inspected; the plan entry checks its
+// host copy before it installs it)
+int describe_mes(omb_ctx* ctx, int k, int S, Plan* pl) {
+  int rc = check_mes(E(ctx), k, S, nullptr, nullptr, 0, 0, nullptr, nullptr);
+  if (rc) return rc;
+  pl->kind = PLAN_MES;
+  pl->k = k;
+  pl->var_mask = all_objectives(k);   // mes_kernel: γ_js over every σ_j
+  pl->S = S;
+  return OMB_OK;
+}
+
 // omb_ehvi_boxes_k's kernel: candidate-blocked, or (OMB_DEBUG_BOXES_KD = 1, where its tables fit) the baseline
 hipError_t launch_boxes_k(omb_ctx* ctx, int k, const double* mu, const double* var, int64_t ld, int64_t N,
                           const double* coords, int C, const uint16_t* boxes, int B, double* out) {
@@ -333,6 +347,8 @@ hipError_t launch_acq(omb_ctx* ctx, const Plan& pl, const double* mu, const doub
     case PLAN_EI:
       if (pl.log) return launch_log_ei(st, pl.ei_kind, pl.k, mu, var, ld, N, pl.best, pl.var_eps, pl.pof_eps, out);
       return launch_ei(st, pl.ei_kind, pl.k, mu, var, ld, N, pl.best, pl.var_eps, pl.pof_eps, out);
+    case PLAN_MES:
+      return launch_mes(st, pl.k, mu, var, ld, N, pl.geo, pl.S, out);
     default:
       return hipErrorInvalidValue;
   }
@@ -361,6 +377,9 @@ int launch_acq_grad(omb_ctx* ctx, const Plan& pl, const double* mu, const double
         e = launch_log_ei_grad(st, pl.ei_kind, pl.k, mu, var, N, N, pl.best, pl.var_eps, pl.pof_eps, dadm, dadv);
       else if (dadm)
         e = launch_ei_grad(st, pl.ei_kind, pl.k, mu, var, N, N, pl.best, pl.var_eps, pl.pof_eps, dadm, dadv);
+      break;
+    case PLAN_MES:
+      if (dadm) e = launch_mes_grad(st, pl.k, mu, var, N, N, pl.geo, pl.S, dadm, dadv);
       break;
     case PLAN_EHVI_MC: unsup = "Monte-Carlo EHVI"; break;
     case PLAN_EXPDEC: unsup = "expected decomposition"; break;
@@ -584,7 +603,7 @@ int omb_destroy(omb_ctx* ctx) {
   if (ctx->result_host) (void)hipHostFree(ctx->result_host);
   if (ctx->info_host) (void)hipHostFree(ctx->info_host);
   for (DevBuf* b : {&ctx->geo, &ctx->work, &ctx->tws, &ctx->ichol, &ctx->sws, &ctx->ews, &ctx->fws, &ctx->dws, &ctx->gws,
-                    &ctx->aws, &ctx->hws})
+                    &ctx->aws, &ctx->hws, &ctx->pws})
     if (b->p) (void)hipFree(b->p);
   if (ctx->stage) (void)hipHostFree(ctx->stage);
   if (ctx->sob) (void)hipFree(ctx->sob);
@@ -991,6 +1010,16 @@ int omb_log_feasibility(omb_ctx* ctx, int c, const double* mu_dev, const double*
   return OMB_OK;
 }
 
+int omb_mes(omb_ctx* ctx, int k, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
+            const double* ystar_dev, int S, double* out_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  Plan pl;
+  if ((rc = describe_mes(ctx, k, S, &pl))) return rc;
+  if ((rc = check_mes(E(ctx), k, S, mu_dev, var_dev, ld, N, ystar_dev, out_dev))) return rc;
+  return run_acq(ctx, pl, ystar_dev, nullptr, mu_dev, var_dev, ld, N, out_dev, nullptr, "mes");
+}
+
 int omb_argmax_dev(omb_ctx* ctx, const double* vals_dev, int64_t N, int64_t offset, double* result_dev) {
   int rc = enter(ctx);
   if (rc) return rc;
@@ -1091,6 +1120,15 @@ int omb_plan_ei_ext(omb_ctx* ctx, int kind, int k, double best, double var_eps, 
   return OMB_OK;
 }
 
+int omb_plan_mes(omb_ctx* ctx, int k, int S, const double* ystar_host) {
+  int rc = plan_enter(ctx);
+  if (rc) return rc;
+  Plan pl;
+  if ((rc = describe_mes(ctx, k, S, &pl))) return rc;
+  if ((rc = check_plan_mes(E(ctx), k, S, ystar_host))) return rc;
+  return install_plan(ctx, pl, ystar_host, sizeof(double) * (size_t)k * S);
+}
+
 int omb_plan_constraints(omb_ctx* ctx, int n_con, double pof_eps) {
   int rc = enter(ctx);
   if (rc) return rc;
@@ -1110,6 +1148,7 @@ static const char* log_refused(const Plan& pl) {
     case PLAN_EHVI_MC: return "Monte-Carlo EHVI";
     case PLAN_HVPOI: return "HV-PoI";
     case PLAN_EXPDEC: return "expected decomposition";
+    case PLAN_MES: return "max-value entropy search";
     default: return "unknown";
   }
 }
@@ -1840,6 +1879,30 @@ int omb_paths_eval(omb_ctx* ctx, int n_obj, const double* Xc_dev, int64_t N, int
   if ((N + 63) / 64 > 0x7fffffffLL) return fail(ctx, OMB_EUNSUP, "N=%lld too large", (long long)N);
   hipError_t e = launch_paths_eval(ctx->stream, pa, n_obj, ctx->obj[0].kind, ctx->paths_libcos, Xc_dev, N, ld, out_dev);
   if (e != hipSuccess) return hip_fail(ctx, e, "paths_eval");
+  return OMB_OK;
+}
+
+int omb_paths_min(omb_ctx* ctx, int n_obj, const double* Xc_dev, int64_t N, int64_t offset, double* res_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  PathsObjInfo info[OMB_MAX_OBJ];
+  for (int o = 0; o < OMB_MAX_OBJ; ++o) info[o] = paths_info(ctx->obj[o]);
+  if ((rc = check_paths_min(E(ctx), n_obj, Xc_dev, N, res_dev, info))) return rc;
+  PathArgs pa{};
+  for (int o = 0; o < n_obj; ++o) {
+    const ObjState& s = ctx->obj[o];
+    if (s.d != ctx->obj[0].d) return fail(ctx, OMB_EINVAL, "objectives disagree on n_var (%d vs %d)", s.d, ctx->obj[0].d);
+    if (s.kind != ctx->obj[0].kind) return fail(ctx, OMB_EINVAL, "objectives disagree on kernel kind");
+    pa.o[o] = PathObj{s.dev, s.path_Of, s.path_Wf, s.path_Vf, s.path_MT, s.R, s.path_S, 0};
+  }
+  pa.d = ctx->obj[0].d;
+  pa.DP = ctx->obj[0].DP;
+  if ((N + 63) / 64 > 0x7fffffffLL) return fail(ctx, OMB_EUNSUP, "N=%lld too large", (long long)N);
+  const size_t pairs = (size_t)paths_min_blocks(N) * (size_t)n_obj * kPathsMaxS;
+  if ((rc = grow_dev(ctx, ctx->pws, sizeof(double) * 2 * (pairs ? pairs : 1), "paths_min partials"))) return rc;
+  hipError_t e = launch_paths_min(ctx->stream, pa, n_obj, ctx->obj[0].kind, ctx->paths_libcos, Xc_dev, N, offset,
+                                  ctx->pws.as<double>(), res_dev);
+  if (e != hipSuccess) return hip_fail(ctx, e, "paths_min");
   return OMB_OK;
 }
 

@@ -156,6 +156,39 @@ int check_paths_eval(std::string* err, int n_obj, const void* Xc, int64_t N, int
   return OMB_OK;
 }
 
+int check_paths_min(std::string* err, int n_obj, const void* Xc, int64_t N, const void* res, const PathsObjInfo* info) {
+  if (n_obj < 1 || n_obj > OMB_MAX_OBJ) return errf(err, OMB_EINVAL, "n_obj=%d outside [1, %d]", n_obj, OMB_MAX_OBJ);
+  if (N < 0) return errf(err, OMB_EINVAL, "N=%lld < 0", (long long)N);
+  if (!res) return errf(err, OMB_EINVAL, "null result pointer");
+  // N as the pitch: the remaining refusals are check_paths_eval's own, in its order
+  return check_paths_eval(err, n_obj, Xc, N, N, res, info);
+}
+
+static int check_mes_shape(std::string* err, int k, int S) {
+  if (k < 1 || k > OMB_MAX_OBJ) return errf(err, OMB_EINVAL, "k=%d outside [1, %d]", k, OMB_MAX_OBJ);
+  if (S < 1 || S > kMesMaxS) return errf(err, OMB_EINVAL, "S=%d sampled minima outside [1, %d]", S, kMesMaxS);
+  return OMB_OK;
+}
+
+int check_mes(std::string* err, int k, int S, const void* mu, const void* var, int64_t ld, int64_t N,
+              const void* ystar, const void* out) {
+  int rc = check_mes_shape(err, k, S);
+  if (rc) return rc;
+  if (N < 0) return errf(err, OMB_EINVAL, "N=%lld < 0", (long long)N);
+  if (N > 0 && !ystar) return errf(err, OMB_EINVAL, "null device pointer");
+  return check_moments(err, mu, var, ld, N, k, out);
+}
+
+int check_plan_mes(std::string* err, int k, int S, const double* ystar) {
+  int rc = check_mes_shape(err, k, S);
+  if (rc) return rc;
+  if (!ystar) return errf(err, OMB_EINVAL, "null sampled minima");
+  for (int i = 0; i < k * S; ++i)
+    if (!(ystar[i] >= -1.79769313486231570815e308 && ystar[i] <= 1.79769313486231570815e308))
+      return errf(err, OMB_EINVAL, "ystar[%d][%d]=%g is not finite", i / S, i % S, ystar[i]);
+  return OMB_OK;
+}
+
 void paths_pack(int m, int d, int DP, int S, const double* omega, const double* phase, const double* w, double scale,
                 double* Of, double* Wf) {
   const int ksf = paths_ksf(DP);

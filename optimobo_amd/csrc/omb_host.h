@@ -91,6 +91,21 @@ int check_paths_set(std::string* err, int obj, int S, int m, const void* omega, 
 // paths, or with another S than objective 0; OMB_EUNSUP for n_var > kPathsMaxDim or n_train > OMB_MAX_TRAIN_DENSE.
 int check_paths_eval(std::string* err, int n_obj, const void* Xc, int64_t N, int64_t ld, const void* out,
                      const PathsObjInfo* info);
+// omb_paths_min: check_paths_eval's refusals in its order, without a pitch and with res in out's place — and res may
+// not be null even at N = 0 (the empty batch still writes {+inf, −1} for every path): OMB_EINVAL for n_obj outside
+// [1, OMB_MAX_OBJ], N < 0, a null res or (N > 0) a null Xc; then OMB_ESTATE and OMB_EUNSUP as there.
+int check_paths_min(std::string* err, int n_obj, const void* Xc, int64_t N, const void* res, const PathsObjInfo* info);
+// Workgroups per objective of omb_paths_min's first launch (each leaves one (value, index) pair per path).
+constexpr int kPathsMinMaxBlocks = 1024;
+// Max-value entropy search (omb_mes / omb_plan_mes, omb_mes.hip): sampled minima per objective.
+constexpr int kMesMaxS = 64;
+// omb_mes, in this order: OMB_EINVAL for k outside [1, OMB_MAX_OBJ], S outside [1, kMesMaxS], N < 0, (N > 0) a null
+// mu / var / ystar / out, or ld < N with k > 1.
+int check_mes(std::string* err, int k, int S, const void* mu, const void* var, int64_t ld, int64_t N,
+              const void* ystar, const void* out);
+// omb_plan_mes, in this order: OMB_EINVAL for k outside [1, OMB_MAX_OBJ], S outside [1, kMesMaxS], a null ystar, or a
+// non-finite entry among its k·S (a plan built on it would be NaN everywhere).
+int check_plan_mes(std::string* err, int k, int S, const double* ystar);
 // The paths' operands in the A-fragment order of v_mfma_f64_16x16x4_f64 (lane l holds A[l & 15][l >> 4]), zero
 // padded to whole tiles of 16 features and to 16 paths:
 //   Of[(T·ksf + s)·64 + l] = [ω̃_i, b_i, 0 …][4s + (l >> 4)] of feature i = 16T + (l & 15)   (ksf = paths_ksf(DP))

@@ -145,6 +145,13 @@ hipError_t launch_log_ei_grad(hipStream_t stream, int kind, int k, const double*
 hipError_t launch_log_pof_grad(hipStream_t stream, const double* mu, const double* var, int64_t ld, int64_t N, int k,
                                int c, double pof_eps, double* dadm, double* dadv);
 
+// Max-value entropy search (omb_mes.hip; omb_mes / omb_plan_mes): α over the moments (k, N) at pitch ld and the
+// sampled minima ystar (k, S) on the device, 1 ≤ S ≤ kMesMaxS; the partials into rows 0..k-1 of dadm / dadv (pitch N)
+hipError_t launch_mes(hipStream_t stream, int k, const double* mu, const double* var, int64_t ld, int64_t N,
+                      const double* ystar, int S, double* out);
+hipError_t launch_mes_grad(hipStream_t stream, int k, const double* mu, const double* var, int64_t ld, int64_t N,
+                           const double* ystar, int S, double* dadm, double* dadv);
+
 // Deterministic arg-max; `partials` must hold kArgmaxMaxBlocks (val, idx) pairs followed by one zeroed ticket word
 // (one_pass: both passes in one launch, the last workgroup to arrive reducing; it leaves the word zeroed again).
 constexpr int kArgmaxMaxBlocks = 1024;
@@ -384,6 +391,12 @@ struct PathArgs {
 // in place of the kernel's own (OMB_DEBUG_PATHS_LIBCOS, the baseline it is measured against)
 hipError_t launch_paths_eval(hipStream_t stream, const PathArgs& pa, int n_obj, int kind, bool libcos,
                              const double* Xc, int64_t N, int64_t ld, double* out);
+// res[(o·S + s)·2 + {0, 1}] = {min_i of path s of objective o over Xc (N ≥ 0), the lowest such i + offset}; {+inf, −1}
+// where no value is comparable.  partials: paths_min_blocks(N)·n_obj·16·2 doubles (the workgroups' pairs of the first
+// launch; a second launch reduces them in a fixed order).
+int paths_min_blocks(int64_t N);
+hipError_t launch_paths_min(hipStream_t stream, const PathArgs& pa, int n_obj, int kind, bool libcos, const double* Xc,
+                            int64_t N, int64_t offset, double* partials, double* res);
 // U (n, S) = Fᵀ + sd·z, F (S rows of pitch n), z (n, S) or null
 hipError_t launch_paths_u(hipStream_t stream, const double* F, const double* z, double sd, int n, int S, double* U);
 // Vf (paths_vf_doubles(R)) from α (n) and G = L⁻ᵀL⁻¹U (n, S)

@@ -76,6 +76,40 @@ __device__ __forceinline__ double log_h(double t) {
   return (-(t * t) / 2.0 - kLogSqrt2Pi) + log(tail_ratios(t).T);
 }
 
+// Max-value entropy search (omb_mes.hip): the per-sample term a(γ) = γφ(γ)/(2Φ(γ)) − log Φ(γ) and its
+// derivative a'(γ) = −(q/2)(1 + γ² + γq), q = φ/Φ.  Above 0 the direct expressions (−log Φ = −log1p(−Φ(−γ))); below
+// 0 on the tail ratios, where nothing cancels:
+//   a = γT/(2R) + log√(2π) − log R,     a' = −D/(2R),  D = 1 + γT/R = 1 + γ² + γq.
+// D → 2/γ² (a' → 1/γ) while its terms grow like γ²: below −30, with w = 1/γ², M = −γR = 1 − T = Σ (−1)^k (2k−1)!! w^k
+// and P = T/w = Σ (−1)^k (2k+1)!! w^k, D = (M − P)/M and the difference is summed term by term,
+//   M − P = Σ_{k≥1} (−1)^{k+1}·2k·(2k−1)!!·w^k = 2w(1 − 6w + 45w² − 420w³ + 4725w⁴ − 62370w⁵ + 945945w⁶ − …):
+// the first term left out, 16·15!!·w⁸, is 3.4e-14 of D at γ = −30 and falls as γ⁻¹⁴.  NaN stays NaN.
+struct MesTerm {
+  double a, da;
+};
+__device__ __forceinline__ MesTerm mes_term(double g) {
+#pragma clang fp contract(off)
+  MesTerm o;
+  if (g < 0.0) {
+    const TailRatios r = tail_ratios(g);
+    o.a = (g * r.T / (2.0 * r.R) + kLogSqrt2Pi) - log(r.R);
+    double D;
+    if (g > -30.0) {
+      D = 1.0 + g * r.T / r.R;
+    } else {
+      const double w = 1.0 / (g * g);
+      const double n = 2.0 * w * (1.0 - w * (6.0 - w * (45.0 - w * (420.0 - w * (4725.0 - w * (62370.0 - w * 945945.0))))));
+      D = n / (1.0 - r.T);
+    }
+    o.da = -D / (2.0 * r.R);
+  } else {
+    const double q = npdf(g) / ndtr(g);
+    o.a = g * q / 2.0 - log1p(-(0.5 * erfc(g * kSqrt1_2)));
+    o.da = -(q / 2.0) * ((1.0 + g * g) + g * q);
+  }
+  return o;
+}
+
 // log(1 − e^d) for d ≤ 0 (Mächler's split at −ln 2): −inf at d = 0, 0 at d = −inf, NaN stays NaN.
 __device__ __forceinline__ double log1mexp(double d) {
 #pragma clang fp contract(off)

@@ -1,4 +1,4 @@
-// Posterior sample paths on gfx950 (omb_paths_set / omb_paths_eval): pathwise conditioning with random Fourier
+// Posterior sample paths on gfx950 (omb_paths_set / omb_paths_eval / omb_paths_min): pathwise conditioning with random Fourier
 // features (Wilson et al. 2020, "Efficiently sampling functions from Gaussian process posteriors"),
 //     f_s(x) = Σ_i w_is·sqrt(2σ_f²/m)·cos(ω̃_i·(x/ℓ) + b_i)  +  Σ_j k(x, X_j)·v_js.
 // A draw is a function: evaluating S ≤ 16 of them at N points is O(N·(m + n)·S), nothing is N × N, nothing is
@@ -63,34 +63,38 @@ __device__ __forceinline__ double path_cos(double t) {
     return cos_cw(t);
 }
 
-template <int DP, int KIND, bool LIBCOS>
-__global__ __launch_bounds__(256) void paths_eval_kernel(PathArgs pa, const double* __restrict__ Xc, int64_t N,
-                                                         int64_t ld, double* __restrict__ out, ExpCoef ec) {
-  constexpr bool kAug = DP <= 8;
-  constexpr int KSD = kAug ? (DP + 5) / 4 : (DP + 3) / 4;
-  constexpr int KSDP = ((DP + 5) / 4 + 1) / 2;   // = packed_X_pairs(DP)
-  constexpr int KSF = (DP + 4) / 4;              // = paths_ksf(DP): k-steps of [x/ℓ, 1]
-  constexpr bool kTab256 = KIND == OMB_KERNEL_MATERN52;
-  __shared__ double etab[kTab256 ? 256 : 64];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  if constexpr (kTab256)
-    etab[tid] = kExp2Tab256[tid];   // 256 threads
+// The k-step counts of one instantiation (n_var padded to DP).
+template <int DP>
+struct PathsDims {
+  static constexpr bool kAug = DP <= 8;
+  static constexpr int KSD = kAug ? (DP + 5) / 4 : (DP + 3) / 4;
+  static constexpr int KSDP = ((DP + 5) / 4 + 1) / 2;   // = packed_X_pairs(DP)
+  static constexpr int KSF = (DP + 4) / 4;              // = paths_ksf(DP): k-steps of [x/ℓ, 1]
+};
+
+// exp2 table of the Matern / RBF transform into LDS (256 threads; the caller's barrier follows)
+template <int KIND>
+__device__ __forceinline__ void paths_stage_table(double* etab, int tid) {
+  if constexpr (KIND == OMB_KERNEL_MATERN52)
+    etab[tid] = kExp2Tab256[tid];
   else if (tid < 64)
     etab[tid] = kExp2Tab64[tid];
-  const int o = blockIdx.y;
-  const PathObj& po = pa.o[o];
-  const GPDev& g = po.g;
-  const int d = pa.d;
-  const int64_t col = (int64_t)blockIdx.x * 64 + 16 * wave + (lane & 15);
-  const int64_t ci = col < N ? col : N - 1;
-  double csq = 0.0;
+}
+
+// A lane's B fragments of candidate ci: the r² operand [−2·x/ℓ, 1, ‖x/ℓ‖²] (n_var ≤ 8) or x/ℓ, and the feature
+// operand [x/ℓ, 1]
+template <int DP>
+__device__ __forceinline__ void paths_operands(const GPDev& g, int d, const double* __restrict__ Xc, int64_t ci,
+                                               int lane, double& csq, double (&bfr)[PathsDims<DP>::KSD],
+                                               double (&bff)[PathsDims<DP>::KSF]) {
+  constexpr bool kAug = PathsDims<DP>::kAug;
+  constexpr int KSD = PathsDims<DP>::KSD, KSF = PathsDims<DP>::KSF;
+  csq = 0.0;
 #pragma unroll
   for (int j = 0; j < DP; ++j) {
     const double c = (j < d) ? Xc[ci * d + j] / g.ls[j] : 0.0;
     csq = fma(c, c, csq);
   }
-  double bfr[KSD];   // the r² operand: [−2·x/ℓ, 1, ‖x/ℓ‖²] (n_var ≤ 8) or x/ℓ
 #pragma unroll
   for (int s = 0; s < KSD; ++s) {
     const int j = 4 * s + (lane >> 4);
@@ -100,15 +104,26 @@ __global__ __launch_bounds__(256) void paths_eval_kernel(PathArgs pa, const doub
     else
       bfr[s] = c;
   }
-  double bff[KSF];   // the feature operand: [x/ℓ, 1]
 #pragma unroll
   for (int s = 0; s < KSF; ++s) {
     const int j = 4 * s + (lane >> 4);
     const double c = (j < d) ? Xc[ci * d + j] / g.ls[j] : 0.0;
     bff[s] = (j < d) ? c : (j == d ? 1.0 : 0.0);
   }
+}
+
+// The 16 paths × 16 candidates tile of a wave: features, then training rows (register e of the result: path
+// 4e + (lane >> 4) at the wave's candidate lane & 15)
+template <int DP, int KIND, bool LIBCOS>
+__device__ __forceinline__ d4 paths_tile(const PathObj& po, int lane, double csq,
+                                         const double (&bfr)[PathsDims<DP>::KSD],
+                                         const double (&bff)[PathsDims<DP>::KSF], const double* etab,
+                                         const ExpCoef& ec) {
+  constexpr bool kAug = PathsDims<DP>::kAug;
+  constexpr int KSD = PathsDims<DP>::KSD, KSDP = PathsDims<DP>::KSDP, KSF = PathsDims<DP>::KSF;
+  constexpr bool kTab256 = KIND == OMB_KERNEL_MATERN52;
+  const GPDev& g = po.g;
   const double pm[3] = {g.variance, kSqrt5 * g.variance, kFiveThirds * g.variance};
-  __syncthreads();
   d4 acc = d4{0.0, 0.0, 0.0, 0.0};
   // features
   for (int T = 0; T < po.MT; ++T) {
@@ -155,6 +170,24 @@ __global__ __launch_bounds__(256) void paths_eval_kernel(PathArgs pa, const doub
       acc = __builtin_amdgcn_mfma_f64_16x16x4f64(vv[e + 1], v1, acc, 0, 0, 0);
     }
   }
+  return acc;
+}
+
+template <int DP, int KIND, bool LIBCOS>
+__global__ __launch_bounds__(256) void paths_eval_kernel(PathArgs pa, const double* __restrict__ Xc, int64_t N,
+                                                         int64_t ld, double* __restrict__ out, ExpCoef ec) {
+  __shared__ double etab[KIND == OMB_KERNEL_MATERN52 ? 256 : 64];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  paths_stage_table<KIND>(etab, tid);
+  const int o = blockIdx.y;
+  const PathObj& po = pa.o[o];
+  const int64_t col = (int64_t)blockIdx.x * 64 + 16 * wave + (lane & 15);
+  const int64_t ci = col < N ? col : N - 1;
+  double csq, bfr[PathsDims<DP>::KSD], bff[PathsDims<DP>::KSF];
+  paths_operands<DP>(po.g, pa.d, Xc, ci, lane, csq, bfr, bff);
+  __syncthreads();
+  const d4 acc = paths_tile<DP, KIND, LIBCOS>(po, lane, csq, bfr, bff, etab, ec);
   if (col < N) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -162,6 +195,171 @@ __global__ __launch_bounds__(256) void paths_eval_kernel(PathArgs pa, const doub
       if (s < po.S) out[((int64_t)o * po.S + s) * ld + col] = acc[e];
     }
   }
+}
+
+// ---------------------------------------------------------------------------------------
+// omb_paths_min: the same tiles, the minimum of every path in the epilogue.  A (value, index) pair is better when
+// its value is smaller, else — at equal values — when its index is lower; index < 0 = none yet (NaN never enters).
+// The order is total, so the result does not depend on how the candidates are spread over lanes, waves and
+// workgroups.  Four stages, no atomics:
+//   1. a lane keeps the best pair of its column in every 64-column block its workgroup visits (grid-stride);
+//   2. the 16 candidate lanes of a path meet by xor shuffles, the workgroup's four waves through LDS in wave order;
+//   3. thread s < S writes the workgroup's pair of path s to partials[((o·16 + s)·nb + block)·2];
+//   4. paths_min_reduce_kernel, one workgroup per (objective, path), reduces the nb pairs and adds the offset.
+__device__ __forceinline__ bool min_better(double av, long long ai, double bv, long long bi) {
+  if (ai < 0) return false;
+  if (bi < 0) return true;
+  return (av < bv) || (av == bv && ai < bi);
+}
+
+template <int DP, int KIND, bool LIBCOS>
+__global__ __launch_bounds__(256) void paths_min_kernel(PathArgs pa, const double* __restrict__ Xc, int64_t N,
+                                                        double* __restrict__ partials, ExpCoef ec) {
+  __shared__ double etab[KIND == OMB_KERNEL_MATERN52 ? 256 : 64];
+  __shared__ double red_v[4 * 16];
+  __shared__ long long red_i[4 * 16];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  paths_stage_table<KIND>(etab, tid);
+  __syncthreads();
+  const int o = blockIdx.y;
+  const PathObj& po = pa.o[o];
+  double bv[4];
+  long long bi[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    bv[e] = HUGE_VAL;
+    bi[e] = -1;
+  }
+  const int64_t nblk = (N + 63) / 64;
+  for (int64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    const int64_t col = blk * 64 + 16 * wave + (lane & 15);
+    const int64_t ci = col < N ? col : N - 1;
+    double csq, bfr[PathsDims<DP>::KSD], bff[PathsDims<DP>::KSF];
+    paths_operands<DP>(po.g, pa.d, Xc, ci, lane, csq, bfr, bff);
+    const d4 acc = paths_tile<DP, KIND, LIBCOS>(po, lane, csq, bfr, bff, etab, ec);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const double v = acc[e];
+      const long long i = (col < N && v == v) ? (long long)col : -1;
+      if (min_better(v, i, bv[e], bi[e])) {
+        bv[e] = v;
+        bi[e] = i;
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) {
+      const double ov = __shfl_xor(bv[e], off);
+      const long long oi = __shfl_xor(bi[e], off);
+      if (min_better(ov, oi, bv[e], bi[e])) {
+        bv[e] = ov;
+        bi[e] = oi;
+      }
+    }
+    if ((lane & 15) == 0) {
+      red_v[16 * wave + 4 * e + (lane >> 4)] = bv[e];
+      red_i[16 * wave + 4 * e + (lane >> 4)] = bi[e];
+    }
+  }
+  __syncthreads();
+  if (tid < po.S) {
+    double v = red_v[tid];
+    long long i = red_i[tid];
+    for (int w = 1; w < 4; ++w)
+      if (min_better(red_v[16 * w + tid], red_i[16 * w + tid], v, i)) {
+        v = red_v[16 * w + tid];
+        i = red_i[16 * w + tid];
+      }
+    double* p = partials + (((int64_t)o * 16 + tid) * gridDim.x + blockIdx.x) * 2;
+    p[0] = i < 0 ? HUGE_VAL : v;
+    p[1] = (double)i;
+  }
+}
+
+// grid (S, n_obj): the nb pairs of one path → res[(o·S + s)·2 + {0, 1}] = {value, index + offset} or {+inf, −1}
+__global__ __launch_bounds__(256) void paths_min_reduce_kernel(const double* __restrict__ partials, int nb, int S,
+                                                               int64_t offset, double* __restrict__ res) {
+  __shared__ double red_v[4];
+  __shared__ long long red_i[4];
+  const int s = blockIdx.x, o = blockIdx.y, tid = threadIdx.x;
+  const double* p = partials + ((int64_t)o * 16 + s) * nb * 2;
+  double v = HUGE_VAL;
+  long long i = -1;
+  for (int b = tid; b < nb; b += 256) {
+    const double pv = p[2 * b];
+    const long long pi = (long long)p[2 * b + 1];
+    if (min_better(pv, pi, v, i)) {
+      v = pv;
+      i = pi;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const double ov = __shfl_xor(v, off);
+    const long long oi = __shfl_xor(i, off);
+    if (min_better(ov, oi, v, i)) {
+      v = ov;
+      i = oi;
+    }
+  }
+  if ((tid & 63) == 0) {
+    red_v[tid >> 6] = v;
+    red_i[tid >> 6] = i;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 4; ++w)
+      if (min_better(red_v[w], red_i[w], v, i)) {
+        v = red_v[w];
+        i = red_i[w];
+      }
+    double* r = res + ((int64_t)o * S + s) * 2;
+    r[0] = i < 0 ? HUGE_VAL : v;
+    r[1] = i < 0 ? -1.0 : (double)(i + offset);
+  }
+}
+
+int paths_min_blocks(int64_t N) {
+  const int64_t nblk = (N + 63) / 64;
+  return (int)(nblk < kPathsMinMaxBlocks ? nblk : kPathsMinMaxBlocks);
+}
+
+template <int KIND, bool LIBCOS>
+static hipError_t launch_paths_min_kind(hipStream_t stream, const PathArgs& pa, int n_obj, const double* Xc, int64_t N,
+                                        double* partials) {
+  const dim3 grid((unsigned)paths_min_blocks(N), (unsigned)n_obj);
+  switch (pa.DP) {
+#define OMB_PATHS(DPV)                                                                                          \
+  case DPV:                                                                                                     \
+    hipLaunchKernelGGL((paths_min_kernel<DPV, KIND, LIBCOS>), grid, dim3(256), 0, stream, pa, Xc, N, partials,  \
+                       exp_coef());                                                                             \
+    break;
+    OMB_PATHS(2) OMB_PATHS(4) OMB_PATHS(6) OMB_PATHS(8) OMB_PATHS(16) OMB_PATHS(32) OMB_PATHS(64)
+#undef OMB_PATHS
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_paths_min(hipStream_t stream, const PathArgs& pa, int n_obj, int kind, bool libcos, const double* Xc,
+                            int64_t N, int64_t offset, double* partials, double* res) {
+  const int nb = paths_min_blocks(N);
+  if (nb > 0) {
+    hipError_t e;
+    if (kind == OMB_KERNEL_RBF)
+      e = libcos ? launch_paths_min_kind<OMB_KERNEL_RBF, true>(stream, pa, n_obj, Xc, N, partials)
+                 : launch_paths_min_kind<OMB_KERNEL_RBF, false>(stream, pa, n_obj, Xc, N, partials);
+    else
+      e = libcos ? launch_paths_min_kind<OMB_KERNEL_MATERN52, true>(stream, pa, n_obj, Xc, N, partials)
+                 : launch_paths_min_kind<OMB_KERNEL_MATERN52, false>(stream, pa, n_obj, Xc, N, partials);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(paths_min_reduce_kernel, dim3((unsigned)pa.o[0].S, (unsigned)n_obj), dim3(256), 0, stream,
+                     partials, nb, pa.o[0].S, offset, res);
+  return hipGetLastError();
 }
 
 template <int KIND, bool LIBCOS>

@@ -317,6 +317,19 @@ class AcqContext:
                     "omb_log_feasibility")
         return out
 
+    def mes(self, mu, var, ystar, out=None):
+        """omb_mes: max-value entropy search over rows 0..k-1 of (mu, var) (1-D moments are taken as one row) and
+        the sampled minima ``ystar`` (k, S): Σ_j mean_s a((μ_j − y*_js)/σ_j), a(γ) = γφ/(2Φ) − log Φ."""
+        if mu.dim() == 1:
+            mu, var = mu.reshape(1, -1), var.reshape(1, -1)
+        k, N = mu.shape
+        ystar = _dev_f64(ystar, self.device).reshape(k, -1)
+        out = self._out(out, N)
+        self._stream()
+        self._check(self.lib.omb_mes(self._h, k, _ptr(mu), _ptr(var), mu.stride(0), N, _ptr(ystar), ystar.shape[1],
+                                     _ptr(out)), "omb_mes")
+        return out
+
     def argmax_dev(self, vals, offset=0, out=None):
         out = self._out(out, 2)
         self._stream()
@@ -340,7 +353,8 @@ class AcqContext:
         self.plan_kind = (fn, mode)
 
     # plans omb_eval_grad differentiates (include/optimobo_hip.h); EHVI-2D in "sigma" mode is not one
-    _GRAD_PLANS = ("omb_plan_ei", "omb_plan_ei_ext", "omb_plan_ehvi2d", "omb_plan_ehvi_boxes", "omb_plan_ehvi_boxes_k")
+    _GRAD_PLANS = ("omb_plan_ei", "omb_plan_ei_ext", "omb_plan_ehvi2d", "omb_plan_ehvi_boxes", "omb_plan_ehvi_boxes_k",
+                   "omb_plan_mes")
 
     def plan_has_gradient(self):
         """True when the plan last set through this context is one omb_eval_grad differentiates."""
@@ -387,6 +401,14 @@ class AcqContext:
 
     def plan_ei_ext(self, kind, k, best, var_eps=0.0, pof_eps=0.0):
         self._plan("omb_plan_ei_ext", _EI_KINDS[kind], int(k), float(best), float(var_eps), float(pof_eps))
+
+    def plan_mes(self, ystar):
+        """omb_plan_mes: ``mes`` as the chain's plan over objectives 0..k-1, ystar (k, S) on the host (a non-finite
+        entry is refused and leaves no plan)."""
+        y = np.ascontiguousarray(ystar, dtype=np.float64)
+        if y.ndim != 2:
+            raise ValueError(f"plan_mes: ystar {y.shape} is not (k, S)")
+        self._plan("omb_plan_mes", y.shape[0], y.shape[1], _lib.host_ptr(y))
 
     def plan_constraints(self, n_con, pof_eps=1e-5):
         """omb_plan_constraints: the plan that is set treats objective slots k..k+n_con-1 as constraint models
@@ -667,6 +689,23 @@ class AcqContext:
         self._stream()
         self._check(self.lib.omb_paths_eval(self._h, int(n_obj), _ptr(Xc), N, int(ld), _ptr(out)), "omb_paths_eval")
         return out
+
+    def paths_min(self, Xc, n_obj=None, offset=0):
+        """The minimum of every installed path of objectives 0..n_obj-1 over candidates Xc (N, d) (omb_paths_min):
+        (values (n_obj, S) fp64, indices (n_obj, S) int64 = the lowest arg-min + offset), bitwise
+        ``paths_eval(Xc).min(-1)`` without the (n_obj, S, N) matrix.  NaN never wins; an empty batch or an all-NaN
+        row gives (+inf, −1)."""
+        Xc = _dev_f64(Xc, self.device)
+        if Xc.shape[0]:
+            self._check_width(Xc)
+        n_obj = n_obj if n_obj is not None else len(self.gp_info)
+        res = torch.empty((max(1, int(n_obj)), 16, 2), dtype=torch.float64, device=self.device)   # S ≤ 16
+        self._stream()
+        self._check(self.lib.omb_paths_min(self._h, int(n_obj), _ptr(Xc), Xc.shape[0], int(offset), _ptr(res)),
+                    "omb_paths_min")
+        S = self._paths_S[0]
+        res = res.reshape(-1)[:2 * n_obj * S].reshape(n_obj, S, 2)
+        return res[:, :, 0].contiguous(), res[:, :, 1].to(torch.int64)
 
     def ea_search(self, pop, tape, best, lower, upper, mode=0, var_eps=1e-6):
         """ParEGO (mode 0: EI of objective 0) / KEEP (mode 1: μ of objective 1 · EI of objective 0)
