@@ -36,6 +36,7 @@ extern "C" {
                               (DP 128 / 256: GEMM-tiled cross terms over 16-dim slabs, the dense posterior) */
 #define OMB_MAX_TRAIN 1024 /* n_train handled by the fused posterior kernel */
 #define OMB_MAX_TRAIN_DENSE 16384 /* n_train of the GEMM-based posterior path used above OMB_MAX_TRAIN */
+#define OMB_HVI_PATHS_CHUNK 262144 /* candidates per pass of the fused chain under an omb_plan_hvi_paths plan */
 
 enum {
   OMB_OK = 0,
@@ -134,7 +135,10 @@ const char* omb_last_error(const omb_ctx* ctx);
  * kernel launched before it; 0 inside the posterior launch, by its mean-only workgroups.  μ is bit-identical.
  * omb_debug_set(ctx, OMB_DEBUG_PATHS_LIBCOS, 1) evaluates the sample paths' features (omb_paths_set, omb_paths_eval)
  * with the device library's cosine instead of the kernel's own reduction (default 0): the baseline the kernel's
- * cosine is measured against (tools/paths_timing.py); values agree to the cosines' rounding. */
+ * cosine is measured against (tools/paths_timing.py); values agree to the cosines' rounding.
+ * omb_debug_set(ctx, OMB_DEBUG_HVI_PATHS_CHUNK, c) sets the candidates per pass of the fused chain under an
+ * omb_plan_hvi_paths plan (default OMB_HVI_PATHS_CHUNK; 0: one pass over all N, whose workspace is the whole
+ * (k·S, N) matrix of path values).  Values and arg-max pairs are bit-identical for every c. */
 enum {
   OMB_DEBUG_SPIN_LIMIT = 1,
   OMB_DEBUG_COV_TABLE = 2,
@@ -148,7 +152,8 @@ enum {
   OMB_DEBUG_BOXES_KD = 11,
   OMB_DEBUG_POSTERIOR_ALL_VAR = 12,
   OMB_DEBUG_POSTERIOR_MEAN_KERNEL = 13,
-  OMB_DEBUG_PATHS_LIBCOS = 14
+  OMB_DEBUG_PATHS_LIBCOS = 14,
+  OMB_DEBUG_HVI_PATHS_CHUNK = 15
 };
 int omb_debug_set(omb_ctx* ctx, int what, int64_t value);
 
@@ -240,6 +245,30 @@ int omb_ehvi_boxes_k(omb_ctx* ctx, int k, const double* mu_dev, const double* va
  * past the grid reads the grid's last coordinate. */
 int omb_hvi_boxes(omb_ctx* ctx, int k, const double* y_dev, int64_t ld, int64_t N, const double* coords_dev, int C,
                   const uint16_t* boxes_dev, int B, double* out_dev);
+
+/* The mean hypervolume improvement over S sampled fronts: the Monte-Carlo integrand of the noisy EHVI (Daulton et al.
+ * 2021) and, at k = 1, of the noisy EI (Letham et al. 2019), everything minimised.  Posterior sample path s
+ * (omb_paths_set) evaluated at the training inputs gives a draw of the latent values there, hence a front (k = 1: a
+ * best value b_s) and a box decomposition of its own; the same path at candidate i is jointly distributed with it:
+ *   t_s(i) = Σ_{b in list s} Π_j (hi_bj − max(y_{j,s,i}, lo_bj))⁺,   out_dev[i] = ((…((0 + t_0) + t_1) + …) + t_{S−1}) / S
+ * y_dev is omb_paths_eval's output: path s of objective j is row j·S + s, pitch ld ≥ N.  List s is rows
+ * box_off_host[s] .. box_off_host[s+1] of boxes_dev (box_off_host: S + 1 HOST ints from 0; (box_off[S], 2k) uint16
+ * index pairs, 4-byte aligned), over the grid coords_dev + s·k·C — the S grids (S, k, C), each with a leading −∞
+ * column and padded with its last coordinate exactly like one omb_hvi_boxes grid.  At k = 1 list s is the single box
+ * (−∞, b_s]: t_s = (b_s − y)⁺.  t_s is bitwise omb_hvi_boxes' value of list s on rows {j·S + s} (slices of 1024 boxes
+ * counted from the list's own start, added in slice order); the paths are added in path order from 0.0 and the sum
+ * divided once by S, unfused.  One lane per candidate; LDS holds the current path's k·C grid doubles; no atomics; a
+ * candidate's value is bitwise the same whatever N, its column or the launch shape (a small batch gives every path a
+ * workgroup row of its own and adds the stored t_s in the same order).  1 ≤ S ≤ 16: one path install.  Asynchronous.
+ *   a NaN coordinate in any path: NaN for that candidate; y_j ≥ r_j in every path: exactly 0
+ *   OMB_EINVAL  k outside [1, OMB_MAX_OBJ], S outside [1, 16], N < 0, a null grid / box list / offsets, offsets not
+ *               increasing from 0 (an empty list included), a null y / out with N > 0, a pointer off its alignment
+ *               (8 bytes; the box list 4), ld < N
+ *   OMB_EUNSUP  C < 2, k·C > 8192 (one grid in 64 KiB of LDS), box_off[S] > 2^24
+ * in that order; N = 0 returns OMB_OK and writes nothing.  Indices are not checked (the lists are on the device); one
+ * past the grid reads the grid's last coordinate.  omb_hvi_boxes itself stays k ≥ 2. */
+int omb_hvi_paths(omb_ctx* ctx, int k, int S, const double* y_dev, int64_t ld, int64_t N, const double* coords_dev,
+                  int C, const int32_t* box_off_host, const uint16_t* boxes_dev, double* out_dev);
 
 /* Hypervolume-based PoI of EMO (emo.py:176-228): cells_dev (C, 2, 2) [upper, lower]. */
 int omb_hvpoi(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
@@ -367,6 +396,23 @@ int omb_plan_ei_ext(omb_ctx* ctx, int kind, int k, double best, double var_eps, 
  * q = φ/Φ.  omb_plan_constraints applies as to every plan; omb_plan_log answers OMB_EUNSUP. */
 int omb_plan_mes(omb_ctx* ctx, int k, int S, const double* ystar_host);
 
+/* omb_hvi_paths as a plan of the fused chain over objectives 0..k-1: coords_host (S, k, C), box_off_host (S + 1),
+ * boxes_host (box_off[S], 2k), all on the host and held to omb_hvi_paths' checks; every list's indices are checked
+ * as omb_plan_ehvi_boxes_k checks its list (OMB_EINVAL, no plan left).  Under this plan the chain's posterior stage is
+ * the evaluation of the installed sample paths: [Sobol →] omb_paths_eval(0..k-1) → omb_hvi_paths → [arg-max], in
+ * passes of OMB_HVI_PATHS_CHUNK candidates, so the workspace holds (k·S, chunk) path values, not (k·S, N); values are
+ * bitwise omb_paths_eval → omb_hvi_paths on the same points, whatever the chunk.  omb_timing's "posterior" interval
+ * is the path evaluation (with several passes it ends after the last pass's, and so holds the earlier passes'
+ * acquisition launches).  Before anything is launched the eval calls return OMB_ESTATE, naming omb_paths_set, when an
+ * objective of 0..k-1 has no GP, has no paths, or holds another number of paths than the plan's S — omb_set_gp,
+ * omb_gp_fit_state and omb_gp_append drop an objective's paths, so a plan over a changed state is refused, never
+ * evaluated; omb_paths_eval's OMB_EUNSUP (n_var > 64, n_train > OMB_MAX_TRAIN_DENSE) applies.  omb_eval_grad returns
+ * OMB_EUNSUP (no analytic gradient through the paths), as do omb_plan_log and omb_plan_constraints with n_con > 0 (the
+ * weight would need a posterior of the constraint slots, which this chain does not compute); each names the plan and
+ * leaves it as it was. */
+int omb_plan_hvi_paths(omb_ctx* ctx, int k, int S, const double* coords_host, int C, const int32_t* box_off_host,
+                       const uint16_t* boxes_host);
+
 /* Inequality constraints on the plan that is set (g ≤ 0 feasible).  From here on omb_eval, omb_eval_argmax,
  * omb_eval_argmax_sobol and omb_eval_grad also compute the posterior (μ and σ²) of context slots k..k+n_con−1 — the
  * constraint models, set like objectives with omb_set_gp / omb_gp_fit_state — and multiply the acquisition by their
@@ -387,7 +433,8 @@ int omb_plan_constraints(omb_ctx* ctx, int n_con, double pof_eps);
  * omb_plan_constraints; with both, the chain adds log F (omb_log_feasibility) in place of the multiplication by F.
  * The posterior's variance mask is the linear plan's.  Errors, in this order, each leaving the plan as it was:
  * OMB_ESTATE with no plan; OMB_EINVAL for `on` outside {0, 1}; OMB_EUNSUP, naming the plan, for Pareto EI, EHVI-2D
- * (any mode), Monte-Carlo EHVI, HV-PoI, expected decomposition and max-value entropy search.
+ * (any mode), Monte-Carlo EHVI, HV-PoI, expected decomposition, max-value entropy search and the sampled-front
+ * improvement (omb_plan_hvi_paths).
  * omb_eval_grad on a log plan: log EI (plain or constrained, with or without omb_plan_constraints) is analytic —
  *   ∂/∂μ = −ρ/(σ + 1e-10),  ∂/∂σ² = (1/σ − ρ·γ/(σ + 1e-10))/(2σ),  ρ = Φ(γ)/h(γ) = R/T for γ < 0,
  *   a constraint row: ∂ log Φ(z)/∂z = φ(z)/Φ(z) = 1/R(z) times ∂z/∂μ, ∂z/∂σ² —

@@ -33,7 +33,9 @@ DEBUG_BOXES_KD = 11
 DEBUG_POSTERIOR_ALL_VAR = 12
 DEBUG_POSTERIOR_MEAN_KERNEL = 13
 DEBUG_PATHS_LIBCOS = 14
+DEBUG_HVI_PATHS_CHUNK = 15
 MAX_OBJ, MAX_DIM, MAX_TRAIN, MAX_TRAIN_DENSE = 8, 256, 1024, 16384
+HVI_PATHS_CHUNK = 1 << 18      # OMB_HVI_PATHS_CHUNK: candidates per pass of the chain under plan_hvi_paths
 
 _p = ctypes.c_void_p
 _d = ctypes.c_double
@@ -60,6 +62,7 @@ SIGNATURES = {
     "omb_ehvi_boxes": (_i, [_p, _i, _p, _p, _i64, _i64, _p, _i, _p, _i, _p]),
     "omb_ehvi_boxes_k": (_i, [_p, _i, _p, _p, _i64, _i64, _p, _i, _p, _i, _p]),
     "omb_hvi_boxes": (_i, [_p, _i, _p, _i64, _i64, _p, _i, _p, _i, _p]),
+    "omb_hvi_paths": (_i, [_p, _i, _i, _p, _i64, _i64, _p, _i, _p, _p, _p]),
     "omb_hvpoi": (_i, [_p, _p, _p, _i64, _i64, _p, _i, _p]),
     "omb_expdec": (_i, [_p, _i, _p, _p, _i64, _i64, _p, _i, _i, _dp, _dp, _dp, _dp, _d, _p]),
     "omb_ei": (_i, [_p, _p, _p, _i64, _d, _d, _p]),
@@ -84,6 +87,7 @@ SIGNATURES = {
     "omb_plan_ei": (_i, [_p, _d, _d]),
     "omb_plan_ei_ext": (_i, [_p, _i, _i, _d, _d, _d]),
     "omb_plan_mes": (_i, [_p, _i, _i, _p]),
+    "omb_plan_hvi_paths": (_i, [_p, _i, _i, _p, _i, _p, _p]),
     "omb_plan_constraints": (_i, [_p, _i, _d]),
     "omb_plan_log": (_i, [_p, _i]),
     "omb_set_sobol": (_i, [_p, _i, _i, _p, _p, _dp, _dp]),

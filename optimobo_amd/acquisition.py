@@ -40,6 +40,8 @@ class AcquisitionEngine:
         self.condition_jitter = 0.0
         self.paths_floored = 0
         self.ystar = None       # sample_minima's last result (n_obj, S)
+        self._front_lists = None    # sample_fronts' packed box lists (coords, box_off, boxes)
+        self._cond_X = []           # rows ``condition`` appended to every resident state since the last upload
         self.n_obj = 0
 
     # ------------------------------------------------------------------ model state
@@ -48,6 +50,7 @@ class AcquisitionEngine:
             st = _state_of(m)
             if self._resident.get(o) is not st or o in self._stale:
                 self.ctx.set_gp_state(o, st)
+                self._cond_X = []
                 self._resident[o] = st
                 self._stale.discard(o)
         self.n_obj = len(models)
@@ -95,6 +98,7 @@ class AcquisitionEngine:
                     if e.code != OMB_ENOTPD or t == 4:
                         raise
             self.condition_jitter = max(self.condition_jitter, extra)
+        self._cond_X.append(Xnew)
         return mus
 
     def _dev(self, x):
@@ -147,6 +151,7 @@ class AcquisitionEngine:
             raise RuntimeError("sample_paths: no models loaded (call load_models first)")
         rng = np.random.default_rng(seed)
         self.paths_floored = 0      # (model, dimension) pairs whose lengthscale was below the features' floor
+        self._front_lists = None    # fronts of the previous paths say nothing about these
         for o in range(self.n_obj):
             st = self._resident[o]
             info = self.ctx.gp_info[o]
@@ -233,6 +238,61 @@ class AcquisitionEngine:
     def plan_mes(self, ystar=None):
         """``mes`` as the fused chain's plan (None: the last ``sample_minima`` result); ``has_gradient`` is True."""
         self.ctx.plan_mes(self._ystar(ystar, "plan_mes"))
+
+    def sample_fronts(self, S, max_point, lower, upper, seed=0, n_features=1024, max_boxes=1 << 20):
+        """S fresh posterior sample paths of every loaded model, evaluated at the training inputs: S draws of the latent
+        objective values there and so S fronts, the integration set of the noisy EHVI (one model: S best values, the
+        noisy EI's).  The paths are latent — no observation noise is added at X.
+
+        ``sample_paths(S, n_features, seed, lower=…, upper=…)`` (1 ≤ S ≤ 16: one path install), then ``path_values``
+        at the resident training inputs, which the models must share (ValueError otherwise: a front needs every
+        objective at the same rows), and at the rows ``condition`` has appended since.  Per path ``pareto.calc_pf`` and ``pareto.box_decomposition(PF_s, max_point,
+        max_boxes)`` (``pareto.BoxBudgetError`` propagates); with one model, ``max_point`` is None and the lists are
+        ``pareto.threshold_lists`` of the paths' minima over the training inputs (``AcqContext.paths_min``).  The
+        packed lists (``pareto.pack_box_lists``) are kept on the engine for ``nehvi`` / ``plan_nehvi``, which hold
+        while the paths do: until a model is loaded or conditioned.  Returns the list of fronts (S arrays (P_s, k)),
+        or b (S,) for one model."""
+        S = int(S)
+        if not 1 <= S <= 16:
+            raise ValueError(f"sample_fronts: S={S} outside [1, 16] (one path install)")
+        k = self.n_obj
+        if k < 1:
+            raise RuntimeError("sample_fronts: no models loaded (call load_models first)")
+        if any(not np.array_equal(self._resident[o].X, self._resident[0].X) for o in range(1, k)):
+            raise ValueError("sample_fronts: the loaded models do not share their training inputs (a front needs every "
+                             "objective at the same rows)")
+        if (k == 1) != (max_point is None):
+            raise ValueError("sample_fronts: one model takes max_point=None (noisy EI's thresholds), several models "
+                             "need the reference point")
+        self._front_lists = None
+        self.sample_paths(S, n_features=n_features, seed=seed, lower=lower, upper=upper)
+        # the rows the device states hold: the fitted ones and, inside a believer batch, the fantasies behind them
+        Xt = self._dev(np.vstack([self._resident[0].X] + self._cond_X))
+        if k == 1:
+            out = self.ctx.paths_min(Xt, 1)[0][0].cpu().numpy()
+            decomps = pareto.threshold_lists(out)
+        else:
+            F = self.path_values(Xt).cpu().numpy()                  # (k, S, n)
+            out = [pareto.calc_pf(np.ascontiguousarray(F[:, s, :].T)) for s in range(S)]
+            decomps = [pareto.box_decomposition(pf, max_point, max_boxes=max_boxes) for pf in out]
+        self._front_lists = pareto.pack_box_lists(decomps)
+        return out
+
+    def _fronts(self, what):
+        lists = self._front_lists
+        if lists is None:
+            raise RuntimeError(f"{what}: no sampled fronts (call sample_fronts first)")
+        return lists
+
+    def nehvi(self, Xc):
+        """Noisy EHVI (one model: noisy EI) on every row of Xc: the mean over the fronts of the last ``sample_fronts``
+        of the hypervolume improvement of each path's value at the candidate (``path_values`` → ``hvi_paths``)."""
+        lists = self._fronts("nehvi")
+        return self.ctx.hvi_paths(self.path_values(Xc)[:lists[0].shape[1]], *lists)
+
+    def plan_nehvi(self):
+        """``nehvi`` as the fused chain's plan; ``has_gradient`` is False, so ``polish="auto"`` takes the stencil."""
+        self.ctx.plan_hvi_paths(*self._fronts("plan_nehvi"))
 
     def thompson_batch(self, q, lower, upper, PF=None, max_point=None, n_candidates=None, seed=0,
                        max_boxes=1 << 20, sampler="joint", n_features=1024, refine_rounds=0, shrink=0.1,

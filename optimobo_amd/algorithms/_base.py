@@ -89,7 +89,10 @@ class BODriver:
         # the acquisition of every pick (not in the reference): None is the driver's own (EHVI / expected decomposition
         # / EI), call for call; "mes" is max-value entropy search — MESMO over MultiSurrogateOptimiser's objectives, MES
         # on MonoSurrogateOptimiser's scalarised surrogate — from ``mes_samples`` posterior sample paths per pick, each
-        # minimised over ``mes_candidates`` Sobol' points and the training inputs (AcquisitionEngine.sample_minima)
+        # minimised over ``mes_candidates`` Sobol' points and the training inputs (AcquisitionEngine.sample_minima);
+        # "nehvi" (MultiSurrogateOptimiser) / "nei" (MonoSurrogateOptimiser) are the noisy EHVI / EI: the improvement
+        # averaged over ``nehvi_samples`` fronts (best values) drawn from the posterior at the points already evaluated,
+        # in place of the improvement over the observed — noisy — front (AcquisitionEngine.sample_fronts)
         self.acquisition = self._check_acquisition(acquisition, mes_samples, mes_candidates)
         self.thompson_fallbacks = 0   # Thompson iterations that fell back to the believer batch
         self._iteration = 0
@@ -124,19 +127,27 @@ class BODriver:
                              "plans an acquisition without a log form)")
         return True
 
-    # acquisition="mes": MultiSurrogateOptimiser (acquisition_func=None) and MonoSurrogateOptimiser
+    # acquisition="mes": MultiSurrogateOptimiser (acquisition_func=None) and MonoSurrogateOptimiser; "nehvi": the
+    # former, "nei": the latter
     _acquisitions = ()
     mes_features = 1024          # random Fourier features per model of a pick's sample paths
+    nehvi_samples = 16           # sampled fronts (paths per model) of a noisy-EHVI / noisy-EI pick: 1..16, one install
+    nehvi_features = 1024        # random Fourier features per model of those paths
 
     def _check_acquisition(self, acquisition, mes_samples, mes_candidates):
         self.mes_samples, self.mes_candidates = mes_samples, mes_candidates
         if acquisition is None:
             return None
-        if acquisition != "mes":
-            raise ValueError(f"acquisition must be None or 'mes', not {acquisition!r}")
+        if not isinstance(acquisition, str) or acquisition not in ("mes", "nehvi", "nei"):
+            raise ValueError(f"acquisition must be None or 'mes', 'nehvi' or 'nei', not {acquisition!r}")
         if acquisition not in self._acquisitions:
-            raise ValueError(f"{type(self).__name__} does not support acquisition='mes' (MultiSurrogateOptimiser and "
-                             "MonoSurrogateOptimiser do)")
+            if acquisition == "mes":
+                raise ValueError(f"{type(self).__name__} does not support acquisition='mes' (MultiSurrogateOptimiser "
+                                 "and MonoSurrogateOptimiser do)")
+            raise ValueError(f"{type(self).__name__} does not support acquisition={acquisition!r} ('nehvi' is "
+                             "MultiSurrogateOptimiser's, 'nei' MonoSurrogateOptimiser's)")
+        if acquisition != "mes":
+            return self._check_noisy_acquisition(acquisition)
         if self.batch_strategy == "thompson":
             raise ValueError("acquisition='mes' does not support batch_strategy='thompson' (a Thompson batch maximises "
                              "no acquisition; 'believer' batches take it)")
@@ -151,6 +162,34 @@ class BODriver:
             raise ValueError(f"mes_candidates must be an integer >= 1, not {mes_candidates!r}")
         self.mes_samples, self.mes_candidates = int(mes_samples), int(mes_candidates)
         return "mes"
+
+    def _check_noisy_acquisition(self, acquisition):
+        if self.constraints == "pof":
+            raise ValueError(f"acquisition={acquisition!r} does not support constraints='pof' (the sampled-front plan "
+                             "computes no posterior for the constraint models to weight it with)")
+        if self.batch_strategy == "thompson":
+            raise ValueError(f"acquisition={acquisition!r} does not support batch_strategy='thompson' (a Thompson "
+                             "batch maximises no acquisition; 'believer' batches take it)")
+        if self.log_acquisition:
+            raise ValueError(f"acquisition={acquisition!r} does not support log_acquisition=True (the mean over "
+                             "sampled fronts has no log form)")
+        if self.n_vars > 64:
+            raise ValueError(f"acquisition={acquisition!r} samples posterior paths, which need n_var <= 64 "
+                             f"(n_var={self.n_vars})")
+        return acquisition
+
+    def _plan_nehvi(self, eng, k):
+        """The noisy-EHVI (k = 1: noisy-EI) plan of one pick on ``eng`` over its ``k`` models: ``nehvi_samples`` fresh
+        sample paths (a seed of their own per pick, derived as ``_plan_mes`` derives it, on the same counter), their
+        fronts at the training inputs, the plan.  ``eng.condition`` drops the paths, so a believer batch samples again
+        for every pick, from the conditioned state.  ``pareto.BoxBudgetError`` (n_obj ≥ 4, a front past
+        ``exact_max_boxes``) propagates."""
+        base = self.seed if self.seed is not None else np.random.randint(0, 2 ** 31 - 1)
+        self._mes_picks += 1
+        eng.sample_fronts(self.nehvi_samples, self.max_point if k > 1 else None, self.test_problem.xl,
+                          self.test_problem.xu, seed=base + 15485863 + 7919 * self._mes_picks,
+                          n_features=self.nehvi_features, max_boxes=getattr(self, "exact_max_boxes", 1 << 20))
+        eng.plan_nehvi()
 
     def _plan_mes(self, eng, k):
         """The MES plan of one pick on ``eng`` over its first ``k`` models: fresh sample paths (a seed of their own

@@ -33,7 +33,7 @@ class MultiSurrogateOptimiser(BODriver):
     _pof_objective_models = "n_obj"
     _batch_strategies = ("believer", "thompson")
     _log_acquisition_modes = ("textbook",)     # the exact EHVI over boxes; reference mode plans EHVI-2D / Monte-Carlo
-    _acquisitions = ("mes",)                   # MESMO in place of EHVI, in either mode
+    _acquisitions = ("mes", "nehvi")           # MESMO / the noisy EHVI in place of EHVI, in either mode
 
     def _get_cached_samples(self, dimensions, sample_exponent):
         """optimisers.py:121-141 — scrambled Sobol mapped through the normal ppf."""
@@ -51,6 +51,9 @@ class MultiSurrogateOptimiser(BODriver):
         """The EHVI plan of one proposal on ``eng``: 2-D, Monte-Carlo or exact, as mode and n_obj ask."""
         if self.acquisition == "mes":
             self._plan_mes(eng, self.n_obj)             # acquisition="mes": MESMO over the objectives' sampled minima
+            return
+        if self.acquisition == "nehvi":
+            self._plan_nehvi(eng, self.n_obj)           # the noisy EHVI: fronts sampled at the training inputs, not pf
             return
         mc = function == "EHVI_3D" or self.n_obj >= 3          # optimisers.py:245-248: EHVI_3D for n_obj != 2
         if self.log_acquisition and self.n_obj <= 3:
@@ -101,9 +104,9 @@ class MultiSurrogateOptimiser(BODriver):
         With ``constraints="pof"``: ``_solve_pof``, which returns a ``Constrained_Res``.
         With ``log_acquisition=True`` (textbook mode, ``acquisition_func`` None) every pick maximises the logarithm
         of the exact EHVI (plus log F under ``constraints="pof"``; log F alone while no row is feasible)."""
-        if self.acquisition == "mes" and acquisition_func is not None:
-            raise ValueError("acquisition='mes' takes the place of the EHVI (acquisition_func=None), not of a "
-                             "scalarised expected decomposition")
+        if self.acquisition is not None and acquisition_func is not None:
+            raise ValueError(f"acquisition={self.acquisition!r} takes the place of the EHVI (acquisition_func=None), "
+                             "not of a scalarised expected decomposition")
         if self.log_acquisition and acquisition_func is not None:
             raise ValueError("log_acquisition=True takes the exact EHVI (acquisition_func=None): the expected "
                              "decomposition has no log form")
@@ -249,13 +252,16 @@ class MonoSurrogateOptimiser(BODriver):
     _pof_objective_models = 1
     _batch_strategies = ("believer", "thompson")
     _log_acquisition_modes = ("reference", "textbook")     # EI either way
-    _acquisitions = ("mes",)                               # MES on the scalarised surrogate, in place of EI
+    _acquisitions = ("mes", "nei")                         # MES / the noisy EI on the scalarised surrogate, in place of EI
 
     def _plan_ei(self, eng, best):
         """EI against ``best`` on ``eng``; its logarithm with ``log_acquisition``.  acquisition="mes": max-value
         entropy search on the surrogate instead (``best`` is not used: the sampled minima take its place)."""
         if self.acquisition == "mes":
             self._plan_mes(eng, 1)
+            return
+        if self.acquisition == "nei":
+            self._plan_nehvi(eng, 1)                   # the noisy EI: ``best`` is not used, every path brings its own
             return
         eng.plan_ei(best, 0.0)
         if self.log_acquisition:

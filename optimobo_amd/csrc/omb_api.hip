@@ -36,14 +36,17 @@ struct ObjState {
 // One acquisition request.  A describe_* function validates the scalar arguments and fills everything but geo / boxes;
 // a stand-alone entry then points those at the caller's device arrays, an omb_plan_* entry uploads the host geometry
 // and points them at ctx->geo (the fused chain's plan).  launch_acq / launch_acq_grad run it.
-enum PlanKind { PLAN_NONE = 0, PLAN_EHVI2D, PLAN_EHVI_MC, PLAN_EHVI_BOXES, PLAN_HVPOI, PLAN_EXPDEC, PLAN_EI, PLAN_MES };
+enum PlanKind { PLAN_NONE = 0, PLAN_EHVI2D, PLAN_EHVI_MC, PLAN_EHVI_BOXES, PLAN_HVPOI, PLAN_EXPDEC, PLAN_EI, PLAN_MES,
+                PLAN_HVI_PATHS };
 
 struct Plan {
   int kind = PLAN_NONE;
   int k = 0;                    // objectives the acquisition reads (posterior of 0..k-1)
   unsigned var_mask = 0;        // bit o: the plan's kernel loads σ² of objective o (the others' is never computed)
   int P = 0, M = 0, C = 0, B = 0, mode = 0;
-  int S = 0;                    // PLAN_MES: sampled minima per objective (geo: ystar (k, S))
+  int S = 0;                    // PLAN_MES: sampled minima per objective (geo: ystar (k, S)); PLAN_HVI_PATHS: paths
+  int32_t box_off[kPathsMaxS + 1] = {};   // PLAN_HVI_PATHS: list s is rows box_off[s]..box_off[s+1] of boxes (geo: the
+                                          // S grids (S, k, C))
   double r[OMB_MAX_OBJ] = {};
   double s00 = 0, s01 = 0, hv = 0, best = 0, var_eps = 0, pof_eps = 0;
   int ei_kind = OMB_EI_PLAIN;
@@ -127,6 +130,7 @@ struct omb_ctx {
   int select_seq = 0;            // OMB_DEBUG_SELECT_SEQ: the sequential greedy walk for B ≤ 64 too
   int boxes_kd_wave = 0;         // OMB_DEBUG_BOXES_KD: omb_ehvi_boxes_k by one wavefront per candidate where that fits
   int paths_libcos = 0;          // OMB_DEBUG_PATHS_LIBCOS: the sample paths' features through the library cosine
+  int hvi_paths_chunk = (int)kHviPathsChunk;   // OMB_DEBUG_HVI_PATHS_CHUNK: candidates per pass of a sampled-front chain
   int posterior_all_var = 0;     // OMB_DEBUG_POSTERIOR_ALL_VAR: the chain computes σ² of every objective
   int posterior_mean_kernel = kMeanKernelAfter;   // OMB_DEBUG_POSTERIOR_MEAN_KERNEL: masked objectives' μ in a launch of its own
 };
@@ -318,6 +322,33 @@ int describe_mes(omb_ctx* ctx, int k, int S, Plan* pl) {
   return OMB_OK;
 }
 
+// omb_hvi_paths / omb_plan_hvi_paths: every argument of the stand-alone entry; the plan entry passes y = out = null,
+// N = 0 and its host arrays.  The offsets are kept in the Plan (the launch takes them from the host).
+int describe_hvi_paths(omb_ctx* ctx, int k, int S, const void* y, int64_t ld, int64_t N, const void* coords, int C,
+                       const int32_t* box_off, const void* boxes, const void* out, Plan* pl) {
+  int rc = check_hvi_paths(E(ctx), k, S, y, ld, N, coords, C, box_off, boxes, out);
+  if (rc) return rc;
+  pl->kind = PLAN_HVI_PATHS;
+  pl->k = k;
+  pl->var_mask = 0u;   // no posterior moment is read: the chain evaluates the paths instead
+  pl->S = S;
+  pl->C = C;
+  for (int s = 0; s <= kPathsMaxS; ++s) pl->box_off[s] = box_off[s < S ? s : S];
+  return OMB_OK;
+}
+
+// The described sampled-front improvement over path values y (k·S rows at pitch ld), N > 0: the only place that
+// launches hvi_paths_kernel (the stand-alone entry and the chain's chunks).
+int run_hvi_paths(omb_ctx* ctx, const Plan& pl, const double* y, int64_t ld, int64_t N, double* out, const char* where) {
+  const int64_t wsd = hvi_paths_ws_doubles(N, pl.S);
+  int rc;
+  if (wsd && (rc = grow_dev(ctx, ctx->hws, sizeof(double) * (size_t)wsd, "HVI path workspace"))) return rc;
+  hipError_t e = launch_hvi_paths(ctx->stream, pl.k, pl.S, y, ld, N, pl.geo, pl.C, pl.boxes, pl.box_off, out,
+                                  wsd ? ctx->hws.as<double>() : nullptr);
+  if (e != hipSuccess) return hip_fail(ctx, e, where);
+  return OMB_OK;
+}
+
 // omb_ehvi_boxes_k's kernel: candidate-blocked, or (OMB_DEBUG_BOXES_KD = 1, where its tables fit) the baseline
 hipError_t launch_boxes_k(omb_ctx* ctx, int k, const double* mu, const double* var, int64_t ld, int64_t N,
                           const double* coords, int C, const uint16_t* boxes, int B, double* out) {
@@ -384,6 +415,7 @@ int launch_acq_grad(omb_ctx* ctx, const Plan& pl, const double* mu, const double
     case PLAN_EHVI_MC: unsup = "Monte-Carlo EHVI"; break;
     case PLAN_EXPDEC: unsup = "expected decomposition"; break;
     case PLAN_HVPOI: unsup = "HV-PoI"; break;
+    case PLAN_HVI_PATHS: unsup = "sampled-front improvement (noisy EHVI / EI)"; break;
     default:
       return fail(ctx, OMB_ESTATE, "corrupt plan");
   }
@@ -462,7 +494,37 @@ void gather_Ld(omb_ctx* ctx, int n_obj, const double** Ld) {
   for (int o = 0; o < n_obj; ++o) Ld[o] = ctx->obj[o].Ld;
 }
 
-// The fused chain: [Sobol →] posterior(0..k-1) → planned acquisition → [arg-max].  The posterior computes σ² of the
+// A sampled-front plan's state checks, before anything is launched, and its path arguments: every objective of
+// 0..k-1 holds a GP and exactly the plan's S sample paths (install_gp drops them, so a plan over a changed state is
+// refused here, never evaluated), within omb_paths_eval's limits.
+int chain_paths(omb_ctx* ctx, const Plan& pl, PathArgs* pa) {
+  PathsObjInfo info[OMB_MAX_OBJ];
+  for (int o = 0; o < OMB_MAX_OBJ; ++o) {
+    const ObjState& s = ctx->obj[o];
+    info[o] = PathsObjInfo{s.set ? 1 : 0, s.d, s.n, s.path_S};
+  }
+  for (int o = 0; o < pl.k; ++o) {
+    const ObjState& s = ctx->obj[o];
+    if (!s.set)
+      return fail(ctx, OMB_ESTATE, "objective %d has no GP state (call omb_set_gp, then omb_paths_set)", o);
+    if (s.path_S < 1) return fail(ctx, OMB_ESTATE, "objective %d has no sample paths (call omb_paths_set)", o);
+    if (s.path_S != pl.S)
+      return fail(ctx, OMB_ESTATE, "objective %d holds %d sample paths, the plan has %d fronts (call omb_paths_set)",
+                  o, s.path_S, pl.S);
+  }
+  int rc = check_paths_eval(E(ctx), pl.k, nullptr, 0, 0, nullptr, info);   // what is left: omb_paths_eval's OMB_EUNSUP
+  if (rc) return rc;
+  for (int o = 0; o < pl.k; ++o) {
+    const ObjState& s = ctx->obj[o];
+    pa->o[o] = PathObj{s.dev, s.path_Of, s.path_Wf, s.path_Vf, s.path_MT, s.R, s.path_S, 0};
+  }
+  pa->d = ctx->obj[0].d;
+  pa->DP = ctx->obj[0].DP;
+  return OMB_OK;
+}
+
+// The fused chain: [Sobol →] posterior(0..k-1) → planned acquisition → [arg-max].  Under a sampled-front plan
+// (PLAN_HVI_PATHS) the posterior stage is the evaluation of the installed sample paths, in passes of Nc candidates.  The posterior computes σ² of the
 // objectives in the plan's var_mask only (the others' slots of the workspace keep whatever they held); all_var (the
 // gradient chain, which reads every σ² afterwards, and OMB_DEBUG_POSTERIOR_ALL_VAR) computes all of them.
 int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t N, int64_t offset, double* vals_out,
@@ -472,6 +534,9 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
   const Plan& pl = ctx->plan;
   if (pl.kind == PLAN_NONE) return fail(ctx, OMB_ESTATE, "no acquisition plan (call an omb_plan_* function)");
   if (N < 0) return fail(ctx, OMB_EINVAL, "N=%lld < 0", (long long)N);
+  const bool paths = pl.kind == PLAN_HVI_PATHS;   // the posterior stage is the evaluation of the sample paths
+  PathArgs pa{};
+  if (paths && (rc = chain_paths(ctx, pl, &pa))) return rc;
   GPArgs args;
   int max_R = 0;
   if ((rc = gather_gp(ctx, pl.k + pl.n_con, &args, &max_R))) return rc;
@@ -493,13 +558,23 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
   // per-workgroup pairs (≤ kArgmaxMaxBlocks) go to ctx->partials
   const bool acq_argmax = result_dev && !vals_out && N > 0 && ctx->fused_chain && pl.kind == PLAN_EHVI2D &&
                           pl.n_con == 0;   // the weight comes between EHVI and the arg-max: the plain path
-  const size_t doubles = 2 * (size_t)K * nd + nd + (nd + 1) / 2 + (sobol ? nd * args.d : 0);
+  // a sampled-front plan holds the (k·S, Nc) path values of one pass over Nc candidates in place of μ | σ² (K, N):
+  // both of its kernels are per-candidate functions, so the values do not depend on the chunk
+  const int64_t Nc = (paths && ctx->hvi_paths_chunk > 0 && ctx->hvi_paths_chunk < N) ? ctx->hvi_paths_chunk : N;
+  const size_t head = paths ? (size_t)k * pl.S * (size_t)Nc : 2 * (size_t)K * nd;
+  const size_t doubles = head + nd + (nd + 1) / 2 + (sobol ? nd * args.d : 0);
   if ((rc = grow_dev(ctx, ctx->work, (doubles ? doubles : 1) * sizeof(double), "chain workspace"))) return rc;
+  if (paths && N > 0) {
+    // the largest any pass asks for (a short last pass may split where the full ones do not): before the marks
+    const int64_t wsa = hvi_paths_ws_doubles(Nc, pl.S), wsb = hvi_paths_ws_doubles(N % Nc, pl.S);
+    const int64_t wsd = wsa > wsb ? wsa : wsb;
+    if (wsd && (rc = grow_dev(ctx, ctx->hws, sizeof(double) * (size_t)wsd, "HVI path workspace"))) return rc;
+  }
   double* mu = ctx->work.as<double>();
   double* var = mu + (size_t)K * nd;
-  double* vals = vals_out ? vals_out : var + (size_t)K * nd;
-  int32_t* raised = reinterpret_cast<int32_t*>(var + (size_t)K * nd + nd);
-  double* Xs = var + (size_t)K * nd + nd + (nd + 1) / 2;
+  double* vals = vals_out ? vals_out : mu + head;
+  int32_t* raised = reinterpret_cast<int32_t*>(mu + head + nd);
+  double* Xs = mu + head + nd + (nd + 1) / 2;
   // with constraints the caller may want the unweighted acquisition kept (omb_eval_grad): it goes to acq_raw and the
   // weighted value to vals; otherwise the weight is applied in place
   double* acq = (pl.n_con && acq_raw) ? acq_raw : vals;
@@ -531,9 +606,22 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
   if (e == hipSuccess) e = mark(1);
   const double* Ld[OMB_MAX_OBJ];
   gather_Ld(ctx, K, Ld);
-  if (e == hipSuccess && N > 0) e = posterior_any(ctx, args, Ld, K, max_R, Xc, N, mu, var);
-  if (e == hipSuccess) e = mark(2);
-  if (e == hipSuccess && N > 0) {
+  if (paths) {
+    // per pass: the paths of objectives 0..k-1 at Nc candidates, then their mean improvement into vals.  Mark 2 stands
+    // after the last pass's path evaluation: with several passes the "posterior" interval holds the earlier passes'
+    // acquisition launches too (the stages alternate on one stream).
+    for (int64_t c0 = 0; c0 < N && e == hipSuccess; c0 += Nc) {
+      const int64_t nc = (N - c0) < Nc ? (N - c0) : Nc;
+      e = launch_paths_eval(ctx->stream, pa, k, ctx->obj[0].kind, ctx->paths_libcos, Xc + c0 * args.d, nc, nc, mu);
+      if (e == hipSuccess && c0 + nc == N) e = mark(2);
+      if (e == hipSuccess && (rc = run_hvi_paths(ctx, pl, mu, nc, nc, vals + c0, "fused chain (hvi_paths)"))) return rc;
+    }
+    if (e == hipSuccess && N == 0) e = mark(2);
+  } else if (e == hipSuccess && N > 0) {
+    e = posterior_any(ctx, args, Ld, K, max_R, Xc, N, mu, var);
+  }
+  if (e == hipSuccess && !paths) e = mark(2);
+  if (e == hipSuccess && N > 0 && !paths) {
     if (acq_argmax) {
       unsigned* ticket = ctx->fused_chain == 1 ? reinterpret_cast<unsigned*>(ctx->partials + 2 * kArgmaxMaxBlocks)
                                                : nullptr;
@@ -654,6 +742,8 @@ static const DebugSwitch kDebugSwitches[] = {
     {OMB_DEBUG_SELECT_SEQ, &omb_ctx::select_seq, 0, 1, nullptr},
     {OMB_DEBUG_BOXES_KD, &omb_ctx::boxes_kd_wave, 0, 1, nullptr},
     {OMB_DEBUG_PATHS_LIBCOS, &omb_ctx::paths_libcos, 0, 1, nullptr},
+    {OMB_DEBUG_HVI_PATHS_CHUNK, &omb_ctx::hvi_paths_chunk, 0, 0x7fffffff,
+     "sampled-front chain chunk %lld outside [0, 2^31) (0: one pass)"},
     {OMB_DEBUG_POSTERIOR_ALL_VAR, &omb_ctx::posterior_all_var, 0, 1, nullptr},
 };
 
@@ -937,6 +1027,19 @@ int omb_hvi_boxes(omb_ctx* ctx, int k, const double* y_dev, int64_t ld, int64_t 
   return OMB_OK;
 }
 
+int omb_hvi_paths(omb_ctx* ctx, int k, int S, const double* y_dev, int64_t ld, int64_t N, const double* coords_dev,
+                  int C, const int32_t* box_off_host, const uint16_t* boxes_dev, double* out_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  Plan pl;
+  if ((rc = describe_hvi_paths(ctx, k, S, y_dev, ld, N, coords_dev, C, box_off_host, boxes_dev, out_dev, &pl)))
+    return rc;
+  if (N == 0) return OMB_OK;
+  pl.geo = coords_dev;
+  pl.boxes = boxes_dev;
+  return run_hvi_paths(ctx, pl, y_dev, ld, N, out_dev, "hvi_paths");
+}
+
 int omb_hvpoi(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
               const double* cells_dev, int C, double* out_dev) {
   int rc = enter(ctx);
@@ -1129,11 +1232,27 @@ int omb_plan_mes(omb_ctx* ctx, int k, int S, const double* ystar_host) {
   return install_plan(ctx, pl, ystar_host, sizeof(double) * (size_t)k * S);
 }
 
+int omb_plan_hvi_paths(omb_ctx* ctx, int k, int S, const double* coords_host, int C, const int32_t* box_off_host,
+                       const uint16_t* boxes_host) {
+  int rc = plan_enter(ctx);
+  if (rc) return rc;
+  Plan pl;
+  if ((rc = describe_hvi_paths(ctx, k, S, nullptr, 0, 0, coords_host, C, box_off_host, boxes_host, nullptr, &pl)))
+    return rc;
+  if ((rc = check_box_lists(E(ctx), k, S, C, box_off_host, boxes_host))) return rc;
+  // the grids' bytes are a multiple of 8: the box lists behind them stay 4-byte aligned
+  return install_plan(ctx, pl, coords_host, sizeof(double) * (size_t)S * k * C, boxes_host,
+                      sizeof(uint16_t) * 2 * (size_t)k * (size_t)box_off_host[S]);
+}
+
 int omb_plan_constraints(omb_ctx* ctx, int n_con, double pof_eps) {
   int rc = enter(ctx);
   if (rc) return rc;
   // a failed call leaves the plan and its previous constraints as they were
   if ((rc = check_constraints(E(ctx), ctx->plan.kind == PLAN_NONE ? 0 : ctx->plan.k, n_con, pof_eps))) return rc;
+  // the weight needs posterior moments of the constraint slots; the sampled-front chain computes none
+  if (ctx->plan.kind == PLAN_HVI_PATHS && n_con > 0)
+    return fail(ctx, OMB_EUNSUP, "the sampled-front improvement (noisy EHVI / EI) plan takes no constraints");
   ctx->plan.n_con = n_con;
   ctx->plan.con_eps = n_con ? pof_eps : 0.0;
   return OMB_OK;
@@ -1149,6 +1268,7 @@ static const char* log_refused(const Plan& pl) {
     case PLAN_HVPOI: return "HV-PoI";
     case PLAN_EXPDEC: return "expected decomposition";
     case PLAN_MES: return "max-value entropy search";
+    case PLAN_HVI_PATHS: return "sampled-front improvement (noisy EHVI / EI)";
     default: return "unknown";
   }
 }

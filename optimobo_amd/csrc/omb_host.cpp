@@ -189,6 +189,42 @@ int check_plan_mes(std::string* err, int k, int S, const double* ystar) {
   return OMB_OK;
 }
 
+int check_hvi_paths(std::string* err, int k, int S, const void* y, int64_t ld, int64_t N, const void* coords, int C,
+                    const int32_t* box_off, const void* boxes, const void* out) {
+  if (k < 1 || k > OMB_MAX_OBJ)
+    return errf(err, OMB_EINVAL, "the sampled-front improvement needs 1 <= k <= %d objectives (k=%d)", OMB_MAX_OBJ, k);
+  if (S < 1 || S > kPathsMaxS) return errf(err, OMB_EINVAL, "S=%d paths outside [1, %d]", S, kPathsMaxS);
+  if (N < 0) return errf(err, OMB_EINVAL, "N=%lld < 0", (long long)N);
+  if (!coords || !boxes || !box_off) return errf(err, OMB_EINVAL, "null grids, box lists or offsets");
+  if (box_off[0] != 0) return errf(err, OMB_EINVAL, "box_off[0]=%d, not 0", box_off[0]);
+  for (int s = 0; s < S; ++s)
+    if (box_off[s + 1] <= box_off[s])
+      return errf(err, OMB_EINVAL, "box_off[%d]=%d, box_off[%d]=%d: list %d is empty or the offsets decrease", s,
+                  box_off[s], s + 1, box_off[s + 1], s);
+  if (N > 0 && (!y || !out)) return errf(err, OMB_EINVAL, "null device pointer");
+  if (((uintptr_t)y | (uintptr_t)coords | (uintptr_t)out) & 7)
+    return errf(err, OMB_EINVAL, "path values, grids or output not 8-byte aligned");
+  if ((uintptr_t)boxes & 3) return errf(err, OMB_EINVAL, "box lists not 4-byte aligned");
+  if (ld < N) return errf(err, OMB_EINVAL, "ld=%lld < N=%lld", (long long)ld, (long long)N);
+  // one path's grid is staged in the 64 KiB of dynamic LDS; the box lists are streamed
+  if (C < 2 || (int64_t)k * C > kMaxLdsDoubles)
+    return errf(err, OMB_EUNSUP, "grid size C=%d outside [2, %d] for k=%d (k*C <= %d)", C, kMaxLdsDoubles / k, k,
+                kMaxLdsDoubles);
+  if (box_off[S] > kMaxBoxesK)
+    return errf(err, OMB_EUNSUP, "box count box_off[%d]=%d above %d", S, box_off[S], kMaxBoxesK);
+  return OMB_OK;
+}
+
+int check_box_lists(std::string* err, int k, int S, int C, const int32_t* box_off, const uint16_t* boxes) {
+  for (int s = 0; s < S; ++s) {
+    std::string one;
+    const int rc = check_box_list(err ? &one : nullptr, k, C, boxes + 2 * (size_t)k * (size_t)box_off[s],
+                                  (int64_t)box_off[s + 1] - box_off[s]);
+    if (rc) return errf(err, rc, "list %d, %s", s, one.c_str());
+  }
+  return OMB_OK;
+}
+
 void paths_pack(int m, int d, int DP, int S, const double* omega, const double* phase, const double* w, double scale,
                 double* Of, double* Wf) {
   const int ksf = paths_ksf(DP);

@@ -106,6 +106,17 @@ int check_mes(std::string* err, int k, int S, const void* mu, const void* var, i
 // omb_plan_mes, in this order: OMB_EINVAL for k outside [1, OMB_MAX_OBJ], S outside [1, kMesMaxS], a null ystar, or a
 // non-finite entry among its k·S (a plan built on it would be NaN everywhere).
 int check_plan_mes(std::string* err, int k, int S, const double* ystar);
+// omb_hvi_paths (and, with y = out = null and N = 0, omb_plan_hvi_paths over its host arrays), in this order:
+// OMB_EINVAL for k outside [1, OMB_MAX_OBJ], S outside [1, kPathsMaxS], N < 0, a null grid / box list / offsets,
+// offsets that do not start at 0 or decrease or leave a list empty, (N > 0) a null y / out, a pointer off its alignment
+// (8 bytes; the box list 4) or ld < N; OMB_EUNSUP for C < 2, k·C > kMaxLdsDoubles or box_off[S] > kMaxBoxesK.
+int check_hvi_paths(std::string* err, int k, int S, const void* y, int64_t ld, int64_t N, const void* coords, int C,
+                    const int32_t* box_off, const void* boxes, const void* out);
+// check_box_list over every list of a host (box_off[S], 2k) list whose offsets passed check_hvi_paths.
+int check_box_lists(std::string* err, int k, int S, int C, const int32_t* box_off, const uint16_t* boxes);
+// Candidates per pass of the fused chain under an omb_plan_hvi_paths plan (the default of OMB_DEBUG_HVI_PATHS_CHUNK):
+// the chain holds the (k·S, chunk) path values, not (k·S, N).
+constexpr int64_t kHviPathsChunk = OMB_HVI_PATHS_CHUNK;
 // The paths' operands in the A-fragment order of v_mfma_f64_16x16x4_f64 (lane l holds A[l & 15][l >> 4]), zero
 // padded to whole tiles of 16 features and to 16 paths:
 //   Of[(T·ksf + s)·64 + l] = [ω̃_i, b_i, 0 …][4s + (l >> 4)] of feature i = 16T + (l & 15)   (ksf = paths_ksf(DP))

@@ -125,4 +125,130 @@ hipError_t launch_hvi_boxes(hipStream_t stream, int k, const double* y, int64_t 
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------
+// The mean hypervolume improvement over S sampled fronts (omb_hvi_paths): candidate i holds one value per posterior
+// sample path and objective (row j·S + s of y, omb_paths_eval's layout), path s has a box list and a grid of its own,
+//   out[i] = ((…((0 + t_0) + t_1) + …) + t_{S−1}) / S,   t_s = hvi_boxes_kernel's value of list s on rows {j·S + s}.
+//   * One lane per candidate, as above.  LDS holds the current path's K·C grid doubles, re-staged per path between two
+//     barriers (a grid is a few hundred doubles; the S grids together would cost occupancy for nothing, and every
+//     workgroup reads each grid once).  The lists' offsets are a kernel argument: list s is rows off[s]..off[s+1] of
+//     the concatenated list, its index words wave-uniform as above.
+//   * t_s is hvi_slice's sum over slices of kHviSlice boxes counted from the list's own start, added in slice order
+//     from 0 — the additions of hvi_boxes_kernel, so t_s is bitwise omb_hvi_boxes' value.  K = 1 (noisy EI: list s is
+//     the box (−∞, b_s]) has a single factor per box, which hvi_slice's product would square: hvi_slice1 adds it.
+//   * A small batch (too few workgroups to fill the chip) gives every path a workgroup row of its own (blockIdx.y),
+//     which stores t_s to a workspace, and hvi_paths_finish_kernel adds them in path order and divides.  Both forms
+//     perform the same operations in the same order.  No atomics.
+//   * A NaN coordinate of any path makes the candidate's value NaN.
+struct HviPathOff {
+  int32_t off[kPathsMaxS + 1];
+};
+
+// hvi_slice for one objective: the box's single factor, added in list order
+__device__ __forceinline__ double hvi_slice1(double y, const double* grid, int C, const uint32_t* __restrict__ boxes,
+                                             int b0, int b1) {
+#pragma clang fp contract(off)
+  double p = 0.0;
+  for (int b = b0; b < b1; ++b) {
+    const uint32_t w = boxes[b];   // lo | hi << 16, wave-uniform
+    const int il = min((int)(w & 0xffffu), C - 1), ih = min((int)(w >> 16), C - 1);
+    p = p + fmax(grid[ih] - fmax(y, grid[il]), 0.0);
+  }
+  return p;
+}
+
+// SPLIT: blockIdx.y is the path, out is the workspace (S, N) of the t_s.  Otherwise out (N) takes the means.
+template <int K, bool SPLIT>
+__global__ __launch_bounds__(kHviThreads) void hvi_paths_kernel(const double* __restrict__ y, int64_t ld, int64_t N,
+                                                                int S, const double* __restrict__ coords, int C,
+                                                                const uint32_t* __restrict__ boxes, HviPathOff po,
+                                                                double* __restrict__ out) {
+#pragma clang fp contract(off)
+  extern __shared__ double hvi_paths_grid[];
+  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+  const int s0 = SPLIT ? (int)blockIdx.y : 0, s1 = SPLIT ? s0 + 1 : S;
+  // the tile loop is uniform over the workgroup: every lane reaches the barriers
+  for (int64_t base = (int64_t)blockIdx.x * kHviThreads; base < N; base += (int64_t)gridDim.x * kHviThreads) {
+    const int64_t i = base + threadIdx.x;
+    double total = 0.0;
+    for (int s = s0; s < s1; ++s) {
+      __syncthreads();   // the previous path's grid is read to the end
+      const double* g = coords + (size_t)s * K * C;
+      for (int t = threadIdx.x; t < K * C; t += kHviThreads) hvi_paths_grid[t] = g[t];
+      __syncthreads();
+      if (i < N) {
+        double yv[K];
+        bool nan = false;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+          yv[j] = y[((int64_t)j * S + s) * ld + i];
+          nan |= yv[j] != yv[j];
+        }
+        const int B = po.off[s + 1] - po.off[s];
+        const uint32_t* bl = boxes + (size_t)po.off[s] * K;
+        const int slices = (B + kHviSlice - 1) / kHviSlice;
+        double ts = 0.0;
+        for (int c = 0; c < slices; ++c) {
+          double p;
+          if constexpr (K == 1) p = hvi_slice1(yv[0], hvi_paths_grid, C, bl, c * kHviSlice, min(B, (c + 1) * kHviSlice));
+          else p = hvi_slice<K>(yv, hvi_paths_grid, C, bl, c * kHviSlice, min(B, (c + 1) * kHviSlice));
+          ts += nan ? qnan : p;
+        }
+        if constexpr (SPLIT) out[(int64_t)s * N + i] = ts;
+        else total += ts;
+      }
+    }
+    if constexpr (!SPLIT)
+      if (i < N) out[i] = total / (double)S;
+  }
+}
+
+// out[i] = (Σ_s part[s][i] in path order, from 0) / S: the operations of the unsplit kernel
+__global__ __launch_bounds__(kHviThreads) void hvi_paths_finish_kernel(const double* __restrict__ part, int S,
+                                                                       int64_t N, double* __restrict__ out) {
+#pragma clang fp contract(off)
+  for (int64_t i = (int64_t)blockIdx.x * kHviThreads + threadIdx.x; i < N; i += (int64_t)gridDim.x * kHviThreads) {
+    double total = 0.0;
+    for (int s = 0; s < S; ++s) total += part[(int64_t)s * N + i];
+    out[i] = total / (double)S;
+  }
+}
+
+int64_t hvi_paths_ws_doubles(int64_t N, int S) {
+  const int64_t nb = (N + kHviThreads - 1) / kHviThreads;
+  if (S < 2 || N < 1 || nb >= kHviSplitBlocks) return 0;
+  return (int64_t)S * N;
+}
+
+hipError_t launch_hvi_paths(hipStream_t stream, int k, int S, const double* y, int64_t ld, int64_t N,
+                            const double* coords, int C, const uint16_t* boxes, const int32_t* box_off, double* out,
+                            double* ws) {
+  if (N < 1 || S < 1 || S > kPathsMaxS || C < 2 || (int64_t)k * C > kMaxLdsDoubles ||
+      (reinterpret_cast<uintptr_t>(boxes) & 3))
+    return hipErrorInvalidValue;
+  HviPathOff po;
+  for (int s = 0; s <= kPathsMaxS; ++s) po.off[s] = box_off[s < S ? s : S];
+  const bool split = ws != nullptr && hvi_paths_ws_doubles(N, S) > 0;
+  const size_t shm = sizeof(double) * (size_t)k * C;
+  const int64_t nb = (N + kHviThreads - 1) / kHviThreads;
+  const dim3 g((unsigned)(nb > (1 << 20) ? (1 << 20) : nb), split ? (unsigned)S : 1u), b(kHviThreads);
+  const uint32_t* bw = reinterpret_cast<const uint32_t*>(boxes);
+  switch (k) {
+#define OMB_HVIP(KV)                                                                                          \
+  case KV:                                                                                                    \
+    if (split)                                                                                                \
+      hipLaunchKernelGGL((hvi_paths_kernel<KV, true>), g, b, shm, stream, y, ld, N, S, coords, C, bw, po, ws); \
+    else                                                                                                      \
+      hipLaunchKernelGGL((hvi_paths_kernel<KV, false>), g, b, shm, stream, y, ld, N, S, coords, C, bw, po, out); \
+    break;
+    OMB_HVIP(1) OMB_HVIP(2) OMB_HVIP(3) OMB_HVIP(4) OMB_HVIP(5) OMB_HVIP(6) OMB_HVIP(7) OMB_HVIP(8)
+#undef OMB_HVIP
+    default: return hipErrorInvalidValue;
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !split) return e;
+  hipLaunchKernelGGL(hvi_paths_finish_kernel, dim3(g.x), b, 0, stream, ws, S, N, out);
+  return hipGetLastError();
+}
+
 }  // namespace omb

@@ -111,6 +111,16 @@ int64_t hvi_ws_doubles(int64_t N, int B);
 hipError_t launch_hvi_boxes(hipStream_t stream, int k, const double* y, int64_t ld, int64_t N, const double* coords,
                             int C, const uint16_t* boxes, int B, double* out, double* ws);
 
+// The mean of that improvement over S sampled fronts (omb_hvi.hip, omb_hvi_paths / omb_plan_hvi_paths): y holds
+// omb_paths_eval's rows (path s of objective j at row j·S + s, pitch ld), list s is rows box_off[s]..box_off[s+1] of
+// boxes (S + 1 host offsets from 0) over the grid coords + s·k·C; 1 ≤ k ≤ OMB_MAX_OBJ, 1 ≤ S ≤ kPathsMaxS, N > 0.
+// ws: hvi_paths_ws_doubles(N, S) device doubles — the per-path values where a small batch gives every path a
+// workgroup row, 0 otherwise; null runs unsplit.  Bitwise the same values either way.
+int64_t hvi_paths_ws_doubles(int64_t N, int S);
+hipError_t launch_hvi_paths(hipStream_t stream, int k, int S, const double* y, int64_t ld, int64_t N,
+                            const double* coords, int C, const uint16_t* boxes, const int32_t* box_off, double* out,
+                            double* ws);
+
 hipError_t launch_hvpoi(hipStream_t stream, const double* mu, const double* var, int64_t ld, int64_t N,
                         const double* cells, int C, double* out);
 

@@ -258,6 +258,40 @@ def box_decomposition(pf, ref, max_boxes=1 << 20):
             np.ascontiguousarray(idx.astype(np.uint16)))
 
 
+def threshold_lists(b):
+    """One objective's "decompositions": for every sampled best value b_s the grid [−∞, b_s] and the single box
+    (0, 1), whose improvement is (b_s − y)⁺ — the input of ``pack_box_lists`` for the noisy EI."""
+    b = np.asarray(b, np.float64).reshape(-1)
+    return [(np.array([[-np.inf, v]]), np.array([2], np.int32), np.array([[0, 1]], np.uint16)) for v in b]
+
+
+def pack_box_lists(decomps):
+    """S ``box_decomposition`` results (or ``threshold_lists``) of the same k as one input of omb_hvi_paths:
+    (coords (S, k, C) f64, box_off (S + 1,) int32, boxes (ΣB, 2k) uint16).  C is the largest grid; a shorter grid is
+    padded with its last coordinate, as ``box_decomposition`` pads within one grid.  List s is rows
+    box_off[s]..box_off[s + 1] of boxes; an empty front still has one box (the whole of (−∞, ref])."""
+    decomps = list(decomps)
+    if not decomps:
+        raise ValueError("pack_box_lists: no decompositions")
+    k = decomps[0][0].shape[0]
+    if any(d[0].ndim != 2 or d[0].shape[0] != k or d[2].ndim != 2 or d[2].shape[1] != 2 * k for d in decomps):
+        raise ValueError("pack_box_lists: the decompositions disagree on the number of objectives")
+    if any(len(d[2]) < 1 for d in decomps):
+        raise ValueError("pack_box_lists: an empty box list")
+    C = max(d[0].shape[1] for d in decomps)
+    coords = np.empty((len(decomps), k, C), np.float64)
+    for s, d in enumerate(decomps):
+        c = d[0].shape[1]
+        coords[s, :, :c] = d[0]
+        coords[s, :, c:] = d[0][:, -1:]
+    box_off = np.zeros(len(decomps) + 1, np.int64)
+    np.cumsum([len(d[2]) for d in decomps], out=box_off[1:])
+    if box_off[-1] > np.iinfo(np.int32).max:
+        raise ValueError("pack_box_lists: more than 2^31 boxes")
+    boxes = np.ascontiguousarray(np.concatenate([np.asarray(d[2], np.uint16) for d in decomps]))
+    return coords, box_off.astype(np.int32), boxes
+
+
 def cached_samples(k, sample_exponent, seed=None):
     s = qmc.Sobol(d=k, scramble=True, seed=seed).random_base2(m=sample_exponent)
     return np.ascontiguousarray(np.column_stack([norm.ppf(s[:, i]) for i in range(k)]))
