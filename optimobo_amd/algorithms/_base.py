@@ -141,21 +141,24 @@ class BODriver:
         if not isinstance(acquisition, str) or acquisition not in ("mes", "nehvi", "nei"):
             raise ValueError(f"acquisition must be None or 'mes', 'nehvi' or 'nei', not {acquisition!r}")
         if acquisition not in self._acquisitions:
-            if acquisition == "mes":
-                raise ValueError(f"{type(self).__name__} does not support acquisition='mes' (MultiSurrogateOptimiser "
-                                 "and MonoSurrogateOptimiser do)")
-            raise ValueError(f"{type(self).__name__} does not support acquisition={acquisition!r} ('nehvi' is "
-                             "MultiSurrogateOptimiser's, 'nei' MonoSurrogateOptimiser's)")
-        if acquisition != "mes":
-            return self._check_noisy_acquisition(acquisition)
+            raise ValueError(f"{type(self).__name__} does not support acquisition={acquisition!r} ('mes' is "
+                             "MultiSurrogateOptimiser's and MonoSurrogateOptimiser's, 'nehvi' the former's alone, "
+                             "'nei' the latter's)")
+        if acquisition != "mes" and self.constraints == "pof":
+            raise ValueError(f"acquisition={acquisition!r} does not support constraints='pof' (the sampled-front plan "
+                             "computes no posterior for the constraint models to weight it with)")
+        # what the three share: every pick plans from fresh posterior sample paths
         if self.batch_strategy == "thompson":
-            raise ValueError("acquisition='mes' does not support batch_strategy='thompson' (a Thompson batch maximises "
-                             "no acquisition; 'believer' batches take it)")
+            raise ValueError(f"acquisition={acquisition!r} does not support batch_strategy='thompson' (a Thompson "
+                             "batch maximises no acquisition; 'believer' batches take it)")
         if self.log_acquisition:
-            raise ValueError("acquisition='mes' does not support log_acquisition=True (max-value entropy search has no "
-                             "log form)")
+            raise ValueError(f"acquisition={acquisition!r} does not support log_acquisition=True (neither max-value "
+                             "entropy search nor the mean over sampled fronts has a log form)")
         if self.n_vars > 64:
-            raise ValueError(f"acquisition='mes' samples posterior paths, which need n_var <= 64 (n_var={self.n_vars})")
+            raise ValueError(f"acquisition={acquisition!r} samples posterior paths, which need n_var <= 64 "
+                             f"(n_var={self.n_vars})")
+        if acquisition != "mes":
+            return acquisition
         if isinstance(mes_samples, bool) or not isinstance(mes_samples, (int, np.integer)) or not 1 <= mes_samples <= 16:
             raise ValueError(f"mes_samples must be an integer in [1, 16], not {mes_samples!r}")
         if isinstance(mes_candidates, bool) or not isinstance(mes_candidates, (int, np.integer)) or mes_candidates < 1:
@@ -163,42 +166,37 @@ class BODriver:
         self.mes_samples, self.mes_candidates = int(mes_samples), int(mes_candidates)
         return "mes"
 
-    def _check_noisy_acquisition(self, acquisition):
-        if self.constraints == "pof":
-            raise ValueError(f"acquisition={acquisition!r} does not support constraints='pof' (the sampled-front plan "
-                             "computes no posterior for the constraint models to weight it with)")
-        if self.batch_strategy == "thompson":
-            raise ValueError(f"acquisition={acquisition!r} does not support batch_strategy='thompson' (a Thompson "
-                             "batch maximises no acquisition; 'believer' batches take it)")
-        if self.log_acquisition:
-            raise ValueError(f"acquisition={acquisition!r} does not support log_acquisition=True (the mean over "
-                             "sampled fronts has no log form)")
-        if self.n_vars > 64:
-            raise ValueError(f"acquisition={acquisition!r} samples posterior paths, which need n_var <= 64 "
-                             f"(n_var={self.n_vars})")
-        return acquisition
+    def _base_seed(self):
+        return self.seed if self.seed is not None else np.random.randint(0, 2 ** 31 - 1)
+
+    def _search_seed(self):
+        """The seed of the next search or Thompson batch: one per call, so every rank computes the same one."""
+        seed = self._base_seed() + 7919 * self._iteration
+        self._iteration += 1
+        return seed
+
+    def _path_seed(self):
+        """The seed of the next pick's sample paths (``_plan_mes`` and ``_plan_nehvi`` share the counter)."""
+        base = self._base_seed()
+        self._mes_picks += 1
+        return base + 15485863 + 7919 * self._mes_picks
 
     def _plan_nehvi(self, eng, k):
         """The noisy-EHVI (k = 1: noisy-EI) plan of one pick on ``eng`` over its ``k`` models: ``nehvi_samples`` fresh
-        sample paths (a seed of their own per pick, derived as ``_plan_mes`` derives it, on the same counter), their
-        fronts at the training inputs, the plan.  ``eng.condition`` drops the paths, so a believer batch samples again
-        for every pick, from the conditioned state.  ``pareto.BoxBudgetError`` (n_obj ≥ 4, a front past
-        ``exact_max_boxes``) propagates."""
-        base = self.seed if self.seed is not None else np.random.randint(0, 2 ** 31 - 1)
-        self._mes_picks += 1
+        sample paths, their fronts at the training inputs, the plan.  ``eng.condition`` drops the paths, so a believer
+        batch samples again for every pick, from the conditioned state.  ``pareto.BoxBudgetError`` (n_obj ≥ 4, a
+        front past ``exact_max_boxes``) propagates."""
         eng.sample_fronts(self.nehvi_samples, self.max_point if k > 1 else None, self.test_problem.xl,
-                          self.test_problem.xu, seed=base + 15485863 + 7919 * self._mes_picks,
-                          n_features=self.nehvi_features, max_boxes=getattr(self, "exact_max_boxes", 1 << 20))
+                          self.test_problem.xu, seed=self._path_seed(), n_features=self.nehvi_features,
+                          max_boxes=getattr(self, "exact_max_boxes", 1 << 20))
         eng.plan_nehvi()
 
     def _plan_mes(self, eng, k):
-        """The MES plan of one pick on ``eng`` over its first ``k`` models: fresh sample paths (a seed of their own
-        per pick, derived as ``_maximise`` derives a search's), their minima, the plan.  ``eng.condition`` drops the
-        paths, so a believer batch samples again for every pick, from the conditioned state."""
-        base = self.seed if self.seed is not None else np.random.randint(0, 2 ** 31 - 1)
-        self._mes_picks += 1
+        """The MES plan of one pick on ``eng`` over its first ``k`` models: fresh sample paths, their minima, the
+        plan.  ``eng.condition`` drops the paths, so a believer batch samples again for every pick, from the
+        conditioned state."""
         ystar = eng.sample_minima(self.mes_samples, self.test_problem.xl, self.test_problem.xu,
-                                  n_candidates=self.mes_candidates, seed=base + 15485863 + 7919 * self._mes_picks,
+                                  n_candidates=self.mes_candidates, seed=self._path_seed(),
                                   n_features=self.mes_features)
         eng.plan_mes(ystar[:k])
 
@@ -225,9 +223,13 @@ class BODriver:
 
     # -- constraints="pof"
     def _constraint_values(self, X):
-        """G (len(X), n_ieq_constr) of the rows of X through ``problem.evaluate_constraints``."""
-        return np.asarray([np.atleast_1d(self.test_problem.evaluate_constraints(x, return_values_of=["G"])) for x in np.atleast_2d(X)],
-                          dtype=np.float64).reshape(len(np.atleast_2d(X)), -1)
+        """G (len(X), n_ieq_constr) of the rows of X through ``problem.evaluate_constraints``.  Without
+        constraints="pof" nothing is evaluated and G has no columns, so that ``_feasible`` passes every row."""
+        X = np.atleast_2d(X)
+        if self.constraints != "pof":
+            return np.empty((len(X), 0))
+        return np.asarray([np.atleast_1d(self.test_problem.evaluate_constraints(x, return_values_of=["G"])) for x in X],
+                          dtype=np.float64).reshape(len(X), -1)
 
     @staticmethod
     def _feasible(G):
@@ -289,10 +291,24 @@ class BODriver:
         again would undo); None loads ``models``."""
         if eng is None:
             eng = engine_for(models, self.device)
-        seed = (self.seed if self.seed is not None else np.random.randint(0, 2 ** 31 - 1)) + 7919 * self._iteration
-        self._iteration += 1
         return eng.maximise(acq_fn, self.test_problem.xl, self.test_problem.xu, n_candidates=self.n_candidates,
-                            seed=seed, refine_rounds=self.refine_rounds, polish=self.polish, starts=self.starts)
+                            seed=self._search_seed(), refine_rounds=self.refine_rounds, polish=self.polish,
+                            starts=self.starts)
+
+    def _maximise_plan(self, models, eng):
+        """The search of a ``_get_proposed*`` hook once its plan is set.  Under constraints="pof" the plan is first
+        weighted by the probability of feasibility of the ``n_con`` models behind it (AcquisitionEngine
+        .plan_constraints, after the plan and its ``plan_log``: a log plan keeps its flag, log F is added).
+        ``eng`` None — an iteration's first pick — is the reference loop's two-argument ``_maximise`` call."""
+        if self.constraints == "pof":
+            (engine_for(models, self.device) if eng is None else eng).plan_constraints(self.n_con, self.pof_eps)
+        return self._maximise(models, None) if eng is None else self._maximise(models, None, eng=eng)
+
+    def _maximise_feasibility(self, models, eng):
+        """constraints="pof" while no row is feasible: the point most likely to be feasible (by log F with
+        ``log_acquisition``)."""
+        pof = eng.log_feasibility if self.log_acquisition else eng.feasibility
+        return self._maximise(models, lambda Xd: pof(Xd, self.n_con, self.pof_eps), eng=eng)[0]
 
     def _thompson_picks(self, eng, b, PF=None):
         """``b`` proposals of one iteration by AcquisitionEngine.thompson_batch on ``eng`` as it stands (seeded as
@@ -301,8 +317,7 @@ class BODriver:
         (OMB_ENOTPD — near-singular fits can exhaust it) or the front needs more boxes than the budget
         (pareto.BoxBudgetError).  A fallback warns and is counted in ``thompson_fallbacks``; any other error of the
         call — a batch larger than the candidate set, say — is the caller's and is raised."""
-        seed = (self.seed if self.seed is not None else np.random.randint(0, 2 ** 31 - 1)) + 7919 * self._iteration
-        self._iteration += 1
+        seed = self._search_seed()
         kw = {}
         if self.thompson_sampler == "paths":
             kw = dict(sampler="paths", n_features=self.thompson_features, refine_rounds=self.thompson_refine_rounds)

@@ -19,6 +19,7 @@ import numpy as np
 from .. import pareto
 from ..refdirs import get_reference_directions
 from .._lib import OMB_EUNSUP, OMBError
+from ..acquisition import engine_for
 from ._base import BODriver
 
 
@@ -39,12 +40,10 @@ class MultiSurrogateOptimiser(BODriver):
         """optimisers.py:121-141 — scrambled Sobol mapped through the normal ppf."""
         return pareto.cached_samples(dimensions, sample_exponent, seed=self.seed)
 
-    def _get_proposed_EHVI(self, function, models, ideal_point, max_point, pf, cache):
-        """optimisers.py:91-119 on the device: returns (x, −EHVI(x))."""
-        from ..acquisition import engine_for
-        eng = engine_for(models, self.device)
-        self._plan_EHVI(eng, function, max_point, pf, cache)
-        x, v = self._maximise(models, None)
+    def _get_proposed_EHVI(self, function, models, ideal_point, max_point, pf, cache, eng=None):
+        """optimisers.py:91-119 on the device: returns (x, −EHVI(x)).  ``eng``: as in ``_maximise``."""
+        self._plan_EHVI(engine_for(models, self.device) if eng is None else eng, function, max_point, pf, cache)
+        x, v = self._maximise_plan(models, eng)
         return x, -v
 
     def _plan_EHVI(self, eng, function, max_point, pf, cache):
@@ -90,118 +89,51 @@ class MultiSurrogateOptimiser(BODriver):
         eng.plan_ehvi3d(max_point, pf, cache)
         return False
 
-    def _get_proposed_scalarisation(self, function, models, min_val, scalar_func, ref_dir, cache):
-        """optimisers.py:62-88 on the device: returns (x, −value, ref_dir)."""
-        from ..acquisition import engine_for
-        eng = engine_for(models, self.device)
-        eng.plan_expected_decomposition(ref_dir, scalar_func, min_val, cache)
-        x, v = self._maximise(models, None)
+    def _get_proposed_scalarisation(self, function, models, min_val, scalar_func, ref_dir, cache, eng=None):
+        """optimisers.py:62-88 on the device: returns (x, −value, ref_dir).  ``eng``: as in ``_maximise``."""
+        planned = engine_for(models, self.device) if eng is None else eng
+        planned.plan_expected_decomposition(ref_dir, scalar_func, min_val, cache)
+        x, v = self._maximise_plan(models, eng)
         return x, -v, ref_dir
 
     def solve(self, budget=100, n_init_samples=5, sample_exponent=5, acquisition_func=None):
-        """``budget`` true evaluations.  With ``batch_size`` q > 1 they come in ⌈budget/q⌉ iterations of q proposals
-        (the last one truncated), one ``hypervolume_convergence`` entry per iteration: see ``_solve_batched``.
-        With ``constraints="pof"``: ``_solve_pof``, which returns a ``Constrained_Res``.
-        With ``log_acquisition=True`` (textbook mode, ``acquisition_func`` None) every pick maximises the logarithm
-        of the exact EHVI (plus log F under ``constraints="pof"``; log F alone while no row is feasible)."""
+        """``budget`` true evaluations in ⌈budget/q⌉ iterations of q = ``batch_size`` proposals (the last one
+        truncated; 1 is the reference's loop, call for call), one ``hypervolume_convergence`` entry per iteration.
+
+        One iteration: one fit, then the batch.  The Kriging believer builds it greedily: every pick draws a fresh
+        reference direction, plans the acquisition from the samples plus the fantasies so far (their front, or the
+        scalarisation's minimum) and maximises it through ``_get_proposed_EHVI`` / ``_get_proposed_scalarisation``;
+        before the next pick the resident GPs are conditioned on the point with their own posterior mean as its
+        value (AcquisitionEngine.condition: μ stays, σ² collapses around the pick, so the next arg-max moves on),
+        and that pick searches the engine as it stands (``eng=``).  The picks are then evaluated for real; the next
+        fit uploads the fitted states again, so no fantasy outlives its batch.
+
+        ``batch_strategy="thompson"`` (EHVI acquisitions): one AcquisitionEngine.thompson_batch over the true
+        samples' front proposes all the iteration's points at once (``_thompson_picks``) and draws no reference
+        direction; an iteration it cannot serve is built by the believer instead.
+
+        ``constraints="pof"`` returns a ``Constrained_Res``: one more GP per inequality constraint on the same
+        inputs, every pick's acquisition weighted by their probability of feasibility (``_maximise_plan``), and the
+        believer conditions them as well.  A row is feasible when every g ≤ 0; the front, the scalarisation's minimum
+        and the hypervolume trace (0.0 while nothing is feasible) use feasible rows only — fantasies count as
+        feasible by the constraint models' means.  While no row is feasible the pick maximises the probability of
+        feasibility alone (``_maximise_feasibility``).  Without the keyword G has no columns: every row is feasible.
+
+        ``log_acquisition=True`` (textbook mode, ``acquisition_func`` None): every pick maximises the logarithm of
+        the exact EHVI (plus log F under ``constraints="pof"``; log F alone while no row is feasible)."""
         if self.acquisition is not None and acquisition_func is not None:
             raise ValueError(f"acquisition={self.acquisition!r} takes the place of the EHVI (acquisition_func=None), "
                              "not of a scalarised expected decomposition")
         if self.log_acquisition and acquisition_func is not None:
             raise ValueError("log_acquisition=True takes the exact EHVI (acquisition_func=None): the expected "
                              "decomposition has no log form")
-        if self.constraints == "pof":
-            return self._solve_pof(budget, n_init_samples, sample_exponent, acquisition_func)
         if self.batch_strategy == "thompson" and acquisition_func is not None:
             raise ValueError("batch_strategy='thompson' scores draws by hypervolume improvement: it supports the EHVI "
                              "acquisitions (acquisition_func=None), not a scalarised expected decomposition")
-        if self.batch_size > 1 or self.batch_strategy == "thompson":
-            return self._solve_batched(budget, n_init_samples, sample_exponent, acquisition_func)
         problem = self.test_problem
-        Xsample, ysample = self._initial_samples(n_init_samples)
+        pof, k = self.constraints == "pof", problem.n_obj
         cached_samples = self._get_cached_samples(self.n_obj, sample_exponent)
-        ref_dirs = get_reference_directions("das-dennis", self.n_obj, n_partitions=100)
-        hypervolume_convergence = []
-        for _ in range(budget):
-            self._update_bounds(ysample, acquisition_func)
-            hypervolume_convergence.append(self._hypervolume(ysample))
-            models = self._fit_many(Xsample, ysample[:, :problem.n_obj])
-            ref_dir = np.asarray(ref_dirs[np.random.randint(0, len(ref_dirs))])
-            if acquisition_func is None:
-                pf = pareto.calc_pf(ysample)
-                fn = "EHVI" if problem.n_obj == 2 else "EHVI_3D"
-                X_next, _ = self._get_proposed_EHVI(fn, models, self.ideal_point, self.max_point, pf, cached_samples)
-            else:
-                min_scalar = np.min([acquisition_func(y, ref_dir) for y in ysample])
-                X_next, _, _ = self._get_proposed_scalarisation("expected_decomposition", models, min_scalar,
-                                                                acquisition_func, ref_dir, cached_samples)
-            y_next = self._objective_function(problem, X_next)
-            ysample = np.vstack((ysample, y_next))
-            Xsample = np.vstack((Xsample, X_next))
-        return self._result(ysample, Xsample, hypervolume_convergence, n_init_samples)
-
-    def _solve_batched(self, budget, n_init_samples, sample_exponent, acquisition_func):
-        """Sequential-greedy batches with the Kriging believer: one fit per iteration; every pick plans the
-        acquisition from the samples plus the fantasies so far (front, or the scalarisation's minimum under a fresh
-        reference direction) and maximises it; before the next pick the resident GPs are conditioned on the point
-        with their own posterior mean as its value (AcquisitionEngine.condition: μ stays, σ² collapses around the
-        pick, so the next arg-max moves on).  The picks are then evaluated for real; the next iteration's fit
-        uploads the fitted states again, so no fantasy outlives its batch.
-
-        ``batch_strategy="thompson"`` (EHVI acquisitions): after the fit, one AcquisitionEngine.thompson_batch over
-        the true samples' front proposes all b points at once (``_thompson_picks``); an iteration it cannot serve
-        is built by the believer loop above instead.  It draws no reference direction."""
-        from ..acquisition import engine_for
-        problem = self.test_problem
-        q = self.batch_size
-        Xsample, ysample = self._initial_samples(n_init_samples)
-        cached_samples = self._get_cached_samples(self.n_obj, sample_exponent)
-        ref_dirs = get_reference_directions("das-dennis", self.n_obj, n_partitions=100)
-        hypervolume_convergence = []
-        done = 0
-        while done < budget:
-            b = min(q, budget - done)
-            self._update_bounds(ysample, acquisition_func)
-            hypervolume_convergence.append(self._hypervolume(ysample))
-            models = self._fit_many(Xsample, ysample[:, :problem.n_obj])
-            eng = engine_for(models, self.device)
-            yfant, picks = ysample[:, :problem.n_obj], None
-            if self.batch_strategy == "thompson":
-                picks = self._thompson_picks(eng, b, pareto.calc_pf(yfant))
-            if picks is None:              # the believer batch (also a Thompson iteration's fallback)
-                picks = []
-                for p in range(b):
-                    ref_dir = np.asarray(ref_dirs[np.random.randint(0, len(ref_dirs))])
-                    if acquisition_func is None:
-                        fn = "EHVI" if problem.n_obj == 2 else "EHVI_3D"
-                        self._plan_EHVI(eng, fn, self.max_point, pareto.calc_pf(yfant), cached_samples)
-                    else:
-                        min_scalar = np.min([acquisition_func(y, ref_dir) for y in yfant])
-                        eng.plan_expected_decomposition(ref_dir, acquisition_func, min_scalar, cached_samples)
-                    x, _ = self._maximise(models, None, eng=eng)
-                    picks.append(x)
-                    if p + 1 < b:
-                        yfant = np.vstack((yfant, eng.condition(x[None, :])))
-            for x in picks:
-                ysample = np.vstack((ysample, self._objective_function(problem, x)))
-                Xsample = np.vstack((Xsample, x))
-            done += b
-        return self._result(ysample, Xsample, hypervolume_convergence, n_init_samples)
-
-
-    def _solve_pof(self, budget, n_init_samples, sample_exponent, acquisition_func):
-        """``constraints="pof"``: the loop of ``_solve_batched`` (``batch_size`` 1 is a batch of one) with one GP per
-        objective and per inequality constraint on the same inputs, and the acquisition of every pick weighted by
-        the constraint models' probability of feasibility (AcquisitionEngine.plan_constraints).  A row is feasible
-        when every g ≤ 0; the front the acquisition is planned from, the scalarisation's minimum and the
-        hypervolume trace (0.0 while nothing is feasible) use feasible rows only — inside a batch, fantasies count
-        as feasible by the constraint models' means.  While no row is feasible the pick maximises the probability of
-        feasibility alone.  The believer conditions the constraint models as well."""
-        from ..acquisition import engine_for
-        problem = self.test_problem
-        q, k, c = self.batch_size, problem.n_obj, self.n_con
-        cached_samples = self._get_cached_samples(self.n_obj, sample_exponent)
-        if acquisition_func is None and k == 2 and self.mode == "reference" and \
+        if pof and acquisition_func is None and k == 2 and self.mode == "reference" and \
                 pareto.cache_stats(np.asarray(cached_samples, np.float64))[1] <= 0:
             # DESIGN §2 item 2: with s01 <= 0 the reference-mode acquisition is <= 0 everywhere, and a weight in
             # [0, 1] on a non-positive value favours the infeasible points
@@ -213,37 +145,41 @@ class MultiSurrogateOptimiser(BODriver):
         hypervolume_convergence = []
         done = 0
         while done < budget:
-            b = min(q, budget - done)
+            b = min(self.batch_size, budget - done)
             self._update_bounds(ysample, acquisition_func)
             hypervolume_convergence.append(self._hypervolume(ysample[self._feasible(gsample)]))
             models = self._fit_many(Xsample, np.hstack((ysample[:, :k], gsample)))
             eng = engine_for(models, self.device)
-            yfant, gfant, picks = ysample[:, :k], gsample, []
-            for p in range(b):
-                ref_dir = np.asarray(ref_dirs[np.random.randint(0, len(ref_dirs))])
-                yfeas = yfant[self._feasible(gfant)]
-                if len(yfeas) == 0:
-                    pof = eng.log_feasibility if self.log_acquisition else eng.feasibility
-                    x, _ = self._maximise(models, lambda Xd: pof(Xd, c, self.pof_eps), eng=eng)
-                else:
-                    if acquisition_func is None:
-                        fn = "EHVI" if k == 2 else "EHVI_3D"
-                        self._plan_EHVI(eng, fn, self.max_point, pareto.calc_pf(yfeas), cached_samples)
+            yfant, gfant, picks = ysample[:, :k], gsample, None
+            if self.batch_strategy == "thompson":
+                picks = self._thompson_picks(eng, b, pareto.calc_pf(yfant))
+            if picks is None:              # the believer batch (also a Thompson iteration's fallback)
+                picks = []
+                for p in range(b):
+                    ref_dir = np.asarray(ref_dirs[np.random.randint(0, len(ref_dirs))])
+                    yfeas = yfant[self._feasible(gfant)]
+                    on = dict(eng=eng) if p else {}        # conditioned since the fit: search it as it stands
+                    if len(yfeas) == 0:
+                        x = self._maximise_feasibility(models, eng)
+                    elif acquisition_func is None:
+                        x, _ = self._get_proposed_EHVI("EHVI" if k == 2 else "EHVI_3D", models, self.ideal_point,
+                                                       self.max_point, pareto.calc_pf(yfeas), cached_samples, **on)
                     else:
                         min_scalar = np.min([acquisition_func(y, ref_dir) for y in yfeas])
-                        eng.plan_expected_decomposition(ref_dir, acquisition_func, min_scalar, cached_samples)
-                    eng.plan_constraints(c, self.pof_eps)     # a log plan (_plan_EHVI) keeps its flag: log F is added
-                    x, _ = self._maximise(models, None, eng=eng)
-                picks.append(x)
-                if p + 1 < b:
-                    m = eng.condition(x[None, :])
-                    yfant, gfant = np.vstack((yfant, m[:, :k])), np.vstack((gfant, m[:, k:]))
+                        x, _, _ = self._get_proposed_scalarisation("expected_decomposition", models, min_scalar,
+                                                                   acquisition_func, ref_dir, cached_samples, **on)
+                    picks.append(x)
+                    if p + 1 < b:
+                        m = eng.condition(x[None, :])
+                        yfant, gfant = np.vstack((yfant, m[:, :k])), np.vstack((gfant, m[:, k:]))
             for x in picks:
                 ysample = np.vstack((ysample, self._objective_function(problem, x)))
                 Xsample = np.vstack((Xsample, x))
-            gsample = np.vstack((gsample, self._constraint_values(np.asarray(picks))))
+            gsample = np.vstack((gsample, self._constraint_values(picks)))
             done += b
-        return self._constrained_result(ysample, Xsample, gsample, hypervolume_convergence, n_init_samples)
+        if pof:
+            return self._constrained_result(ysample, Xsample, gsample, hypervolume_convergence, n_init_samples)
+        return self._result(ysample, Xsample, hypervolume_convergence, n_init_samples)
 
 
 class MonoSurrogateOptimiser(BODriver):
@@ -269,97 +205,30 @@ class MonoSurrogateOptimiser(BODriver):
 
     def _expected_improvement(self, X, model, opt_value, kappa=0.01):
         """optimisers.py:325-344 (σ = sqrt(σ²)); X (d,) → (1,), X (N, d) → (N,)."""
-        from ..acquisition import engine_for
         Xb = np.atleast_2d(np.asarray(X, np.float64))
         out = engine_for([model], self.device).ei(Xb, opt_value, 0.0).cpu().numpy()
         return out[:1] if np.ndim(X) == 1 else out
 
-    def _get_proposed(self, function, models, current_best):
-        from ..acquisition import engine_for
-        eng = engine_for([models], self.device)
-        self._plan_ei(eng, current_best)
-        x, v = self._maximise([models], None)
+    def _get_proposed(self, function, models, current_best, eng=None):
+        """``models``: the surrogate, or under constraints="pof" the list with the constraint models behind it.
+        ``eng``: as in ``_maximise``."""
+        models = models if isinstance(models, list) else [models]
+        self._plan_ei(engine_for(models, self.device) if eng is None else eng, current_best)
+        x, v = self._maximise_plan(models, eng)
         return x, -v
 
     def _normalize_data(self, data):
         return (data - np.min(data)) / (np.max(data) - np.min(data))
 
     def solve(self, aggregation_func, budget=100, n_init_samples=5):
-        """``budget`` true evaluations; with ``batch_size`` q > 1 in ⌈budget/q⌉ iterations (``_solve_batched``).
-        With ``constraints="pof"``: ``_solve_pof``, which returns a ``Constrained_Res``."""
-        if self.constraints == "pof":
-            return self._solve_pof(aggregation_func, budget, n_init_samples)
-        if self.batch_size > 1 or self.batch_strategy == "thompson":
-            return self._solve_batched(aggregation_func, budget, n_init_samples)
+        """MultiSurrogateOptimiser.solve's loop on the single surrogate of the aggregated values.  Every believer
+        pick's ``current_best`` is the minimum over the true and the fantasised aggregated values, and goes through
+        ``_get_proposed``; a reference direction is drawn after each evaluation, to aggregate it.
+        ``batch_strategy="thompson"``: every draw nominates the candidate with its smallest drawn value.
+        ``constraints="pof"``: ``current_best`` over the feasible rows only, and the surrogate is fitted together
+        with the constraint models (``_fit_many``; without the keyword it is ``_fit``'s one model, as before)."""
         problem = self.test_problem
-        weights = np.asarray([1 / problem.n_obj] * problem.n_obj)
-        Xsample, ysample = self._initial_samples(n_init_samples)
-        self._update_bounds(ysample, aggregation_func)
-        aggregated_samples = np.asarray([aggregation_func(i, weights) for i in ysample]).flatten()
-        ref_dirs = get_reference_directions("das-dennis", problem.n_obj, n_partitions=100)
-        hypervolume_convergence = []
-        for _ in range(budget):
-            self._update_bounds(ysample, aggregation_func)
-            hypervolume_convergence.append(self._hypervolume(ysample))
-            current_best = aggregated_samples[np.argmin(aggregated_samples)]
-            model = self._fit(Xsample, aggregated_samples)
-            next_X, _ = self._get_proposed(self._expected_improvement, model, current_best)
-            next_y = self._objective_function(problem, next_X)
-            ysample = np.vstack((ysample, next_y))
-            ref_dir = ref_dirs[np.random.randint(0, len(ref_dirs))]
-            aggregated_samples = np.append(aggregated_samples, aggregation_func(next_y, ref_dir))
-            Xsample = np.vstack((Xsample, next_X))
-        return self._result(ysample, Xsample, hypervolume_convergence, n_init_samples)
-
-    def _solve_batched(self, aggregation_func, budget, n_init_samples):
-        """Sequential-greedy batches with the Kriging believer (see MultiSurrogateOptimiser._solve_batched): one
-        fit per iteration; every pick's ``current_best`` is the minimum over the true and the fantasised
-        aggregated values, and the resident GP is conditioned on the pick with its posterior mean before the next.
-        ``batch_strategy="thompson"``: one AcquisitionEngine.thompson_batch on the single surrogate instead (every
-        draw nominates the candidate with its smallest drawn value), with the believer loop as its fallback."""
-        from ..acquisition import engine_for
-        problem = self.test_problem
-        q = self.batch_size
-        weights = np.asarray([1 / problem.n_obj] * problem.n_obj)
-        Xsample, ysample = self._initial_samples(n_init_samples)
-        self._update_bounds(ysample, aggregation_func)
-        aggregated_samples = np.asarray([aggregation_func(i, weights) for i in ysample]).flatten()
-        ref_dirs = get_reference_directions("das-dennis", problem.n_obj, n_partitions=100)
-        hypervolume_convergence = []
-        done = 0
-        while done < budget:
-            b = min(q, budget - done)
-            self._update_bounds(ysample, aggregation_func)
-            hypervolume_convergence.append(self._hypervolume(ysample))
-            model = self._fit(Xsample, aggregated_samples)
-            eng = engine_for([model], self.device)
-            fant, picks = aggregated_samples, None
-            if self.batch_strategy == "thompson":
-                picks = self._thompson_picks(eng, b)
-            if picks is None:              # the believer batch (also a Thompson iteration's fallback)
-                picks = []
-                for p in range(b):
-                    self._plan_ei(eng, fant[np.argmin(fant)])
-                    x, _ = self._maximise([model], None, eng=eng)
-                    picks.append(x)
-                    if p + 1 < b:
-                        fant = np.append(fant, eng.condition(x[None, :])[0, 0])
-            for x in picks:
-                next_y = self._objective_function(problem, x)
-                ysample = np.vstack((ysample, next_y))
-                ref_dir = ref_dirs[np.random.randint(0, len(ref_dirs))]
-                aggregated_samples = np.append(aggregated_samples, aggregation_func(next_y, ref_dir))
-                Xsample = np.vstack((Xsample, x))
-            done += b
-        return self._result(ysample, Xsample, hypervolume_convergence, n_init_samples)
-
-    def _solve_pof(self, aggregation_func, budget, n_init_samples):
-        """``constraints="pof"``: ``_solve_batched``'s loop (``batch_size`` 1 is a batch of one) with one GP on the
-        aggregated values and one per inequality constraint, EI weighted by the probability of feasibility, and
-        ``current_best`` taken over the feasible rows only (see MultiSurrogateOptimiser._solve_pof)."""
-        from ..acquisition import engine_for
-        problem = self.test_problem
-        q, c = self.batch_size, self.n_con
+        pof = self.constraints == "pof"
         weights = np.asarray([1 / problem.n_obj] * problem.n_obj)
         Xsample, ysample = self._initial_samples(n_init_samples)
         gsample = self._constraint_values(Xsample)
@@ -369,31 +238,38 @@ class MonoSurrogateOptimiser(BODriver):
         hypervolume_convergence = []
         done = 0
         while done < budget:
-            b = min(q, budget - done)
+            b = min(self.batch_size, budget - done)
             self._update_bounds(ysample, aggregation_func)
             hypervolume_convergence.append(self._hypervolume(ysample[self._feasible(gsample)]))
-            models = self._fit_many(Xsample, np.column_stack((aggregated_samples, gsample)))
+            if pof:
+                models = self._fit_many(Xsample, np.column_stack((aggregated_samples, gsample)))
+            else:
+                models = [self._fit(Xsample, aggregated_samples)]
             eng = engine_for(models, self.device)
-            fant, gfant, picks = aggregated_samples, gsample, []
-            for p in range(b):
-                ffeas = fant[self._feasible(gfant)]
-                if len(ffeas) == 0:
-                    pof = eng.log_feasibility if self.log_acquisition else eng.feasibility
-                    x, _ = self._maximise(models, lambda Xd: pof(Xd, c, self.pof_eps), eng=eng)
-                else:
-                    self._plan_ei(eng, ffeas[np.argmin(ffeas)])
-                    eng.plan_constraints(c, self.pof_eps)
-                    x, _ = self._maximise(models, None, eng=eng)
-                picks.append(x)
-                if p + 1 < b:
-                    m = eng.condition(x[None, :])
-                    fant, gfant = np.append(fant, m[0, 0]), np.vstack((gfant, m[:, 1:]))
+            fant, gfant, picks = aggregated_samples, gsample, None
+            if self.batch_strategy == "thompson":
+                picks = self._thompson_picks(eng, b)
+            if picks is None:              # the believer batch (also a Thompson iteration's fallback)
+                picks = []
+                for p in range(b):
+                    ffeas = fant[self._feasible(gfant)]
+                    if len(ffeas) == 0:
+                        x = self._maximise_feasibility(models, eng)
+                    else:                  # eng: conditioned since the fit, so picks 2..b search it as it stands
+                        x, _ = self._get_proposed(self._expected_improvement, models if pof else models[0],
+                                                  ffeas[np.argmin(ffeas)], **(dict(eng=eng) if p else {}))
+                    picks.append(x)
+                    if p + 1 < b:
+                        m = eng.condition(x[None, :])
+                        fant, gfant = np.append(fant, m[0, 0]), np.vstack((gfant, m[:, 1:]))
             for x in picks:
                 next_y = self._objective_function(problem, x)
                 ysample = np.vstack((ysample, next_y))
                 ref_dir = ref_dirs[np.random.randint(0, len(ref_dirs))]
                 aggregated_samples = np.append(aggregated_samples, aggregation_func(next_y, ref_dir))
                 Xsample = np.vstack((Xsample, x))
-            gsample = np.vstack((gsample, self._constraint_values(np.asarray(picks))))
+            gsample = np.vstack((gsample, self._constraint_values(picks)))
             done += b
-        return self._constrained_result(ysample, Xsample, gsample, hypervolume_convergence, n_init_samples)
+        if pof:
+            return self._constrained_result(ysample, Xsample, gsample, hypervolume_convergence, n_init_samples)
+        return self._result(ysample, Xsample, hypervolume_convergence, n_init_samples)

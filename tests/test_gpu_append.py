@@ -376,6 +376,46 @@ def test_batch_size_one_is_the_earlier_run_bitwise(golden_dir):
     assert np.array_equal(bits(X), bits(z["mono_X"]))
 
 
+def _batched_and_pof_runs():
+    """Xsample and hypervolume_convergence of one run of each loop shape beyond batch 1: believer batches and
+    constraints="pof", on both drivers.  Budget 4 in batches of 3 (one full, one truncated) or 2."""
+    import _constraints_fixture as cf
+    import optimobo_amd.algorithms.optimisers as opti
+    import optimobo_amd.scalarisations as sc
+    kw = dict(n_candidates=2048)
+    pof = dict(constraints="pof", mode="textbook", seed=1, batch_size=2, **kw)
+    runs = {}
+    np.random.seed(21)
+    opt = opti.MultiSurrogateOptimiser(_myproblem(), [0, 0], [700, 12], seed=2, batch_size=3, **kw)
+    runs["multi_q3"] = opt.solve(budget=4, n_init_samples=8)
+    np.random.seed(31)
+    opt = opti.MultiSurrogateOptimiser(cf.driver_problem(), [0, 0], [2.5, 2.0], **pof)
+    runs["multi_pof_q2"] = opt.solve(budget=4, n_init_samples=8)
+    np.random.seed(22)
+    opt = opti.MonoSurrogateOptimiser(_myproblem(), [0, 0], [700, 12], seed=3, batch_size=3, **kw)
+    runs["mono_q3"] = opt.solve(sc.Tchebicheff([0, 0], [700, 12]), budget=4, n_init_samples=8)
+    np.random.seed(33)
+    opt = opti.MonoSurrogateOptimiser(cf.driver_problem(), [0, 0], [2.5, 2.0], **pof)
+    runs["mono_pof_q2"] = opt.solve(sc.Tchebicheff([0, 0], [2.5, 2.0]), budget=4, n_init_samples=8)
+    out = {}
+    for name, res in runs.items():
+        out[name + "_X"] = res.Xsample
+        out[name + "_hv"] = np.asarray(res.hypervolume_convergence, np.float64)
+    return out
+
+
+def test_batched_and_pof_runs_are_the_earlier_runs_bitwise(golden_dir):
+    """The runs recorded while ``solve`` still had a loop of its own for batches and one for constraints="pof"
+    (tests/golden/batched_solve.npz; OMB_TEST_RECORD=<file> writes this run's arrays there before comparing)."""
+    z = np.load(os.path.join(golden_dir, "batched_solve.npz"), allow_pickle=False)
+    got = _batched_and_pof_runs()
+    if os.environ.get("OMB_TEST_RECORD"):
+        np.savez(os.environ["OMB_TEST_RECORD"], **got)
+    assert sorted(got) == sorted(z.files)
+    for name in z.files:
+        assert got[name].shape == z[name].shape and np.array_equal(bits(got[name]), bits(z[name])), name
+
+
 def test_batch_size_is_checked():
     import optimobo_amd.algorithms.optimisers as opti
     for bad in (0, -1, 1.5, True):
