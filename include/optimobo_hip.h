@@ -269,6 +269,29 @@ int omb_hvi_boxes(omb_ctx* ctx, int k, const double* y_dev, int64_t ld, int64_t 
  * past the grid reads the grid's last coordinate.  omb_hvi_boxes itself stays k ≥ 2. */
 int omb_hvi_paths(omb_ctx* ctx, int k, int S, const double* y_dev, int64_t ld, int64_t N, const double* coords_dev,
                   int C, const int32_t* box_off_host, const uint16_t* boxes_dev, double* out_dev);
+/* omb_hvi_paths with its gradient through the paths.  y_dev and dy_dev are omb_paths_grad's two outputs at the same
+ * pitch ld (dy_dev[((j·S + s)·d + l)·ld + i] = ∂y_{j,s,i}/∂x_l, d = n_var in [1, 64]):
+ *   ∂t_s/∂y_j = −Σ_b 1[lo_bj < y_j < hi_bj] Π_{l≠j} (hi_bl − max(y_l, lo_bl))⁺      (k = 1: −1[y < b_s])
+ *   ∂t_s/∂x   = Σ_j ∂t_s/∂y_j · dy[j·S + s], j ascending;   ∂out/∂x = ((…(0 + ∂t_0) + …) + ∂t_{S−1}) / S
+ * The inequalities are strict: a value exactly on a grid coordinate takes derivative 0 for that factor.  The sum over
+ * boxes runs in omb_hvi_paths' slices of 1024 boxes from the list's own start, added in slice order.
+ *   out_dev (N)               bitwise omb_hvi_paths' value
+ *   grad_dev[l·ld + i]        ∂out_i/∂x_l
+ *   t_dev (S, ld), tgrad_dev (S, d, ld)   the per-path t_s and ∂t_s/∂x; both NULL or both set
+ * One lane per candidate walks a path's list (a workgroup row per path, the path's grid in LDS), one lane per
+ * (candidate, dimension) chains and averages; no atomics; a candidate's results are bitwise the same whatever N, its
+ * column or the launch shape.  Where the value is NaN every gradient entry of the candidate is NaN (per path: where
+ * t_s is); where y_j ≥ r_j in every path every entry is exactly 0.  Asynchronous; the context's workspace is grown
+ * on demand (a grow synchronises first).
+ *   OMB_EINVAL  omb_hvi_paths' own, in its order; then d outside [1, 64], a NULL dy / grad with N > 0, exactly one of
+ *               t_dev / tgrad_dev NULL, one of the four off its 8-byte alignment
+ *   OMB_EUNSUP  omb_hvi_paths' own
+ * N = 0 returns OMB_OK and writes nothing.  Plans are untouched: under omb_plan_hvi_paths omb_eval_grad stays
+ * OMB_EUNSUP. */
+int omb_hvi_paths_grad(omb_ctx* ctx, int k, int S, int d, const double* y_dev, const double* dy_dev, int64_t ld,
+                       int64_t N, const double* coords_dev, int C, const int32_t* box_off_host,
+                       const uint16_t* boxes_dev, double* out_dev, double* grad_dev, double* t_dev,
+                       double* tgrad_dev);
 
 /* Hypervolume-based PoI of EMO (emo.py:176-228): cells_dev (C, 2, 2) [upper, lower]. */
 int omb_hvpoi(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
@@ -552,6 +575,19 @@ int omb_paths_set(omb_ctx* ctx, int obj, int S, int m, const double* omega_host,
  * Refusals, in this order: OMB_EINVAL for n_obj outside [1, OMB_MAX_OBJ], N < 0, ld < N, a null pointer with N > 0;
  * OMB_ESTATE for an objective that is not set, has no paths or another S than objective 0; OMB_EUNSUP as above. */
 int omb_paths_eval(omb_ctx* ctx, int n_obj, const double* Xc_dev, int64_t N, int64_t ld, double* out_dev);
+/* omb_paths_eval's values and the paths' gradients with respect to the candidate,
+ *   ∂f_s/∂x_j = −(1/ℓ_j) Σ_i w_is·sqrt(2σ_f²/m)·ω̃_ij·sin(ω̃_i·(x/ℓ) + b_i) + Σ_r v_rs·g_r·(x_j − X_rj)/ℓ_j²,
+ * g_r = −(5/3)σ_f²(1 + √5 r)e^{−√5 r} (Matern-5/2; finite at r = 0) or −k_r (RBF); x_j − X_rj is formed as a
+ * difference first, so a candidate on a training row stays accurate.
+ *   out_dev[(o·S + s)·ld + i]            bitwise omb_paths_eval's
+ *   grad_dev[((o·S + s)·d + j)·ld + i]   ∂f_{o,s}/∂x_j at Xc_i (the candidate index innermost)
+ * The evaluation kernel's wave with one more accumulator per input dimension, the dimensions in groups of 8 (one
+ * pass over the tiles per group), a fixed tile order and no atomics: an entry is bitwise the same whatever N, the
+ * point's column and the launch grid.  A NaN coordinate makes that candidate's entries NaN, nobody else's.
+ * Asynchronous; N = 0 is OMB_OK and writes nothing.  Limits and refusals are omb_paths_eval's, in its order; a NULL
+ * grad_dev with N > 0 is OMB_EINVAL where a NULL out_dev is. */
+int omb_paths_grad(omb_ctx* ctx, int n_obj, const double* Xc_dev, int64_t N, int64_t ld, double* out_dev,
+                   double* grad_dev);
 /* res_dev[(o·S + s)·2 + {0, 1}] = { min_i f_{o,s}(Xc_i), the lowest such i + offset (as double) }, objectives
  * 0..n_obj-1: omb_paths_eval's tile loop with the minimum taken in its epilogue, so the (n_obj·S, N) matrix never
  * exists.  The value is bitwise the minimum of omb_paths_eval's row.  Every comparison is "smaller value, else lower

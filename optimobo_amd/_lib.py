@@ -63,6 +63,7 @@ SIGNATURES = {
     "omb_ehvi_boxes_k": (_i, [_p, _i, _p, _p, _i64, _i64, _p, _i, _p, _i, _p]),
     "omb_hvi_boxes": (_i, [_p, _i, _p, _i64, _i64, _p, _i, _p, _i, _p]),
     "omb_hvi_paths": (_i, [_p, _i, _i, _p, _i64, _i64, _p, _i, _p, _p, _p]),
+    "omb_hvi_paths_grad": (_i, [_p, _i, _i, _i, _p, _p, _i64, _i64, _p, _i, _p, _p, _p, _p, _p, _p]),
     "omb_hvpoi": (_i, [_p, _p, _p, _i64, _i64, _p, _i, _p]),
     "omb_expdec": (_i, [_p, _i, _p, _p, _i64, _i64, _p, _i, _i, _dp, _dp, _dp, _dp, _d, _p]),
     "omb_ei": (_i, [_p, _p, _p, _i64, _d, _d, _p]),
@@ -109,6 +110,7 @@ SIGNATURES = {
     "omb_paths_set": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _d]),
     "omb_paths_eval": (_i, [_p, _i, _p, _i64, _i64, _p]),
     "omb_paths_min": (_i, [_p, _i, _p, _i64, _i64, _p]),
+    "omb_paths_grad": (_i, [_p, _i, _p, _i64, _i64, _p, _p]),
     "omb_ea_search": (_i, [_p, _i, _d, _d, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     # GP fit on the device
     "omb_gp_lml_grad": (_i, [_p, _i, _i, _i, _p, _p, _dp, _d, _d, _dp, _dp, _dp]),

@@ -39,7 +39,8 @@ class AcquisitionEngine:
         self._stale = set()     # objectives whose device state was conditioned on top of _resident[o]
         self.condition_jitter = 0.0
         self.paths_floored = 0
-        self.ystar = None       # sample_minima's last result (n_obj, S)
+        self.ystar = None           # sample_minima's last result (n_obj, S)
+        self.ystar_X = None         # and its minimisers (n_obj, S, d)
         self._front_lists = None    # sample_fronts' packed box lists (coords, box_off, boxes)
         self._cond_X = []           # rows ``condition`` appended to every resident state since the last upload
         self.n_obj = 0
@@ -172,8 +173,14 @@ class AcquisitionEngine:
         Xc = Xc if isinstance(Xc, torch.Tensor) else self._dev(np.atleast_2d(Xc))
         return self.ctx.paths_eval(Xc, self.n_obj)
 
+    def path_values_and_grad(self, Xc):
+        """The installed sample paths and their gradients at Xc (N, d) → device tensors (vals (n_obj, S, N), grad
+        (n_obj, S, d, N)) (AcqContext.paths_grad); vals are bitwise ``path_values``'."""
+        Xc = Xc if isinstance(Xc, torch.Tensor) else self._dev(np.atleast_2d(Xc))
+        return self.ctx.paths_grad(Xc, self.n_obj)
+
     def sample_minima(self, S, lower, upper, n_candidates=1 << 16, seed=0, n_features=1024, refine_rounds=0, shrink=0.1,
-                      n_refine=4096):
+                      n_refine=4096, polish=False):
         """The minimum of S fresh posterior sample paths of every loaded model over the box → ``ystar`` (n_obj, S) as
         numpy, kept on the engine for ``mes`` / ``plan_mes`` (max-value entropy search).
 
@@ -183,7 +190,11 @@ class AcquisitionEngine:
         more over the resident training inputs, so that each sampled minimum is at or below its path's value at every
         observed x.  With ``refine_rounds`` > 0, ``thompson_batch``'s refinement: round r evaluates ``n_refine``
         Sobol' points of the box ``shrink``^r times the bounds' size around each path's minimiser (clipped to the
-        bounds; one ``paths_min`` per round, objective and path — the boxes differ) and keeps a smaller value.  The
+        bounds; one ``paths_min`` per round, objective and path — the boxes differ) and keeps a smaller value.  With
+        ``polish``, every (model, path) minimiser is then the start of a bounded L-BFGS-B run on that path's own
+        gradient (Wilson et al. 2020 minimise a path by gradient descent): the n_obj·S runs advance in lockstep, each
+        round is one ``path_values_and_grad`` at the active runs' points (a run reads its own path's row), and a
+        smaller value is kept.  The minimisers stay on the engine as ``ystar_X`` (n_obj, S, d).  The
         installed plan and the Sobol' state of the context are overwritten; the paths stay installed."""
         S = int(S)
         if not 1 <= S <= 16:
@@ -217,7 +228,24 @@ class AcquisitionEngine:
                     if v < ystar[o, s]:
                         ystar[o, s] = v
                         Xbest[o, s] = Xr[int(ir[o, s])].cpu().numpy()
+        if polish:
+            def own(order, X):      # run r = o·S + s reads path s of model o at its own point
+                v, g = self.path_values_and_grad(X)
+                v, g = v.cpu().numpy(), g.cpu().numpy()
+                o, p = np.asarray(order) // S, np.asarray(order) % S
+                i = np.arange(len(order))
+                return v[o, p, i], g[o, p, :, i]
+
+            X1, _ = self._lockstep_minimise(np.clip(Xbest.reshape(k * S, d), lower, upper), own, lower, upper)
+            v1 = self.path_values(X1).cpu().numpy()
+            for o in range(k):
+                for s in range(S):
+                    v = v1[o, s, o * S + s]
+                    if v < ystar[o, s]:
+                        ystar[o, s] = v
+                        Xbest[o, s] = X1[o * S + s]
         self.ystar = ystar
+        self.ystar_X = Xbest
         return ystar
 
     def _ystar(self, ystar, what):
@@ -290,13 +318,22 @@ class AcquisitionEngine:
         lists = self._fronts("nehvi")
         return self.ctx.hvi_paths(self.path_values(Xc)[:lists[0].shape[1]], *lists)
 
+    def nehvi_value_and_grad(self, X):
+        """``nehvi`` and its gradient at host points X (m, d) → numpy (v (m,), g (m, d)), over the fronts of the last
+        ``sample_fronts``: ``path_values_and_grad`` → ``hvi_paths_grad``.  v is bitwise ``nehvi``'s value."""
+        lists = self._fronts("nehvi_value_and_grad")
+        k = lists[0].shape[1]
+        y, dy = self.path_values_and_grad(X)
+        v, g = self.ctx.hvi_paths_grad(y[:k], dy[:k], *lists)
+        return v.cpu().numpy().astype(np.float64), g.cpu().numpy().astype(np.float64)
+
     def plan_nehvi(self):
         """``nehvi`` as the fused chain's plan; ``has_gradient`` is False, so ``polish="auto"`` takes the stencil."""
         self.ctx.plan_hvi_paths(*self._fronts("plan_nehvi"))
 
     def thompson_batch(self, q, lower, upper, PF=None, max_point=None, n_candidates=None, seed=0,
                        max_boxes=1 << 20, sampler="joint", n_features=1024, refine_rounds=0, shrink=0.1,
-                       n_refine=4096):
+                       n_refine=4096, polish=False):
         """A batch of q proposals by Thompson sampling over the loaded models → (X (q, d), info).
 
         The candidates are the first ``n_candidates`` points of the device Sobol' sequence seeded by ``seed``
@@ -325,7 +362,12 @@ class AcquisitionEngine:
         the bounds' size around its nominee (clipped to the bounds), and the nominee moves where its HVI under that
         draw (one model: its drawn value) strictly improves.  ``info`` gains ``sampler``, ``n_features``,
         ``refined``, the number of draws each round moved, and ``floored`` (``sample_paths``' ``paths_floored``);
-        ``jitter`` is 0 per model; ``indices`` are round 0's."""
+        ``jitter`` is 0 per model; ``indices`` are round 0's.  With ``polish`` (``sampler="paths"`` alone) every live
+        draw's nominee is then the start of a bounded L-BFGS-B run under its own draw — one model: path b is
+        minimised; else draw b's HVI over the front is maximised (``hvi_paths_grad(per_path=True)`` over the front
+        packed q times, entry (b, b)) — the runs advance in lockstep, the nominee moves only on strict improvement
+        and never onto a point another nominee holds (runs that end in the same corner of the box), and ``info``
+        gains ``polished``, the number of nominees moved."""
         lower = np.asarray(lower, np.float64).reshape(-1)
         upper = np.asarray(upper, np.float64).reshape(-1)
         d, k, q = lower.size, self.n_obj, int(q)
@@ -334,6 +376,8 @@ class AcquisitionEngine:
         if sampler not in ("joint", "paths"):
             raise ValueError(f"thompson_batch: sampler must be 'joint' or 'paths', not {sampler!r}")
         paths = sampler == "paths"
+        if polish and not paths:
+            raise ValueError("thompson_batch: polish needs sampler='paths' (a joint draw is no function of x)")
         if paths and q > 16:
             raise ValueError(f"thompson_batch: sampler='paths' draws at most 16 paths per call (q={q})")
         if paths:
@@ -400,6 +444,33 @@ class AcquisitionEngine:
                     moved += 1
             refined.append(moved)
         info.update(sampler="paths", n_features=int(n_features), refined=refined, floored=self.paths_floored)
+        if polish:
+            act = np.flatnonzero(live)
+            lists = None if k == 1 else pareto.pack_box_lists([(geo[0], None, geo[1])] * q)
+
+            def own(order, X):      # run r is draw act[r]: −(its score under its own draw) and the gradient of that
+                b = act[np.asarray(order)]
+                i = np.arange(len(order))
+                y, dy = self.path_values_and_grad(X)
+                if k == 1:
+                    return y[0].cpu().numpy()[b, i], dy[0].cpu().numpy()[b, :, i]
+                _, _, t, tg = self.ctx.hvi_paths_grad(y, dy, *lists, per_path=True)
+                return -t.cpu().numpy()[b, i], -tg.cpu().numpy()[b, i, :]
+
+            moved = 0
+            if act.size:
+                X1, _ = self._lockstep_minimise(np.clip(X[act], lower, upper), own, lower, upper)
+                f1, _ = own(range(act.size), X1)
+                for r, b in enumerate(act):
+                    v = f1[r] if k == 1 else -f1[r]
+                    # two runs can end in the same corner of the box: a point another nominee holds is not taken,
+                    # so the batch stays free of duplicates as thompson_select left it
+                    taken = any(np.array_equal(X1[r], X[o]) for o in range(q) if o != b)
+                    if (v < values[b] if k == 1 else v > values[b]) and not taken:
+                        X[b] = X1[r]
+                        values[b] = v
+                        moved += 1
+            info["polished"] = moved
         return X, info
 
     def ehvi3d(self, Xc, max_point, PF, cache):
@@ -570,35 +641,27 @@ class AcquisitionEngine:
         v, g = self.ctx.eval_grad(self._dev(np.atleast_2d(X)))
         return v.cpu().numpy().astype(np.float64), g.cpu().numpy().astype(np.float64)
 
-    def polish_batch(self, starts, lower, upper, maxiter=100):
-        """``polish`` for several starts at once on the analytic gradient: one bounded L-BFGS-B run per start
-        (scipy's routine in reverse communication, gp._LbfgsbRun), advanced in lockstep — every round is ONE
-        omb_eval_grad on the points of the runs still active, instead of a (2d+1)-point stencil per run and step.
-        ``starts``: points (m, d), or (x, v) pairs as ``_starts`` returns them (the value is taken again at x).
-        The objective of run s is −a(x)/|a(x0_s)|, ``polish``'s scaling.  Returns [(x, v)] in the order of the
-        starts; each keeps its x0 unless the polished point scores strictly higher."""
+    def _lockstep_minimise(self, X0, own, lower, upper, maxiter=100):
+        """One bounded L-BFGS-B run per row of X0 (m, d) (scipy's routine in reverse communication, gp._LbfgsbRun),
+        advanced in lockstep: every round is ONE call ``own(order, X)`` → (f (len,), g (len, d)), the objectives to
+        minimise of the runs ``order`` still active at their points X.  The objective of run s is f/|f(x0_s)|,
+        ``polish``'s scaling; a non-finite value reads as +inf with a zero gradient, and a run whose start has one
+        stays where it is.  Returns (the end points (m, d) inside the bounds, f at X0)."""
         from .gp import _LbfgsbRun, _lockstep_ok
-        lower = np.asarray(lower, np.float64)
-        upper = np.asarray(upper, np.float64)
-        d = lower.size
-        if len(starts) and isinstance(starts[0], tuple):
-            starts = [s[0] for s in starts]
-        X0 = np.clip(np.asarray(starts, np.float64).reshape(-1, d), lower, upper)
-        m = X0.shape[0]
-        if m == 0:
-            return []
-        v0, g0 = self.value_and_grad(X0)
-        ok = np.isfinite(v0)
-        scale = np.where(ok & (v0 != 0.0), 1.0 / np.where(ok & (v0 != 0.0), np.abs(v0), 1.0), 1.0)
+        m, d = X0.shape
+        f0, g0 = own(list(range(m)), X0)
+        f0 = np.asarray(f0, np.float64)
+        ok = np.isfinite(f0)
+        scale = np.where(ok & (f0 != 0.0), 1.0 / np.where(ok & (f0 != 0.0), np.abs(f0), 1.0), 1.0)
 
-        def fg(s, v, g):
-            if not np.isfinite(v):
+        def fg(s, f, g):
+            if not np.isfinite(f):
                 return np.inf, np.zeros(d)
-            return -v * scale[s], -np.where(np.isfinite(g), g, 0.0) * scale[s]
+            return f * scale[s], np.where(np.isfinite(g), g, 0.0) * scale[s]
 
         X1 = X0.copy()
         if _lockstep_ok():
-            runs = {s: _LbfgsbRun(X0[s], *fg(s, v0[s], g0[s]), 15000, int(maxiter), bounds=(lower, upper))
+            runs = {s: _LbfgsbRun(X0[s], *fg(s, f0[s], g0[s]), 15000, int(maxiter), bounds=(lower, upper))
                     for s in range(m) if ok[s]}
             while runs:
                 ask = {}
@@ -611,19 +674,50 @@ class AcquisitionEngine:
                 if not ask:
                     break
                 order = sorted(ask)
-                v, g = self.value_and_grad(np.stack([ask[s] for s in order]))
+                f, g = own(order, np.stack([ask[s] for s in order]))
                 for i, s in enumerate(order):
-                    runs[s].supply(ask[s], *fg(s, v[i], g[i]))
+                    runs[s].supply(ask[s], *fg(s, f[i], g[i]))
         else:   # another scipy layout: the same runs one after another
             from scipy.optimize import minimize
             for s in np.flatnonzero(ok):
                 def one(x, s=s):
-                    v, g = self.value_and_grad(np.clip(x, lower, upper)[None, :])
-                    return fg(s, v[0], g[0])
+                    f, g = own([int(s)], np.clip(x, lower, upper)[None, :])
+                    return fg(s, f[0], g[0])
                 X1[s] = minimize(one, X0[s], jac=True, method="L-BFGS-B", bounds=list(zip(lower, upper)),
                                  options={"maxiter": int(maxiter)}).x
-        X1 = np.clip(X1, lower, upper)
-        v1 = self.score(None, X1)
+        return np.clip(X1, lower, upper), f0
+
+    def polish_batch(self, starts, lower, upper, maxiter=100, value_and_grad=None):
+        """``polish`` for several starts at once on the analytic gradient: one bounded L-BFGS-B run per start
+        (``_lockstep_minimise``), advanced in lockstep — every round is ONE omb_eval_grad on the points of the runs
+        still active, instead of a (2d+1)-point stencil per run and step.
+        ``starts``: points (m, d), or (x, v) pairs as ``_starts`` returns them (the value is taken again at x).
+        The objective of run s is −a(x)/|a(x0_s)|, ``polish``'s scaling.  Returns [(x, v)] in the order of the
+        starts; each keeps its x0 unless the polished point scores strictly higher.
+        ``value_and_grad``: a callable X (m, d) → numpy (v (m,), g (m, d)) in place of ``self.value_and_grad`` and of
+        the final ``score`` (None: the plan's own, as before)."""
+        vg = self.value_and_grad if value_and_grad is None else value_and_grad
+        lower = np.asarray(lower, np.float64)
+        upper = np.asarray(upper, np.float64)
+        d = lower.size
+        if len(starts) and isinstance(starts[0], tuple):
+            starts = [s[0] for s in starts]
+        X0 = np.clip(np.asarray(starts, np.float64).reshape(-1, d), lower, upper)
+        m = X0.shape[0]
+        if m == 0:
+            return []
+
+        def own(order, X):
+            v, g = vg(X)
+            return -np.asarray(v, np.float64), -np.asarray(g, np.float64)
+
+        X1, f0 = self._lockstep_minimise(X0, own, lower, upper, maxiter)
+        v0 = -f0
+        if value_and_grad is None:
+            v1 = self.score(None, X1)
+        else:
+            v1 = np.asarray(value_and_grad(X1)[0], np.float64)
+            v1 = np.where(np.isnan(v1), -np.inf, v1)
         v0s = np.where(np.isnan(v0), -np.inf, v0)
         return [(X1[s], float(v1[s])) if v1[s] > v0s[s] else (X0[s], float(v0s[s])) for s in range(m)]
 
@@ -687,15 +781,24 @@ class AcquisitionEngine:
         (L-BFGS-B on the device gradient, one omb_eval_grad per round for all starts); it needs the plan
         (``acq_fn`` None) and a plan with a gradient (``has_gradient``), ValueError otherwise.  ``polish="auto"``
         is "analytic" where that applies and the stencil polish (True) elsewhere.
+        ``polish="paths"`` is the same finish under the noisy EHVI / noisy EI plan, whose gradient goes through the
+        sample paths (``nehvi_value_and_grad``: omb_paths_grad → omb_hvi_paths_grad, one pair per round for all
+        starts); it needs ``acq_fn`` None, the plan set by ``plan_nehvi`` and its fronts still on the engine,
+        ValueError otherwise.
         Returns (x_best (d,), value).
         """
         lower = np.asarray(lower, np.float64)
         upper = np.asarray(upper, np.float64)
         d = lower.size
         W, rank = world()
-        if isinstance(polish, str):
+        if polish == "paths":
+            kind = self.ctx.plan_kind
+            if acq_fn is not None or kind is None or kind[0] != "omb_plan_hvi_paths" or self._front_lists is None:
+                raise ValueError("polish='paths' needs the planned acquisition (acq_fn=None), the plan set by "
+                                 "plan_nehvi and the fronts of sample_fronts still on the engine")
+        elif isinstance(polish, str):
             if polish not in ("analytic", "auto"):
-                raise ValueError(f"polish must be True, False, 'analytic' or 'auto', not {polish!r}")
+                raise ValueError(f"polish must be True, False, 'analytic', 'auto' or 'paths', not {polish!r}")
             can = acq_fn is None and self.has_gradient()
             if polish == "analytic" and not can:
                 raise ValueError("polish='analytic' needs the planned acquisition (acq_fn=None) and a plan with a "
@@ -732,7 +835,7 @@ class AcquisitionEngine:
                 if g[1] >= 0 and g[0] > best_v:
                     best_x = self.ctx.sobol(int(g[1]), 1).cpu().numpy()[0]   # the winner, regenerated
                     best_v = float(g[0])
-            if polish and polish != "analytic":
+            if polish and polish not in ("analytic", "paths"):
                 if W == 1:
                     best_x, best_v = self.polish(acq_fn, best_x, best_v, lower, upper)
                 else:
@@ -742,13 +845,14 @@ class AcquisitionEngine:
                     torch.distributed.broadcast_object_list(box, src=0)
                     best_x, best_v = np.asarray(box[0][0], np.float64), float(box[0][1])
             results.append((best_x, best_v))
-        if polish == "analytic":
+        if polish in ("analytic", "paths"):
+            vg = self.nehvi_value_and_grad if polish == "paths" else None
             if W == 1:
-                results = self.polish_batch(results, lower, upper)
+                results = self.polish_batch(results, lower, upper, value_and_grad=vg)
             else:
                 box = [None]
                 if rank == 0:
-                    box[0] = self.polish_batch(results, lower, upper)
+                    box[0] = self.polish_batch(results, lower, upper, value_and_grad=vg)
                 torch.distributed.broadcast_object_list(box, src=0)
                 results = [(np.asarray(x, np.float64), float(v)) for x, v in box[0]]
         # the best start; ties to the earliest (the single-start search's when it ties)

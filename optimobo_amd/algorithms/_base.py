@@ -30,11 +30,12 @@ class BODriver:
     # thompson_sampler="paths": random Fourier features per model and refinement rounds around every nominee
     thompson_features = 1024
     thompson_refine_rounds = 2
+    path_gradients = False       # the keyword's default (an instance attribute only where it is True)
 
     def __init__(self, test_problem, ideal_point=None, max_point=None, mode="reference", n_candidates=1 << 14,
                  refine_rounds=2, seed=None, device=None, polish=True, starts=None, noise=0.0, batch_size=1,
                  constraints=None, batch_strategy="believer", thompson_sampler="joint", log_acquisition=False,
-                 acquisition=None, mes_samples=8, mes_candidates=1 << 16):
+                 acquisition=None, mes_samples=8, mes_candidates=1 << 16, path_gradients=False):
         self.test_problem = test_problem
         self.max_point = max_point
         self.ideal_point = ideal_point
@@ -94,6 +95,17 @@ class BODriver:
         # averaged over ``nehvi_samples`` fronts (best values) drawn from the posterior at the points already evaluated,
         # in place of the improvement over the observed — noisy — front (AcquisitionEngine.sample_fronts)
         self.acquisition = self._check_acquisition(acquisition, mes_samples, mes_candidates)
+        # finish what a pick takes from posterior sample paths on the paths' own device gradient (not in the reference):
+        # acquisition="mes" polishes every sampled minimum (sample_minima(polish=True)), thompson_sampler="paths" every
+        # nominee under its own draw (thompson_batch(polish=True)), acquisition="nehvi" / "nei" finishes the search
+        # with maximise(polish="paths").  False is the run without it, call for call.
+        if not isinstance(path_gradients, (bool, np.bool_)):
+            raise ValueError(f"path_gradients must be True or False, not {path_gradients!r}")
+        if path_gradients and self.acquisition is None and self.thompson_sampler != "paths":
+            raise ValueError("path_gradients=True needs something drawn from sample paths: acquisition='mes', 'nehvi' "
+                             "or 'nei', or thompson_sampler='paths'")
+        if path_gradients:      # False stays the class attribute: the instance is the one built without the keyword
+            self.path_gradients = True
         self.thompson_fallbacks = 0   # Thompson iterations that fell back to the believer batch
         self._iteration = 0
         self._mes_picks = 0
@@ -197,7 +209,7 @@ class BODriver:
         conditioned state."""
         ystar = eng.sample_minima(self.mes_samples, self.test_problem.xl, self.test_problem.xu,
                                   n_candidates=self.mes_candidates, seed=self._path_seed(),
-                                  n_features=self.mes_features)
+                                  n_features=self.mes_features, **({"polish": True} if self.path_gradients else {}))
         eng.plan_mes(ystar[:k])
 
     def _check_constraints_option(self, constraints):
@@ -291,8 +303,11 @@ class BODriver:
         again would undo); None loads ``models``."""
         if eng is None:
             eng = engine_for(models, self.device)
+        polish = self.polish
+        if self.path_gradients and acq_fn is None and self.acquisition in ("nehvi", "nei"):
+            polish = "paths"
         return eng.maximise(acq_fn, self.test_problem.xl, self.test_problem.xu, n_candidates=self.n_candidates,
-                            seed=self._search_seed(), refine_rounds=self.refine_rounds, polish=self.polish,
+                            seed=self._search_seed(), refine_rounds=self.refine_rounds, polish=polish,
                             starts=self.starts)
 
     def _maximise_plan(self, models, eng):
@@ -321,6 +336,8 @@ class BODriver:
         kw = {}
         if self.thompson_sampler == "paths":
             kw = dict(sampler="paths", n_features=self.thompson_features, refine_rounds=self.thompson_refine_rounds)
+            if self.path_gradients:
+                kw["polish"] = True
         try:
             X, _ = eng.thompson_batch(b, self.test_problem.xl, self.test_problem.xu, PF=PF,
                                       max_point=self.max_point if PF is not None else None,

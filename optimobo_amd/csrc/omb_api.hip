@@ -1040,6 +1040,35 @@ int omb_hvi_paths(omb_ctx* ctx, int k, int S, const double* y_dev, int64_t ld, i
   return run_hvi_paths(ctx, pl, y_dev, ld, N, out_dev, "hvi_paths");
 }
 
+// Candidates per pass of omb_hvi_paths_grad: bounds its workspace at S·(k + 1)·chunk doubles (every lane's work
+// depends on its candidate alone, so the chunking leaves every bit as it is)
+constexpr int64_t kHviPathsGradChunk = 1 << 16;
+
+int omb_hvi_paths_grad(omb_ctx* ctx, int k, int S, int d, const double* y_dev, const double* dy_dev, int64_t ld,
+                       int64_t N, const double* coords_dev, int C, const int32_t* box_off_host,
+                       const uint16_t* boxes_dev, double* out_dev, double* grad_dev, double* t_dev,
+                       double* tgrad_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if ((rc = check_hvi_paths_grad(E(ctx), k, S, d, y_dev, dy_dev, ld, N, coords_dev, C, box_off_host, boxes_dev, out_dev,
+                                 grad_dev, t_dev, tgrad_dev)))
+    return rc;
+  if (N == 0) return OMB_OK;
+  const int64_t chunk = N < kHviPathsGradChunk ? N : kHviPathsGradChunk;
+  if ((rc = grow_dev(ctx, ctx->hws, sizeof(double) * (size_t)hvi_paths_grad_ws_doubles(chunk, k, S),
+                     "HVI path gradient workspace")))
+    return rc;
+  for (int64_t c0 = 0; c0 < N; c0 += chunk) {
+    const int64_t nc = N - c0 < chunk ? N - c0 : chunk;
+    hipError_t e = launch_hvi_paths_grad(ctx->stream, k, S, d, y_dev + c0, dy_dev + c0, ld, nc, coords_dev, C,
+                                         boxes_dev, box_off_host, out_dev + c0, grad_dev + c0,
+                                         t_dev ? t_dev + c0 : nullptr, tgrad_dev ? tgrad_dev + c0 : nullptr,
+                                         ctx->hws.as<double>());
+    if (e != hipSuccess) return hip_fail(ctx, e, "hvi_paths_grad");
+  }
+  return OMB_OK;
+}
+
 int omb_hvpoi(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
               const double* cells_dev, int C, double* out_dev) {
   int rc = enter(ctx);
@@ -1999,6 +2028,30 @@ int omb_paths_eval(omb_ctx* ctx, int n_obj, const double* Xc_dev, int64_t N, int
   if ((N + 63) / 64 > 0x7fffffffLL) return fail(ctx, OMB_EUNSUP, "N=%lld too large", (long long)N);
   hipError_t e = launch_paths_eval(ctx->stream, pa, n_obj, ctx->obj[0].kind, ctx->paths_libcos, Xc_dev, N, ld, out_dev);
   if (e != hipSuccess) return hip_fail(ctx, e, "paths_eval");
+  return OMB_OK;
+}
+
+int omb_paths_grad(omb_ctx* ctx, int n_obj, const double* Xc_dev, int64_t N, int64_t ld, double* out_dev,
+                   double* grad_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  PathsObjInfo info[OMB_MAX_OBJ];
+  for (int o = 0; o < OMB_MAX_OBJ; ++o) info[o] = paths_info(ctx->obj[o]);
+  if ((rc = check_paths_grad(E(ctx), n_obj, Xc_dev, N, ld, out_dev, grad_dev, info))) return rc;
+  PathArgs pa{};
+  for (int o = 0; o < n_obj; ++o) {
+    const ObjState& s = ctx->obj[o];
+    if (s.d != ctx->obj[0].d) return fail(ctx, OMB_EINVAL, "objectives disagree on n_var (%d vs %d)", s.d, ctx->obj[0].d);
+    if (s.kind != ctx->obj[0].kind) return fail(ctx, OMB_EINVAL, "objectives disagree on kernel kind");
+    pa.o[o] = PathObj{s.dev, s.path_Of, s.path_Wf, s.path_Vf, s.path_MT, s.R, s.path_S, 0};
+  }
+  pa.d = ctx->obj[0].d;
+  pa.DP = ctx->obj[0].DP;
+  if (N == 0) return OMB_OK;
+  if ((N + 63) / 64 > 0x7fffffffLL) return fail(ctx, OMB_EUNSUP, "N=%lld too large", (long long)N);
+  hipError_t e = launch_paths_grad(ctx->stream, pa, n_obj, ctx->obj[0].kind, ctx->paths_libcos, Xc_dev, N, ld, out_dev,
+                                   grad_dev);
+  if (e != hipSuccess) return hip_fail(ctx, e, "paths_grad");
   return OMB_OK;
 }
 

@@ -156,6 +156,12 @@ int check_paths_eval(std::string* err, int n_obj, const void* Xc, int64_t N, int
   return OMB_OK;
 }
 
+int check_paths_grad(std::string* err, int n_obj, const void* Xc, int64_t N, int64_t ld, const void* out,
+                     const void* grad, const PathsObjInfo* info) {
+  // a null grad is refused where a null out is: the remaining refusals are check_paths_eval's own, in its order
+  return check_paths_eval(err, n_obj, Xc, N, ld, (N > 0 && !grad) ? nullptr : out, info);
+}
+
 int check_paths_min(std::string* err, int n_obj, const void* Xc, int64_t N, const void* res, const PathsObjInfo* info) {
   if (n_obj < 1 || n_obj > OMB_MAX_OBJ) return errf(err, OMB_EINVAL, "n_obj=%d outside [1, %d]", n_obj, OMB_MAX_OBJ);
   if (N < 0) return errf(err, OMB_EINVAL, "N=%lld < 0", (long long)N);
@@ -189,8 +195,9 @@ int check_plan_mes(std::string* err, int k, int S, const double* ystar) {
   return OMB_OK;
 }
 
-int check_hvi_paths(std::string* err, int k, int S, const void* y, int64_t ld, int64_t N, const void* coords, int C,
-                    const int32_t* box_off, const void* boxes, const void* out) {
+// check_hvi_paths' OMB_EINVAL refusals, then its OMB_EUNSUP ones (check_hvi_paths_grad puts its own between them)
+static int check_hvi_paths_args(std::string* err, int k, int S, const void* y, int64_t ld, int64_t N,
+                                const void* coords, const int32_t* box_off, const void* boxes, const void* out) {
   if (k < 1 || k > OMB_MAX_OBJ)
     return errf(err, OMB_EINVAL, "the sampled-front improvement needs 1 <= k <= %d objectives (k=%d)", OMB_MAX_OBJ, k);
   if (S < 1 || S > kPathsMaxS) return errf(err, OMB_EINVAL, "S=%d paths outside [1, %d]", S, kPathsMaxS);
@@ -206,6 +213,10 @@ int check_hvi_paths(std::string* err, int k, int S, const void* y, int64_t ld, i
     return errf(err, OMB_EINVAL, "path values, grids or output not 8-byte aligned");
   if ((uintptr_t)boxes & 3) return errf(err, OMB_EINVAL, "box lists not 4-byte aligned");
   if (ld < N) return errf(err, OMB_EINVAL, "ld=%lld < N=%lld", (long long)ld, (long long)N);
+  return OMB_OK;
+}
+
+static int check_hvi_paths_limits(std::string* err, int k, int S, int C, const int32_t* box_off) {
   // one path's grid is staged in the 64 KiB of dynamic LDS; the box lists are streamed
   if (C < 2 || (int64_t)k * C > kMaxLdsDoubles)
     return errf(err, OMB_EUNSUP, "grid size C=%d outside [2, %d] for k=%d (k*C <= %d)", C, kMaxLdsDoubles / k, k,
@@ -213,6 +224,26 @@ int check_hvi_paths(std::string* err, int k, int S, const void* y, int64_t ld, i
   if (box_off[S] > kMaxBoxesK)
     return errf(err, OMB_EUNSUP, "box count box_off[%d]=%d above %d", S, box_off[S], kMaxBoxesK);
   return OMB_OK;
+}
+
+int check_hvi_paths(std::string* err, int k, int S, const void* y, int64_t ld, int64_t N, const void* coords, int C,
+                    const int32_t* box_off, const void* boxes, const void* out) {
+  const int rc = check_hvi_paths_args(err, k, S, y, ld, N, coords, box_off, boxes, out);
+  return rc ? rc : check_hvi_paths_limits(err, k, S, C, box_off);
+}
+
+int check_hvi_paths_grad(std::string* err, int k, int S, int d, const void* y, const void* dy, int64_t ld, int64_t N,
+                         const void* coords, int C, const int32_t* box_off, const void* boxes, const void* out,
+                         const void* grad, const void* t, const void* tgrad) {
+  const int rc = check_hvi_paths_args(err, k, S, y, ld, N, coords, box_off, boxes, out);
+  if (rc) return rc;
+  if (d < 1 || d > kPathsMaxDim) return errf(err, OMB_EINVAL, "d=%d outside [1, %d]", d, kPathsMaxDim);
+  if (N > 0 && (!dy || !grad)) return errf(err, OMB_EINVAL, "null path gradients or gradient output");
+  if ((t == nullptr) != (tgrad == nullptr))
+    return errf(err, OMB_EINVAL, "the per-path outputs t and tgrad come together or not at all");
+  if (((uintptr_t)dy | (uintptr_t)grad | (uintptr_t)t | (uintptr_t)tgrad) & 7)
+    return errf(err, OMB_EINVAL, "path gradients or gradient outputs not 8-byte aligned");
+  return check_hvi_paths_limits(err, k, S, C, box_off);
 }
 
 int check_box_lists(std::string* err, int k, int S, int C, const int32_t* box_off, const uint16_t* boxes) {

@@ -91,6 +91,9 @@ int check_paths_set(std::string* err, int obj, int S, int m, const void* omega, 
 // paths, or with another S than objective 0; OMB_EUNSUP for n_var > kPathsMaxDim or n_train > OMB_MAX_TRAIN_DENSE.
 int check_paths_eval(std::string* err, int n_obj, const void* Xc, int64_t N, int64_t ld, const void* out,
                      const PathsObjInfo* info);
+// omb_paths_grad: check_paths_eval's refusals in its order, a null grad (N > 0) refused where a null out is.
+int check_paths_grad(std::string* err, int n_obj, const void* Xc, int64_t N, int64_t ld, const void* out,
+                     const void* grad, const PathsObjInfo* info);
 // omb_paths_min: check_paths_eval's refusals in its order, without a pitch and with res in out's place — and res may
 // not be null even at N = 0 (the empty batch still writes {+inf, −1} for every path): OMB_EINVAL for n_obj outside
 // [1, OMB_MAX_OBJ], N < 0, a null res or (N > 0) a null Xc; then OMB_ESTATE and OMB_EUNSUP as there.
@@ -112,6 +115,12 @@ int check_plan_mes(std::string* err, int k, int S, const double* ystar);
 // (8 bytes; the box list 4) or ld < N; OMB_EUNSUP for C < 2, k·C > kMaxLdsDoubles or box_off[S] > kMaxBoxesK.
 int check_hvi_paths(std::string* err, int k, int S, const void* y, int64_t ld, int64_t N, const void* coords, int C,
                     const int32_t* box_off, const void* boxes, const void* out);
+// omb_hvi_paths_grad: check_hvi_paths' OMB_EINVAL refusals in its order; then OMB_EINVAL for d outside
+// [1, kPathsMaxDim], (N > 0) a null dy / grad, exactly one of t / tgrad null, or one of the four off its 8-byte
+// alignment; then check_hvi_paths' OMB_EUNSUP refusals.
+int check_hvi_paths_grad(std::string* err, int k, int S, int d, const void* y, const void* dy, int64_t ld, int64_t N,
+                         const void* coords, int C, const int32_t* box_off, const void* boxes, const void* out,
+                         const void* grad, const void* t, const void* tgrad);
 // check_box_list over every list of a host (box_off[S], 2k) list whose offsets passed check_hvi_paths.
 int check_box_lists(std::string* err, int k, int S, int C, const int32_t* box_off, const uint16_t* boxes);
 // Candidates per pass of the fused chain under an omb_plan_hvi_paths plan (the default of OMB_DEBUG_HVI_PATHS_CHUNK):

@@ -251,4 +251,164 @@ hipError_t launch_hvi_paths(hipStream_t stream, int k, int S, const double* y, i
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------
+// omb_hvi_paths_grad: omb_hvi_paths' value and its gradient through the paths.  Two launches, no atomics:
+//   1. hvi_paths_dy_kernel, one workgroup row per path (blockIdx.y) and one lane per candidate, walks list s as
+//      hvi_paths_kernel does and leaves t_s (its operations, so bitwise its value) and
+//          ∂t_s/∂y_j = −Σ_b 1[lo_bj < y_j < hi_bj] Π_{l≠j} (hi_bl − max(y_l, lo_bl))⁺
+//      in a workspace, (S, K + 1, N): the slices of kHviSlice boxes from the list's own start are summed from 0 in list
+//      order and added in slice order, as the value's are.  The inequalities are strict: a value on a grid coordinate
+//      takes derivative 0 for that factor (the kink convention), and y_j ≥ r_j, above every hi_bj, zeroes everything.
+//   2. hvi_paths_chain_kernel, one lane per (candidate, dimension): ∂t_s/∂x = Σ_j ∂t_s/∂y_j·dy[(j·S + s)·d + ·], j
+//      ascending, added over the paths in path order from 0 and divided by S; the lanes of dimension 0 add the t_s the
+//      same way into out.  A NaN t_s makes its own ∂t_s/∂x NaN, a NaN value every entry of the candidate's gradient.
+// Every lane's work depends on its candidate alone: bitwise independent of N, the column and the launch shape.
+template <int K>
+__device__ __forceinline__ void hvi_slice_grad(const double (&y)[K], const double* grid, int C,
+                                               const uint32_t* __restrict__ boxes, int b0, int b1, double& p_out,
+                                               double (&dp)[K]) {
+#pragma clang fp contract(off)
+  double p = 0.0;
+#pragma unroll
+  for (int j = 0; j < K; ++j) dp[j] = 0.0;
+  for (int b = b0; b < b1; ++b) {
+    double t[K];
+    bool in[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const uint32_t w = boxes[(size_t)b * K + j];   // lo | hi << 16, wave-uniform
+      const int il = min((int)(w & 0xffffu), C - 1), ih = min((int)(w >> 16), C - 1);
+      const double lo = grid[j * C + il], hi = grid[j * C + ih];
+      t[j] = fmax(hi - fmax(y[j], lo), 0.0);
+      in[j] = lo < y[j] && y[j] < hi;
+    }
+    if constexpr (K == 1) {
+      p = p + t[0];
+      dp[0] = dp[0] - (in[0] ? 1.0 : 0.0);
+    } else {
+      double prod = t[0];
+#pragma unroll
+      for (int j = 1; j < K - 1; ++j) prod *= t[j];
+      p = fma(prod, t[K - 1], p);
+      // Π_{l≠j} t_l = (t_0 ⋯ t_{j−1})·(t_{j+1} ⋯ t_{K−1}), both in ascending order
+      double suf[K];
+      suf[K - 1] = 1.0;
+#pragma unroll
+      for (int j = K - 2; j >= 0; --j) suf[j] = t[j + 1] * suf[j + 1];
+      double pre = 1.0;
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        dp[j] = dp[j] - (in[j] ? pre * suf[j] : 0.0);
+        pre *= t[j];
+      }
+    }
+  }
+  p_out = p;
+}
+
+// ws[(s·(K + 1) + 0)·N + i] = t_s, ws[(s·(K + 1) + 1 + j)·N + i] = ∂t_s/∂y_j; grid (candidate blocks, S)
+template <int K>
+__global__ __launch_bounds__(kHviThreads) void hvi_paths_dy_kernel(const double* __restrict__ y, int64_t ld, int64_t N,
+                                                                   int S, const double* __restrict__ coords, int C,
+                                                                   const uint32_t* __restrict__ boxes, HviPathOff po,
+                                                                   double* __restrict__ ws) {
+#pragma clang fp contract(off)
+  extern __shared__ double hvi_paths_grid[];
+  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+  const int s = blockIdx.y;
+  const double* g = coords + (size_t)s * K * C;
+  for (int t = threadIdx.x; t < K * C; t += kHviThreads) hvi_paths_grid[t] = g[t];
+  __syncthreads();
+  const int B = po.off[s + 1] - po.off[s];
+  const uint32_t* bl = boxes + (size_t)po.off[s] * K;
+  const int slices = (B + kHviSlice - 1) / kHviSlice;
+  for (int64_t i = (int64_t)blockIdx.x * kHviThreads + threadIdx.x; i < N; i += (int64_t)gridDim.x * kHviThreads) {
+    double yv[K];
+    bool nan = false;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      yv[j] = y[((int64_t)j * S + s) * ld + i];
+      nan |= yv[j] != yv[j];
+    }
+    double ts = 0.0, dts[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) dts[j] = 0.0;
+    for (int c = 0; c < slices; ++c) {
+      double p, dp[K];
+      hvi_slice_grad<K>(yv, hvi_paths_grid, C, bl, c * kHviSlice, min(B, (c + 1) * kHviSlice), p, dp);
+      ts += nan ? qnan : p;
+#pragma unroll
+      for (int j = 0; j < K; ++j) dts[j] += dp[j];
+    }
+    double* w = ws + (int64_t)s * (K + 1) * N + i;
+    w[0] = ts;
+#pragma unroll
+    for (int j = 0; j < K; ++j) w[(int64_t)(1 + j) * N] = dts[j];
+  }
+}
+
+// grid (candidate blocks, d): lane (i, jx) chains and averages; t / tgrad (S, ld) / (S, d, ld) or both null
+__global__ __launch_bounds__(kHviThreads) void hvi_paths_chain_kernel(const double* __restrict__ ws, int K, int S,
+                                                                      int d, const double* __restrict__ dy,
+                                                                      int64_t ld, int64_t N, double* __restrict__ out,
+                                                                      double* __restrict__ grad,
+                                                                      double* __restrict__ t_out,
+                                                                      double* __restrict__ tgrad) {
+#pragma clang fp contract(off)
+  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+  const int jx = blockIdx.y;
+  for (int64_t i = (int64_t)blockIdx.x * kHviThreads + threadIdx.x; i < N; i += (int64_t)gridDim.x * kHviThreads) {
+    double total = 0.0, gtotal = 0.0;
+    for (int s = 0; s < S; ++s) {
+      const double* w = ws + (int64_t)s * (K + 1) * N + i;
+      const double ts = w[0];
+      double tg = 0.0;
+      for (int j = 0; j < K; ++j) tg += w[(int64_t)(1 + j) * N] * dy[(((int64_t)j * S + s) * d + jx) * ld + i];
+      if (ts != ts) tg = qnan;
+      total += ts;
+      gtotal += tg;
+      if (t_out) {
+        if (jx == 0) t_out[(int64_t)s * ld + i] = ts;
+        tgrad[((int64_t)s * d + jx) * ld + i] = tg;
+      }
+    }
+    const double v = total / (double)S;
+    if (jx == 0) out[i] = v;
+    grad[(int64_t)jx * ld + i] = (v != v) ? qnan : gtotal / (double)S;
+  }
+}
+
+int64_t hvi_paths_grad_ws_doubles(int64_t N, int k, int S) { return N < 1 ? 0 : (int64_t)S * (k + 1) * N; }
+
+hipError_t launch_hvi_paths_grad(hipStream_t stream, int k, int S, int d, const double* y, const double* dy,
+                                 int64_t ld, int64_t N, const double* coords, int C, const uint16_t* boxes,
+                                 const int32_t* box_off, double* out, double* grad, double* t_out, double* tgrad,
+                                 double* ws) {
+  if (N < 1 || S < 1 || S > kPathsMaxS || d < 1 || d > kPathsMaxDim || C < 2 || (int64_t)k * C > kMaxLdsDoubles ||
+      (reinterpret_cast<uintptr_t>(boxes) & 3) || !ws || (t_out == nullptr) != (tgrad == nullptr))
+    return hipErrorInvalidValue;
+  HviPathOff po;
+  for (int s = 0; s <= kPathsMaxS; ++s) po.off[s] = box_off[s < S ? s : S];
+  const size_t shm = sizeof(double) * (size_t)k * C;
+  const int64_t nb = (N + kHviThreads - 1) / kHviThreads;
+  const unsigned gx = (unsigned)(nb > (1 << 20) ? (1 << 20) : nb);
+  const dim3 b(kHviThreads);
+  const uint32_t* bw = reinterpret_cast<const uint32_t*>(boxes);
+  switch (k) {
+#define OMB_HVIP(KV)                                                                                              \
+  case KV:                                                                                                        \
+    hipLaunchKernelGGL((hvi_paths_dy_kernel<KV>), dim3(gx, (unsigned)S), b, shm, stream, y, ld, N, S, coords, C, bw, \
+                       po, ws);                                                                                   \
+    break;
+    OMB_HVIP(1) OMB_HVIP(2) OMB_HVIP(3) OMB_HVIP(4) OMB_HVIP(5) OMB_HVIP(6) OMB_HVIP(7) OMB_HVIP(8)
+#undef OMB_HVIP
+    default: return hipErrorInvalidValue;
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(hvi_paths_chain_kernel, dim3(gx, (unsigned)d), b, 0, stream, ws, k, S, d, dy, ld, N, out, grad,
+                     t_out, tgrad);
+  return hipGetLastError();
+}
+
 }  // namespace omb

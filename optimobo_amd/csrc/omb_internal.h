@@ -120,6 +120,14 @@ int64_t hvi_paths_ws_doubles(int64_t N, int S);
 hipError_t launch_hvi_paths(hipStream_t stream, int k, int S, const double* y, int64_t ld, int64_t N,
                             const double* coords, int C, const uint16_t* boxes, const int32_t* box_off, double* out,
                             double* ws);
+// launch_hvi_paths' out (bitwise) with grad[j·ld + i] = ∂out_i/∂x_j through dy, omb_paths_grad's gradient of the
+// rows of y at the same pitch ((k·S, d, ld)); t_out (S, ld) / tgrad (S, d, ld): the per-path t_s and ∂t_s/∂x, both
+// null or both set.  ws: hvi_paths_grad_ws_doubles(N, k, S) device doubles (the per-path t_s and ∂t_s/∂y).
+int64_t hvi_paths_grad_ws_doubles(int64_t N, int k, int S);
+hipError_t launch_hvi_paths_grad(hipStream_t stream, int k, int S, int d, const double* y, const double* dy,
+                                 int64_t ld, int64_t N, const double* coords, int C, const uint16_t* boxes,
+                                 const int32_t* box_off, double* out, double* grad, double* t_out, double* tgrad,
+                                 double* ws);
 
 hipError_t launch_hvpoi(hipStream_t stream, const double* mu, const double* var, int64_t ld, int64_t N,
                         const double* cells, int C, double* out);
@@ -401,6 +409,9 @@ struct PathArgs {
 // in place of the kernel's own (OMB_DEBUG_PATHS_LIBCOS, the baseline it is measured against)
 hipError_t launch_paths_eval(hipStream_t stream, const PathArgs& pa, int n_obj, int kind, bool libcos,
                              const double* Xc, int64_t N, int64_t ld, double* out);
+// launch_paths_eval's out (bitwise) and grad[((o·S + s)·d + j)·ld + i] = ∂(path s of objective o)/∂x_j at Xc_i
+hipError_t launch_paths_grad(hipStream_t stream, const PathArgs& pa, int n_obj, int kind, bool libcos,
+                             const double* Xc, int64_t N, int64_t ld, double* out, double* grad);
 // res[(o·S + s)·2 + {0, 1}] = {min_i of path s of objective o over Xc (N ≥ 0), the lowest such i + offset}; {+inf, −1}
 // where no value is comparable.  partials: paths_min_blocks(N)·n_obj·16·2 doubles (the workgroups' pairs of the first
 // launch; a second launch reduces them in a fixed order).

@@ -739,6 +739,60 @@ class AcqContext:
         self._check(self.lib.omb_paths_eval(self._h, int(n_obj), _ptr(Xc), N, int(ld), _ptr(out)), "omb_paths_eval")
         return out
 
+    def paths_grad(self, Xc, n_obj=None, ld=None):
+        """The installed paths of objectives 0..n_obj-1 and their gradients at candidates Xc (N, d) (omb_paths_grad):
+        (vals (n_obj, S, N), bitwise ``paths_eval``'s; grad (n_obj, S, d, N), grad[o, s, j, i] = ∂f_{o,s}/∂x_j at
+        Xc[i]).  ``ld`` ≥ N pitches the rows of both (views of the first N columns are returned)."""
+        Xc = _dev_f64(Xc, self.device)
+        self._check_width(Xc)
+        n_obj = n_obj if n_obj is not None else len(self.gp_info)
+        N, d = Xc.shape
+        ld = N if ld is None else int(ld)
+        if ld < N:
+            raise ValueError(f"paths_grad: ld={ld} < N={N}")
+        S = self._paths_S.get(0, 1)
+        vals = torch.empty((n_obj, S, ld), dtype=torch.float64, device=self.device)
+        grad = torch.empty((n_obj, S, d, ld), dtype=torch.float64, device=self.device)
+        self._stream()
+        self._check(self.lib.omb_paths_grad(self._h, int(n_obj), _ptr(Xc), N, ld, _ptr(vals), _ptr(grad)),
+                    "omb_paths_grad")
+        return vals[:, :, :N], grad[:, :, :, :N]
+
+    def hvi_paths_grad(self, y, dy, coords, box_off, boxes, per_path=False):
+        """omb_hvi_paths_grad: ``hvi_paths``' value and its gradient through the paths — y (k, S, N) and dy
+        (k, S, d, N) as ``paths_grad`` returns them (the same pitch) → (v (N,), g (N, d)); with ``per_path`` also
+        (t (S, N), tg (S, N, d)), the per-path improvement t_s and ∂t_s/∂x.  The (N, d) results are transposed views
+        of the device layout."""
+        c, o, b = self._box_lists_host(coords, box_off, boxes, "hvi_paths_grad")
+        S, k, C = c.shape
+        if not isinstance(y, torch.Tensor) or y.dtype != torch.float64 or y.device != self.device or y.dim() != 3 \
+                or tuple(y.shape[:2]) != (k, S) or (y.shape[2] > 1 and y.stride(2) != 1) \
+                or y.stride(0) != S * y.stride(1) or y.stride(1) < y.shape[2]:
+            raise ValueError(f"hvi_paths_grad: y must be a ({k}, {S}, N) fp64 tensor on {self.device} with unit "
+                             "column stride and evenly pitched rows")
+        N, ld = y.shape[2], y.stride(1)
+        if not isinstance(dy, torch.Tensor) or dy.dtype != torch.float64 or dy.device != self.device \
+                or dy.dim() != 4 or tuple(dy.shape[:2]) != (k, S) or dy.shape[3] != N or dy.shape[2] < 1 \
+                or (N > 1 and dy.stride(3) != 1) or dy.stride(2) != ld or dy.stride(1) != dy.shape[2] * ld \
+                or dy.stride(0) != S * dy.stride(1):
+            raise ValueError(f"hvi_paths_grad: dy must be a ({k}, {S}, d, {N}) fp64 tensor on {self.device} at y's "
+                             f"pitch {ld}")
+        d = dy.shape[2]
+        out = torch.empty(N, dtype=torch.float64, device=self.device)
+        grad = torch.empty((d, ld), dtype=torch.float64, device=self.device)
+        t = torch.empty((S, ld), dtype=torch.float64, device=self.device) if per_path else None
+        tg = torch.empty((S, d, ld), dtype=torch.float64, device=self.device) if per_path else None
+        cd = torch.as_tensor(c, device=self.device)
+        bd = self._boxes_dev(b)
+        self._stream()
+        self._check(self.lib.omb_hvi_paths_grad(self._h, k, S, d, _ptr(y), _ptr(dy), ld, N, _ptr(cd), C,
+                                                _lib.host_ptr(o), _ptr(bd), _ptr(out), _ptr(grad),
+                                                _ptr(t) if per_path else None, _ptr(tg) if per_path else None),
+                    "omb_hvi_paths_grad")
+        if per_path:
+            return out, grad[:, :N].T, t[:, :N], tg[:, :, :N].permute(0, 2, 1)
+        return out, grad[:, :N].T
+
     def paths_min(self, Xc, n_obj=None, offset=0):
         """The minimum of every installed path of objectives 0..n_obj-1 over candidates Xc (N, d) (omb_paths_min):
         (values (n_obj, S) fp64, indices (n_obj, S) int64 = the lowest arg-min + offset), bitwise
