@@ -292,6 +292,30 @@ int omb_hvi_paths_grad(omb_ctx* ctx, int k, int S, int d, const double* y_dev, c
                        int64_t N, const double* coords_dev, int C, const int32_t* box_off_host,
                        const uint16_t* boxes_dev, double* out_dev, double* grad_dev, double* t_dev,
                        double* tgrad_dev);
+/* omb_hvi_paths under constraints through sample paths (everything minimised, g ≤ 0 feasible).  y_dev is
+ * omb_paths_eval's output over k + n_con slots: the objectives are slots 0..k−1, the constraint models slots
+ * k..k+n_con−1, path s of slot o at row o·S + s, pitch ld.  Per path s and candidate i:
+ *   ω(g)  = 1[g ≤ 0]                                                            eta = 0
+ *         = 1/(1 + e^{g/η}) for g ≤ 0,  e^{−g/η}/(1 + e^{−g/η}) for g > 0         eta > 0 (a smoothed indicator)
+ *   w_s   = ((1·ω(g_{0,s,i}))·ω(g_{1,s,i}))·…   in constraint order
+ *   u_s   = t_s·w_s (one multiplication, unfused), exactly 0.0 where w_s == 0.0;  t_s bitwise omb_hvi_paths' t_s
+ *   out_dev[i] = ((…((0 + u_0) + u_1) + …) + u_{S−1}) / S
+ * flags = OMB_CON_VIOLATION (eta = 0 only): where w_s == 0, u_s = −((0 + max(g_0, 0)) + max(g_1, 0) + …) < 0, so a
+ * feasible candidate (u_s ≥ 0) ranks above every infeasible one and the least total violation leads the infeasible
+ * ones.  A NaN among the k + n_con values of path s makes u_s, and so out_dev[i], NaN; no other candidate is
+ * affected.  At n_con = 0 out_dev is bitwise omb_hvi_paths'.  u_dev (S, ld), when not NULL, takes every u_s (row s,
+ * pitch ld); out_dev (N) may then be NULL.  One lane per candidate as omb_hvi_paths; a wavefront whose candidates all
+ * have w_s == 0 walks no box of list s, which changes no bit; no atomics; a candidate's values are bitwise the same
+ * whatever N, its column or the launch shape.  Asynchronous.
+ *   omb_hvi_paths' refusals, in its order (a NULL out_dev is not one of them here); then
+ *   OMB_EINVAL  n_con < 0, eta negative or not finite, flag bits other than OMB_CON_VIOLATION, that flag with eta > 0,
+ *               out_dev and u_dev both NULL with N > 0, u_dev off its 8-byte alignment
+ *   OMB_EUNSUP  k + n_con > OMB_MAX_OBJ
+ * N = 0 returns OMB_OK and writes nothing. */
+#define OMB_CON_VIOLATION 1u
+int omb_hvi_paths_con(omb_ctx* ctx, int k, int S, int n_con, const double* y_dev, int64_t ld, int64_t N,
+                      const double* coords_dev, int C, const int32_t* box_off_host, const uint16_t* boxes_dev,
+                      double eta, unsigned flags, double* out_dev, double* u_dev);
 
 /* Hypervolume-based PoI of EMO (emo.py:176-228): cells_dev (C, 2, 2) [upper, lower]. */
 int omb_hvpoi(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
@@ -435,6 +459,15 @@ int omb_plan_mes(omb_ctx* ctx, int k, int S, const double* ystar_host);
  * leaves it as it was. */
 int omb_plan_hvi_paths(omb_ctx* ctx, int k, int S, const double* coords_host, int C, const int32_t* box_off_host,
                        const uint16_t* boxes_host);
+/* omb_hvi_paths_con (no flag) as a plan of the fused chain: omb_plan_hvi_paths' arguments and checks, then
+ * omb_hvi_paths_con's for n_con and eta.  The chain runs [Sobol →] omb_paths_eval(0..k+n_con−1) →
+ * omb_hvi_paths_con → [arg-max] in passes of OMB_HVI_PATHS_CHUNK candidates (OMB_DEBUG_HVI_PATHS_CHUNK applies); the
+ * workspace holds ((k + n_con)·S, chunk) path values; values are bitwise omb_paths_eval → omb_hvi_paths_con,
+ * whatever the chunk.  The OMB_ESTATE rule of omb_plan_hvi_paths covers all k + n_con slots.  The plan carries its
+ * own constraints: omb_plan_constraints with n_con > 0, omb_plan_log and omb_eval_grad return OMB_EUNSUP on it, as on
+ * omb_plan_hvi_paths. */
+int omb_plan_hvi_paths_con(omb_ctx* ctx, int k, int S, int n_con, double eta, const double* coords_host, int C,
+                           const int32_t* box_off_host, const uint16_t* boxes_host);
 
 /* Inequality constraints on the plan that is set (g ≤ 0 feasible).  From here on omb_eval, omb_eval_argmax,
  * omb_eval_argmax_sobol and omb_eval_grad also compute the posterior (μ and σ²) of context slots k..k+n_con−1 — the

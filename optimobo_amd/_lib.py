@@ -35,6 +35,7 @@ DEBUG_POSTERIOR_MEAN_KERNEL = 13
 DEBUG_PATHS_LIBCOS = 14
 DEBUG_HVI_PATHS_CHUNK = 15
 MAX_OBJ, MAX_DIM, MAX_TRAIN, MAX_TRAIN_DENSE = 8, 256, 1024, 16384
+CON_VIOLATION = 1              # OMB_CON_VIOLATION: omb_hvi_paths_con's flag (infeasible paths score −violation)
 HVI_PATHS_CHUNK = 1 << 18      # OMB_HVI_PATHS_CHUNK: candidates per pass of the chain under plan_hvi_paths
 
 _p = ctypes.c_void_p
@@ -64,6 +65,7 @@ SIGNATURES = {
     "omb_hvi_boxes": (_i, [_p, _i, _p, _i64, _i64, _p, _i, _p, _i, _p]),
     "omb_hvi_paths": (_i, [_p, _i, _i, _p, _i64, _i64, _p, _i, _p, _p, _p]),
     "omb_hvi_paths_grad": (_i, [_p, _i, _i, _i, _p, _p, _i64, _i64, _p, _i, _p, _p, _p, _p, _p, _p]),
+    "omb_hvi_paths_con": (_i, [_p, _i, _i, _i, _p, _i64, _i64, _p, _i, _p, _p, _d, ctypes.c_uint, _p, _p]),
     "omb_hvpoi": (_i, [_p, _p, _p, _i64, _i64, _p, _i, _p]),
     "omb_expdec": (_i, [_p, _i, _p, _p, _i64, _i64, _p, _i, _i, _dp, _dp, _dp, _dp, _d, _p]),
     "omb_ei": (_i, [_p, _p, _p, _i64, _d, _d, _p]),
@@ -89,6 +91,7 @@ SIGNATURES = {
     "omb_plan_ei_ext": (_i, [_p, _i, _i, _d, _d, _d]),
     "omb_plan_mes": (_i, [_p, _i, _i, _p]),
     "omb_plan_hvi_paths": (_i, [_p, _i, _i, _p, _i, _p, _p]),
+    "omb_plan_hvi_paths_con": (_i, [_p, _i, _i, _i, _d, _p, _i, _p, _p]),
     "omb_plan_constraints": (_i, [_p, _i, _d]),
     "omb_plan_log": (_i, [_p, _i]),
     "omb_set_sobol": (_i, [_p, _i, _i, _p, _p, _dp, _dp]),

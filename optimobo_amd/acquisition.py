@@ -42,6 +42,7 @@ class AcquisitionEngine:
         self.ystar = None           # sample_minima's last result (n_obj, S)
         self.ystar_X = None         # and its minimisers (n_obj, S, d)
         self._front_lists = None    # sample_fronts' packed box lists (coords, box_off, boxes)
+        self._front_con = 0         # sample_fronts' n_con: the last models are constraints read through their paths
         self._cond_X = []           # rows ``condition`` appended to every resident state since the last upload
         self.n_obj = 0
 
@@ -267,7 +268,7 @@ class AcquisitionEngine:
         """``mes`` as the fused chain's plan (None: the last ``sample_minima`` result); ``has_gradient`` is True."""
         self.ctx.plan_mes(self._ystar(ystar, "plan_mes"))
 
-    def sample_fronts(self, S, max_point, lower, upper, seed=0, n_features=1024, max_boxes=1 << 20):
+    def sample_fronts(self, S, max_point, lower, upper, seed=0, n_features=1024, max_boxes=1 << 20, n_con=0):
         """S fresh posterior sample paths of every loaded model, evaluated at the training inputs: S draws of the latent
         objective values there and so S fronts, the integration set of the noisy EHVI (one model: S best values, the
         noisy EI's).  The paths are latent — no observation noise is added at X.
@@ -279,14 +280,22 @@ class AcquisitionEngine:
         ``pareto.threshold_lists`` of the paths' minima over the training inputs (``AcqContext.paths_min``).  The
         packed lists (``pareto.pack_box_lists``) are kept on the engine for ``nehvi`` / ``plan_nehvi``, which hold
         while the paths do: until a model is loaded or conditioned.  Returns the list of fronts (S arrays (P_s, k)),
-        or b (S,) for one model."""
-        S = int(S)
+        or b (S,) for one model.
+
+        With ``n_con`` > 0 the last n_con loaded models are constraint models (g ≤ 0 feasible) and "one model" above
+        reads "one objective": every path keeps the rows at which all its constraint paths are ≤ 0
+        (``pareto.feasible_fronts`` on ``path_values``), so each draw has its own feasible front, and ``nehvi`` /
+        ``plan_nehvi`` weight every candidate's path by its feasibility under the same draw."""
+        S, n_con = int(S), int(n_con)
         if not 1 <= S <= 16:
             raise ValueError(f"sample_fronts: S={S} outside [1, 16] (one path install)")
-        k = self.n_obj
-        if k < 1:
+        if self.n_obj < 1:
             raise RuntimeError("sample_fronts: no models loaded (call load_models first)")
-        if any(not np.array_equal(self._resident[o].X, self._resident[0].X) for o in range(1, k)):
+        if not 0 <= n_con < self.n_obj:
+            raise ValueError(f"sample_fronts: n_con={n_con} outside [0, {self.n_obj - 1}] (the loaded models less one "
+                             "objective)")
+        k = self.n_obj - n_con
+        if any(not np.array_equal(self._resident[o].X, self._resident[0].X) for o in range(1, self.n_obj)):
             raise ValueError("sample_fronts: the loaded models do not share their training inputs (a front needs every "
                              "objective at the same rows)")
         if (k == 1) != (max_point is None):
@@ -296,7 +305,10 @@ class AcquisitionEngine:
         self.sample_paths(S, n_features=n_features, seed=seed, lower=lower, upper=upper)
         # the rows the device states hold: the fitted ones and, inside a believer batch, the fantasies behind them
         Xt = self._dev(np.vstack([self._resident[0].X] + self._cond_X))
-        if k == 1:
+        if n_con:
+            F = self.path_values(Xt).cpu().numpy()                  # (k + n_con, S, n)
+            out, decomps = pareto.feasible_fronts(F[:k], F[k:], max_point, max_boxes=max_boxes)
+        elif k == 1:
             out = self.ctx.paths_min(Xt, 1)[0][0].cpu().numpy()
             decomps = pareto.threshold_lists(out)
         else:
@@ -304,6 +316,7 @@ class AcquisitionEngine:
             out = [pareto.calc_pf(np.ascontiguousarray(F[:, s, :].T)) for s in range(S)]
             decomps = [pareto.box_decomposition(pf, max_point, max_boxes=max_boxes) for pf in out]
         self._front_lists = pareto.pack_box_lists(decomps)
+        self._front_con = n_con
         return out
 
     def _fronts(self, what):
@@ -312,28 +325,44 @@ class AcquisitionEngine:
             raise RuntimeError(f"{what}: no sampled fronts (call sample_fronts first)")
         return lists
 
-    def nehvi(self, Xc):
+    def nehvi(self, Xc, eta=0.0):
         """Noisy EHVI (one model: noisy EI) on every row of Xc: the mean over the fronts of the last ``sample_fronts``
-        of the hypervolume improvement of each path's value at the candidate (``path_values`` → ``hvi_paths``)."""
+        of the hypervolume improvement of each path's value at the candidate (``path_values`` → ``hvi_paths``).
+        After ``sample_fronts(n_con > 0)`` every path's improvement is weighted by the candidate's feasibility under
+        the same draw (``hvi_paths_con``): the indicator at ``eta`` = 0, the sigmoid of −g/eta above."""
         lists = self._fronts("nehvi")
-        return self.ctx.hvi_paths(self.path_values(Xc)[:lists[0].shape[1]], *lists)
+        k, c = lists[0].shape[1], self._front_con
+        if c:
+            return self.ctx.hvi_paths_con(self.path_values(Xc)[:k + c], c, *lists, eta=eta)
+        if eta:
+            raise ValueError("nehvi: eta smooths the constraints' indicator; the sampled fronts have no constraints")
+        return self.ctx.hvi_paths(self.path_values(Xc)[:k], *lists)
 
     def nehvi_value_and_grad(self, X):
         """``nehvi`` and its gradient at host points X (m, d) → numpy (v (m,), g (m, d)), over the fronts of the last
         ``sample_fronts``: ``path_values_and_grad`` → ``hvi_paths_grad``.  v is bitwise ``nehvi``'s value."""
         lists = self._fronts("nehvi_value_and_grad")
+        if self._front_con:
+            raise ValueError("nehvi_value_and_grad: no gradient through the constraints' feasibility weight "
+                             "(sample_fronts was called with n_con > 0)")
         k = lists[0].shape[1]
         y, dy = self.path_values_and_grad(X)
         v, g = self.ctx.hvi_paths_grad(y[:k], dy[:k], *lists)
         return v.cpu().numpy().astype(np.float64), g.cpu().numpy().astype(np.float64)
 
-    def plan_nehvi(self):
+    def plan_nehvi(self, eta=0.0):
         """``nehvi`` as the fused chain's plan; ``has_gradient`` is False, so ``polish="auto"`` takes the stencil."""
-        self.ctx.plan_hvi_paths(*self._fronts("plan_nehvi"))
+        lists = self._fronts("plan_nehvi")
+        if self._front_con:
+            self.ctx.plan_hvi_paths_con(self._front_con, *lists, eta=eta)
+        elif eta:
+            raise ValueError("plan_nehvi: eta smooths the constraints' indicator; the sampled fronts have no constraints")
+        else:
+            self.ctx.plan_hvi_paths(*lists)
 
     def thompson_batch(self, q, lower, upper, PF=None, max_point=None, n_candidates=None, seed=0,
                        max_boxes=1 << 20, sampler="joint", n_features=1024, refine_rounds=0, shrink=0.1,
-                       n_refine=4096, polish=False):
+                       n_refine=4096, polish=False, n_con=0, best=None):
         """A batch of q proposals by Thompson sampling over the loaded models → (X (q, d), info).
 
         The candidates are the first ``n_candidates`` points of the device Sobol' sequence seeded by ``seed``
@@ -367,12 +396,27 @@ class AcquisitionEngine:
         minimised; else draw b's HVI over the front is maximised (``hvi_paths_grad(per_path=True)`` over the front
         packed q times, entry (b, b)) — the runs advance in lockstep, the nominee moves only on strict improvement
         and never onto a point another nominee holds (runs that end in the same corner of the box), and ``info``
-        gains ``polished``, the number of nominees moved."""
+        gains ``polished``, the number of nominees moved.
+
+        With ``n_con`` > 0 the last n_con loaded models are constraint models (g ≤ 0 feasible), drawn like the
+        objectives (paths, or ``posterior_samples``), and "models" above reads "objectives".  Draw b nominates its best
+        candidate that is feasible under the same draw, else its least violating one: the score is
+        ``hvi_paths_con``'s per-path u with the violation score, over the front packed once per draw (one objective:
+        the threshold ``best``, the best feasible observation), in groups of at most 16 draws, and −u goes to
+        ``thompson_select``.  The refinement rounds use the same score and also move a draw with no feasible candidate
+        towards less violation; ``polish`` is refused.  ``values`` are the picks' u; ``zero_draws`` counts the draws
+        whose best u ≤ 0 and ``infeasible_draws`` those whose best u < 0 (no candidate feasible under the draw)."""
         lower = np.asarray(lower, np.float64).reshape(-1)
         upper = np.asarray(upper, np.float64).reshape(-1)
-        d, k, q = lower.size, self.n_obj, int(q)
-        if k < 1:
+        n_con = int(n_con)
+        if self.n_obj < 1:
             raise RuntimeError("thompson_batch: no models loaded (call load_models first)")
+        if not 0 <= n_con < self.n_obj:
+            raise ValueError(f"thompson_batch: n_con={n_con} outside [0, {self.n_obj - 1}] (the loaded models less one "
+                             "objective)")
+        if n_con and polish:
+            raise ValueError("thompson_batch: polish has no gradient through the constraints' feasibility (n_con > 0)")
+        d, k, q = lower.size, self.n_obj - n_con, int(q)
         if sampler not in ("joint", "paths"):
             raise ValueError(f"thompson_batch: sampler must be 'joint' or 'paths', not {sampler!r}")
         paths = sampler == "paths"
@@ -397,20 +441,34 @@ class AcquisitionEngine:
             geo = (coords, boxes)
         self.ctx.set_sobol(d, lower, upper, seed=seed)
         Xc = self.ctx.sobol(0, n_c)
+        if n_con and k == 1 and best is None:
+            raise ValueError("thompson_batch: one objective under constraints needs best, the threshold a feasible "
+                             "candidate must beat (the best feasible observation)")
         if paths:
             self.sample_paths(q, n_features=n_features, seed=seed, lower=lower, upper=upper)
-            draws = self.ctx.paths_eval(Xc, k)
-            jitter = [0.0] * k
+            draws = self.ctx.paths_eval(Xc, k + n_con)
+            jitter = [0.0] * (k + n_con)
         else:
             rng = np.random.default_rng(seed)
-            draws = torch.empty((k, q, n_c), dtype=torch.float64, device=self.device)
+            draws = torch.empty((k + n_con, q, n_c), dtype=torch.float64, device=self.device)
             jitter = []
-            for o in range(k):
+            for o in range(k + n_con):
                 Z = self._dev(rng.standard_normal((q, n_c)))
                 _, j = self.ctx.posterior_samples(o, Xc, Z, out=draws[o])
                 jitter.append(j)
         zero = 0
-        if k == 1:
+        if n_con:
+            one = pareto.threshold_lists([best]) if k == 1 else [(geo[0], None, geo[1])]
+
+            def con_score(y):       # y (k + n_con, g, N), g ≤ 16 draws → their own u (g, N)
+                return self.ctx.hvi_paths_con(y, n_con, *pareto.pack_box_lists(one * y.shape[1]), violation=True,
+                                              per_path=True)[1]
+            h = torch.cat([con_score(draws[:, b0:b0 + 16].contiguous()) for b0 in range(0, q, 16)])
+            idx = self.ctx.thompson_select(-h)
+            values = h[torch.arange(q, device=self.device), idx].cpu().numpy()
+            top = h.max(dim=1).values.cpu().numpy()
+            zero = int((top <= 0).sum())
+        elif k == 1:
             score = draws[0]
             idx = self.ctx.thompson_select(score)
             values = score[torch.arange(q, device=self.device), idx].cpu().numpy()
@@ -422,9 +480,14 @@ class AcquisitionEngine:
         idx = idx.cpu().numpy()
         X = Xc[torch.as_tensor(idx, device=self.device)].cpu().numpy()
         info = dict(indices=idx, values=values, jitter=jitter, zero_draws=zero, n_candidates=n_c)
+        if n_con:
+            info["infeasible_draws"] = int((top < 0).sum())
         if not paths:
             return X, info
-        live = np.ones(q, bool) if k == 1 else (h.max(dim=1).values > 0).cpu().numpy()
+        if n_con:
+            live = top != 0         # something to gain, or some violation to lose
+        else:
+            live = np.ones(q, bool) if k == 1 else (h.max(dim=1).values > 0).cpu().numpy()
         refined = []
         for rnd in range(1, int(refine_rounds) + 1):
             moved = 0
@@ -433,12 +496,15 @@ class AcquisitionEngine:
                 self.ctx.set_sobol(d, np.maximum(lower, X[b] - half), np.minimum(upper, X[b] + half),
                                    seed=seed + 104729 * rnd + int(b))
                 Xr = self.ctx.sobol(0, int(n_refine))
-                vals = self.ctx.paths_eval(Xr, k)[:, b, :]
-                # one model: the smallest drawn value; else the largest HVI under draw b
-                score = -vals[0].contiguous() if k == 1 else self.ctx.hvi_boxes(vals, *geo)
+                vals = self.ctx.paths_eval(Xr, k + n_con)[:, b, :]
+                # one model: the smallest drawn value; else the largest HVI under draw b; constraints: the largest u
+                if n_con:
+                    score = con_score(vals.contiguous().unsqueeze(1))[0].contiguous()
+                else:
+                    score = -vals[0].contiguous() if k == 1 else self.ctx.hvi_boxes(vals, *geo)
                 v, i = self.ctx.argmax(score)
-                v = -v if k == 1 else v
-                if i >= 0 and (v < values[b] if k == 1 else v > values[b]):
+                v = -v if k == 1 and not n_con else v
+                if i >= 0 and (v < values[b] if k == 1 and not n_con else v > values[b]):
                     X[b] = Xr[int(i)].cpu().numpy()
                     values[b] = v
                     moved += 1

@@ -31,6 +31,9 @@ class BODriver:
     thompson_features = 1024
     thompson_refine_rounds = 2
     path_gradients = False       # the keyword's default (an instance attribute only where it is True)
+    # constraints="paths": the width of the sigmoid that stands for the feasibility indicator in the noisy EHVI / EI
+    # (0.0: the indicator itself; a Thompson batch always takes the indicator)
+    paths_eta = 0.0
 
     def __init__(self, test_problem, ideal_point=None, max_point=None, mode="reference", n_candidates=1 << 14,
                  refine_rounds=2, seed=None, device=None, polish=True, starts=None, noise=0.0, batch_size=1,
@@ -69,7 +72,9 @@ class BODriver:
         self.batch_size = int(batch_size)
         # inequality constraints of the problem (not in the reference, whose optimisers.py:22 says "Constraints not
         # supported"): None ignores them, as the reference does; "pof" fits one GP per constraint and weights the
-        # acquisition by the probability of feasibility (g <= 0 feasible)
+        # acquisition by the probability of feasibility (g <= 0 feasible); "paths" fits the same GPs and reads them
+        # through posterior sample paths — under every draw a row or a candidate is feasible when all constraint
+        # paths are <= 0 there — which is what the sampled-front acquisitions and Thompson batches can use
         self.constraints = self._check_constraints_option(constraints)
         # how a batch is built (not in the reference): "believer" picks one point after another, conditioning the
         # surrogates on each pick's posterior mean; "thompson" takes q joint posterior draws over one candidate set
@@ -104,6 +109,17 @@ class BODriver:
         if path_gradients and self.acquisition is None and self.thompson_sampler != "paths":
             raise ValueError("path_gradients=True needs something drawn from sample paths: acquisition='mes', 'nehvi' "
                              "or 'nei', or thompson_sampler='paths'")
+        if self.constraints == "paths":
+            if self.acquisition not in ("nehvi", "nei") and self.batch_strategy != "thompson":
+                raise ValueError("constraints='paths' reads the constraint models through posterior sample paths: it "
+                                 "needs acquisition='nehvi' (MultiSurrogateOptimiser) or 'nei' (MonoSurrogateOptimiser), "
+                                 "or batch_strategy='thompson'; the other acquisitions take constraints='pof'")
+            if path_gradients:
+                raise ValueError("path_gradients=True does not support constraints='paths' (no gradient through the "
+                                 "paths' feasibility weight)")
+            if self.n_vars > 64:
+                raise ValueError(f"constraints='paths' samples posterior paths, which need n_var <= 64 "
+                                 f"(n_var={self.n_vars})")
         if path_gradients:      # False stays the class attribute: the instance is the one built without the keyword
             self.path_gradients = True
         self.thompson_fallbacks = 0   # Thompson iterations that fell back to the believer batch
@@ -195,13 +211,16 @@ class BODriver:
 
     def _plan_nehvi(self, eng, k):
         """The noisy-EHVI (k = 1: noisy-EI) plan of one pick on ``eng`` over its ``k`` models: ``nehvi_samples`` fresh
-        sample paths, their fronts at the training inputs, the plan.  ``eng.condition`` drops the paths, so a believer
+        sample paths, their fronts at the training inputs, the plan.  Under constraints="paths" the ``n_con`` models
+        behind them are sampled too: every path's front is its own feasible one and the plan weights every candidate's
+        path by its feasibility under the same draw (``paths_eta``).  ``eng.condition`` drops the paths, so a believer
         batch samples again for every pick, from the conditioned state.  ``pareto.BoxBudgetError`` (n_obj ≥ 4, a
         front past ``exact_max_boxes``) propagates."""
         eng.sample_fronts(self.nehvi_samples, self.max_point if k > 1 else None, self.test_problem.xl,
                           self.test_problem.xu, seed=self._path_seed(), n_features=self.nehvi_features,
-                          max_boxes=getattr(self, "exact_max_boxes", 1 << 20))
-        eng.plan_nehvi()
+                          max_boxes=getattr(self, "exact_max_boxes", 1 << 20),
+                          **({"n_con": self.n_con} if self.constraints == "paths" else {}))
+        eng.plan_nehvi(**({"eta": self.paths_eta} if self.constraints == "paths" else {}))
 
     def _plan_mes(self, eng, k):
         """The MES plan of one pick on ``eng`` over its first ``k`` models: fresh sample paths, their minima, the
@@ -215,30 +234,32 @@ class BODriver:
     def _check_constraints_option(self, constraints):
         if constraints is None:
             return None
-        if constraints != "pof":
-            raise ValueError(f"constraints must be None or 'pof', not {constraints!r}")
+        if not isinstance(constraints, str) or constraints not in ("pof", "paths"):
+            raise ValueError(f"constraints must be None or 'pof' (or 'paths', with the sampled-front acquisitions and "
+                             f"Thompson batches), not {constraints!r}")
         k = self._pof_objective_models
         if k is None:
-            raise ValueError(f"{type(self).__name__} does not support constraints='pof' (MultiSurrogateOptimiser and "
-                             "MonoSurrogateOptimiser do)")
+            raise ValueError(f"{type(self).__name__} does not support constraints={constraints!r} "
+                             "(MultiSurrogateOptimiser and MonoSurrogateOptimiser do)")
         k = self.n_obj if k == "n_obj" else int(k)
         n_ieq = int(getattr(self.test_problem, "n_ieq_constr", 0) or 0)
         if n_ieq == 0:
-            raise ValueError("constraints='pof' needs a problem with n_ieq_constr > 0")
+            raise ValueError(f"constraints={constraints!r} needs a problem with n_ieq_constr > 0")
         if int(getattr(self.test_problem, "n_eq_constr", 0) or 0) > 0:
-            raise ValueError("constraints='pof' does not handle equality constraints (n_eq_constr > 0)")
+            raise ValueError(f"constraints={constraints!r} does not handle equality constraints (n_eq_constr > 0)")
         if k + n_ieq > 8:
-            raise ValueError(f"constraints='pof': {k} objective model(s) + {n_ieq} constraints exceed the device "
-                             "context's 8 models")
+            raise ValueError(f"constraints={constraints!r}: {k} objective model(s) + {n_ieq} constraints exceed the "
+                             "device context's 8 models")
         self.n_con = n_ieq
-        return "pof"
+        return constraints
 
     # -- constraints="pof"
     def _constraint_values(self, X):
         """G (len(X), n_ieq_constr) of the rows of X through ``problem.evaluate_constraints``.  Without
-        constraints="pof" nothing is evaluated and G has no columns, so that ``_feasible`` passes every row."""
+        constraints="pof" / "paths" nothing is evaluated and G has no columns, so that ``_feasible`` passes every
+        row."""
         X = np.atleast_2d(X)
-        if self.constraints != "pof":
+        if self.constraints is None:
             return np.empty((len(X), 0))
         return np.asarray([np.atleast_1d(self.test_problem.evaluate_constraints(x, return_values_of=["G"])) for x in X],
                           dtype=np.float64).reshape(len(X), -1)
@@ -314,10 +335,16 @@ class BODriver:
         """The search of a ``_get_proposed*`` hook once its plan is set.  Under constraints="pof" the plan is first
         weighted by the probability of feasibility of the ``n_con`` models behind it (AcquisitionEngine
         .plan_constraints, after the plan and its ``plan_log``: a log plan keeps its flag, log F is added).
-        ``eng`` None — an iteration's first pick — is the reference loop's two-argument ``_maximise`` call."""
-        if self.constraints == "pof":
+        ``eng`` None — an iteration's first pick — is the reference loop's two-argument ``_maximise`` call.
+        constraints="paths": the sampled-front plan carries its constraints itself; a Thompson iteration that fell
+        back to the believer batch plans the driver's own acquisition and is weighted as under "pof"."""
+        if self.constraints == "pof" or (self.constraints == "paths" and not self._paths_plan()):
             (engine_for(models, self.device) if eng is None else eng).plan_constraints(self.n_con, self.pof_eps)
         return self._maximise(models, None) if eng is None else self._maximise(models, None, eng=eng)
+
+    def _paths_plan(self):
+        """constraints="paths" with the sampled-front acquisition, whose plan reads the constraint paths itself."""
+        return self.constraints == "paths" and self.acquisition in ("nehvi", "nei")
 
     def _maximise_feasibility(self, models, eng):
         """constraints="pof" while no row is feasible: the point most likely to be feasible (by log F with
@@ -325,17 +352,22 @@ class BODriver:
         pof = eng.log_feasibility if self.log_acquisition else eng.feasibility
         return self._maximise(models, lambda Xd: pof(Xd, self.n_con, self.pof_eps), eng=eng)[0]
 
-    def _thompson_picks(self, eng, b, PF=None):
+    def _thompson_picks(self, eng, b, PF=None, best=None):
         """``b`` proposals of one iteration by AcquisitionEngine.thompson_batch on ``eng`` as it stands (seeded as
         ``_maximise`` seeds a search, so every rank computes the same batch), or None when that iteration has to
         fall back to the believer batch: the draws' covariance could not be factorised within the jitter ladder
         (OMB_ENOTPD — near-singular fits can exhaust it) or the front needs more boxes than the budget
         (pareto.BoxBudgetError).  A fallback warns and is counted in ``thompson_fallbacks``; any other error of the
-        call — a batch larger than the candidate set, say — is the caller's and is raised."""
+        call — a batch larger than the candidate set, say — is the caller's and is raised.  Under
+        constraints="paths" the ``n_con`` models behind the objectives are drawn too and every draw nominates its best
+        feasible candidate, else its least violating one; ``PF`` is then the feasible front and ``best`` (one
+        surrogate) the best feasible value."""
         seed = self._search_seed()
         kw = {}
+        if self.constraints == "paths":
+            kw = dict(n_con=self.n_con, best=best)
         if self.thompson_sampler == "paths":
-            kw = dict(sampler="paths", n_features=self.thompson_features, refine_rounds=self.thompson_refine_rounds)
+            kw.update(sampler="paths", n_features=self.thompson_features, refine_rounds=self.thompson_refine_rounds)
             if self.path_gradients:
                 kw["polish"] = True
         try:

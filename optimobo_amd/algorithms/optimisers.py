@@ -132,6 +132,7 @@ class MultiSurrogateOptimiser(BODriver):
                              "acquisitions (acquisition_func=None), not a scalarised expected decomposition")
         problem = self.test_problem
         pof, k = self.constraints == "pof", problem.n_obj
+        con = self.constraints is not None      # "pof" or "paths": constraint models, feasible rows, Constrained_Res
         cached_samples = self._get_cached_samples(self.n_obj, sample_exponent)
         if pof and acquisition_func is None and k == 2 and self.mode == "reference" and \
                 pareto.cache_stats(np.asarray(cached_samples, np.float64))[1] <= 0:
@@ -151,7 +152,10 @@ class MultiSurrogateOptimiser(BODriver):
             models = self._fit_many(Xsample, np.hstack((ysample[:, :k], gsample)))
             eng = engine_for(models, self.device)
             yfant, gfant, picks = ysample[:, :k], gsample, None
-            if self.batch_strategy == "thompson":
+            if self.batch_strategy == "thompson" and self.constraints == "paths":
+                # the draws' score is the improvement over the feasible front (empty: over the reference point's box)
+                picks = self._thompson_picks(eng, b, pareto.calc_pf(yfant[self._feasible(gfant)]))
+            elif self.batch_strategy == "thompson":
                 picks = self._thompson_picks(eng, b, pareto.calc_pf(yfant))
             if picks is None:              # the believer batch (also a Thompson iteration's fallback)
                 picks = []
@@ -159,7 +163,7 @@ class MultiSurrogateOptimiser(BODriver):
                     ref_dir = np.asarray(ref_dirs[np.random.randint(0, len(ref_dirs))])
                     yfeas = yfant[self._feasible(gfant)]
                     on = dict(eng=eng) if p else {}        # conditioned since the fit: search it as it stands
-                    if len(yfeas) == 0:
+                    if len(yfeas) == 0 and not self._paths_plan():         # "paths": every draw has its own front
                         x = self._maximise_feasibility(models, eng)
                     elif acquisition_func is None:
                         x, _ = self._get_proposed_EHVI("EHVI" if k == 2 else "EHVI_3D", models, self.ideal_point,
@@ -177,7 +181,7 @@ class MultiSurrogateOptimiser(BODriver):
                 Xsample = np.vstack((Xsample, x))
             gsample = np.vstack((gsample, self._constraint_values(picks)))
             done += b
-        if pof:
+        if con:
             return self._constrained_result(ysample, Xsample, gsample, hypervolume_convergence, n_init_samples)
         return self._result(ysample, Xsample, hypervolume_convergence, n_init_samples)
 
@@ -228,7 +232,7 @@ class MonoSurrogateOptimiser(BODriver):
         ``constraints="pof"``: ``current_best`` over the feasible rows only, and the surrogate is fitted together
         with the constraint models (``_fit_many``; without the keyword it is ``_fit``'s one model, as before)."""
         problem = self.test_problem
-        pof = self.constraints == "pof"
+        pof = self.constraints is not None      # "pof" or "paths": constraint models, feasible rows, Constrained_Res
         weights = np.asarray([1 / problem.n_obj] * problem.n_obj)
         Xsample, ysample = self._initial_samples(n_init_samples)
         gsample = self._constraint_values(Xsample)
@@ -247,17 +251,21 @@ class MonoSurrogateOptimiser(BODriver):
                 models = [self._fit(Xsample, aggregated_samples)]
             eng = engine_for(models, self.device)
             fant, gfant, picks = aggregated_samples, gsample, None
-            if self.batch_strategy == "thompson":
+            if self.batch_strategy == "thompson" and self.constraints == "paths":
+                ffeas = fant[self._feasible(gfant)]     # nothing feasible yet: any feasible candidate beats the worst
+                picks = self._thompson_picks(eng, b, best=float(ffeas.min() if len(ffeas) else fant.max()))
+            elif self.batch_strategy == "thompson":
                 picks = self._thompson_picks(eng, b)
             if picks is None:              # the believer batch (also a Thompson iteration's fallback)
                 picks = []
                 for p in range(b):
                     ffeas = fant[self._feasible(gfant)]
-                    if len(ffeas) == 0:
+                    if len(ffeas) == 0 and not self._paths_plan():         # "paths": every draw has its own best
                         x = self._maximise_feasibility(models, eng)
                     else:                  # eng: conditioned since the fit, so picks 2..b search it as it stands
                         x, _ = self._get_proposed(self._expected_improvement, models if pof else models[0],
-                                                  ffeas[np.argmin(ffeas)], **(dict(eng=eng) if p else {}))
+                                                  ffeas[np.argmin(ffeas)] if len(ffeas) else None,
+                                                  **(dict(eng=eng) if p else {}))
                     picks.append(x)
                     if p + 1 < b:
                         m = eng.condition(x[None, :])

@@ -37,7 +37,7 @@ struct ObjState {
 // a stand-alone entry then points those at the caller's device arrays, an omb_plan_* entry uploads the host geometry
 // and points them at ctx->geo (the fused chain's plan).  launch_acq / launch_acq_grad run it.
 enum PlanKind { PLAN_NONE = 0, PLAN_EHVI2D, PLAN_EHVI_MC, PLAN_EHVI_BOXES, PLAN_HVPOI, PLAN_EXPDEC, PLAN_EI, PLAN_MES,
-                PLAN_HVI_PATHS };
+                PLAN_HVI_PATHS, PLAN_HVI_PATHS_CON };
 
 struct Plan {
   int kind = PLAN_NONE;
@@ -47,6 +47,11 @@ struct Plan {
   int S = 0;                    // PLAN_MES: sampled minima per objective (geo: ystar (k, S)); PLAN_HVI_PATHS: paths
   int32_t box_off[kPathsMaxS + 1] = {};   // PLAN_HVI_PATHS: list s is rows box_off[s]..box_off[s+1] of boxes (geo: the
                                           // S grids (S, k, C))
+  // PLAN_HVI_PATHS_CON: slots k..k+path_con-1 are constraint models read through their sample paths, weighted by
+  // omb_hvi_paths_con's w_s at path_eta with path_flags (the plan entry sets none)
+  int path_con = 0;
+  double path_eta = 0;
+  unsigned path_flags = 0;
   double r[OMB_MAX_OBJ] = {};
   double s00 = 0, s01 = 0, hv = 0, best = 0, var_eps = 0, pof_eps = 0;
   int ei_kind = OMB_EI_PLAIN;
@@ -337,14 +342,34 @@ int describe_hvi_paths(omb_ctx* ctx, int k, int S, const void* y, int64_t ld, in
   return OMB_OK;
 }
 
-// The described sampled-front improvement over path values y (k·S rows at pitch ld), N > 0: the only place that
-// launches hvi_paths_kernel (the stand-alone entry and the chain's chunks).
-int run_hvi_paths(omb_ctx* ctx, const Plan& pl, const double* y, int64_t ld, int64_t N, double* out, const char* where) {
+// omb_hvi_paths_con / omb_plan_hvi_paths_con: describe_hvi_paths' description with the constraint slots behind it.
+int describe_hvi_paths_con(omb_ctx* ctx, int k, int S, int n_con, const void* y, int64_t ld, int64_t N,
+                           const void* coords, int C, const int32_t* box_off, const void* boxes, double eta,
+                           unsigned flags, const void* out, const void* u, Plan* pl) {
+  int rc = check_hvi_paths_con(E(ctx), k, S, n_con, y, ld, N, coords, C, box_off, boxes, eta, flags, out, u);
+  if (rc) return rc;
+  // every check of describe_hvi_paths has passed (a null out aside, which it never reads)
+  if ((rc = describe_hvi_paths(ctx, k, S, nullptr, 0, 0, coords, C, box_off, boxes, nullptr, pl))) return rc;
+  pl->kind = PLAN_HVI_PATHS_CON;
+  pl->path_con = n_con;
+  pl->path_eta = eta;
+  pl->path_flags = flags;
+  return OMB_OK;
+}
+
+// The described sampled-front improvement over path values y ((k [+ path_con])·S rows at pitch ld), N > 0: the only
+// place that launches hvi_paths_kernel / hvi_paths_con_kernel (the stand-alone entries and the chain's chunks).
+// u: omb_hvi_paths_con's per-path output (PLAN_HVI_PATHS_CON only).
+int run_hvi_paths(omb_ctx* ctx, const Plan& pl, const double* y, int64_t ld, int64_t N, double* out, const char* where,
+                  double* u = nullptr) {
   const int64_t wsd = hvi_paths_ws_doubles(N, pl.S);
   int rc;
   if (wsd && (rc = grow_dev(ctx, ctx->hws, sizeof(double) * (size_t)wsd, "HVI path workspace"))) return rc;
-  hipError_t e = launch_hvi_paths(ctx->stream, pl.k, pl.S, y, ld, N, pl.geo, pl.C, pl.boxes, pl.box_off, out,
-                                  wsd ? ctx->hws.as<double>() : nullptr);
+  double* ws = wsd ? ctx->hws.as<double>() : nullptr;
+  hipError_t e = pl.kind == PLAN_HVI_PATHS_CON
+                     ? launch_hvi_paths_con(ctx->stream, pl.k, pl.S, pl.path_con, y, ld, N, pl.geo, pl.C, pl.boxes,
+                                            pl.box_off, pl.path_eta, (pl.path_flags & OMB_CON_VIOLATION) != 0, out, u, ws)
+                     : launch_hvi_paths(ctx->stream, pl.k, pl.S, y, ld, N, pl.geo, pl.C, pl.boxes, pl.box_off, out, ws);
   if (e != hipSuccess) return hip_fail(ctx, e, where);
   return OMB_OK;
 }
@@ -416,6 +441,7 @@ int launch_acq_grad(omb_ctx* ctx, const Plan& pl, const double* mu, const double
     case PLAN_EXPDEC: unsup = "expected decomposition"; break;
     case PLAN_HVPOI: unsup = "HV-PoI"; break;
     case PLAN_HVI_PATHS: unsup = "sampled-front improvement (noisy EHVI / EI)"; break;
+    case PLAN_HVI_PATHS_CON: unsup = "constrained sampled-front improvement (noisy EHVI / EI)"; break;
     default:
       return fail(ctx, OMB_ESTATE, "corrupt plan");
   }
@@ -494,8 +520,8 @@ void gather_Ld(omb_ctx* ctx, int n_obj, const double** Ld) {
   for (int o = 0; o < n_obj; ++o) Ld[o] = ctx->obj[o].Ld;
 }
 
-// A sampled-front plan's state checks, before anything is launched, and its path arguments: every objective of
-// 0..k-1 holds a GP and exactly the plan's S sample paths (install_gp drops them, so a plan over a changed state is
+// A sampled-front plan's state checks, before anything is launched, and its path arguments: every slot of
+// 0..k-1 (and the constraint slots behind them under PLAN_HVI_PATHS_CON) holds a GP and exactly the plan's S sample paths (install_gp drops them, so a plan over a changed state is
 // refused here, never evaluated), within omb_paths_eval's limits.
 int chain_paths(omb_ctx* ctx, const Plan& pl, PathArgs* pa) {
   PathsObjInfo info[OMB_MAX_OBJ];
@@ -503,7 +529,8 @@ int chain_paths(omb_ctx* ctx, const Plan& pl, PathArgs* pa) {
     const ObjState& s = ctx->obj[o];
     info[o] = PathsObjInfo{s.set ? 1 : 0, s.d, s.n, s.path_S};
   }
-  for (int o = 0; o < pl.k; ++o) {
+  const int slots = pl.k + pl.path_con;
+  for (int o = 0; o < slots; ++o) {
     const ObjState& s = ctx->obj[o];
     if (!s.set)
       return fail(ctx, OMB_ESTATE, "objective %d has no GP state (call omb_set_gp, then omb_paths_set)", o);
@@ -512,9 +539,9 @@ int chain_paths(omb_ctx* ctx, const Plan& pl, PathArgs* pa) {
       return fail(ctx, OMB_ESTATE, "objective %d holds %d sample paths, the plan has %d fronts (call omb_paths_set)",
                   o, s.path_S, pl.S);
   }
-  int rc = check_paths_eval(E(ctx), pl.k, nullptr, 0, 0, nullptr, info);   // what is left: omb_paths_eval's OMB_EUNSUP
+  int rc = check_paths_eval(E(ctx), slots, nullptr, 0, 0, nullptr, info);   // what is left: omb_paths_eval's OMB_EUNSUP
   if (rc) return rc;
-  for (int o = 0; o < pl.k; ++o) {
+  for (int o = 0; o < slots; ++o) {
     const ObjState& s = ctx->obj[o];
     pa->o[o] = PathObj{s.dev, s.path_Of, s.path_Wf, s.path_Vf, s.path_MT, s.R, s.path_S, 0};
   }
@@ -534,12 +561,13 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
   const Plan& pl = ctx->plan;
   if (pl.kind == PLAN_NONE) return fail(ctx, OMB_ESTATE, "no acquisition plan (call an omb_plan_* function)");
   if (N < 0) return fail(ctx, OMB_EINVAL, "N=%lld < 0", (long long)N);
-  const bool paths = pl.kind == PLAN_HVI_PATHS;   // the posterior stage is the evaluation of the sample paths
+  // the posterior stage is the evaluation of the sample paths (of the path_con constraint slots too)
+  const bool paths = pl.kind == PLAN_HVI_PATHS || pl.kind == PLAN_HVI_PATHS_CON;
   PathArgs pa{};
   if (paths && (rc = chain_paths(ctx, pl, &pa))) return rc;
   GPArgs args;
   int max_R = 0;
-  if ((rc = gather_gp(ctx, pl.k + pl.n_con, &args, &max_R))) return rc;
+  if ((rc = gather_gp(ctx, pl.k + pl.n_con + pl.path_con, &args, &max_R))) return rc;
   if (!all_var && !ctx->posterior_all_var) args.var_skip = all_objectives(pl.k) & ~pl.var_mask;
   if (sobol) {
     if (ctx->sob_d == 0) return fail(ctx, OMB_ESTATE, "no Sobol state (call omb_set_sobol)");
@@ -561,7 +589,7 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
   // a sampled-front plan holds the (k·S, Nc) path values of one pass over Nc candidates in place of μ | σ² (K, N):
   // both of its kernels are per-candidate functions, so the values do not depend on the chunk
   const int64_t Nc = (paths && ctx->hvi_paths_chunk > 0 && ctx->hvi_paths_chunk < N) ? ctx->hvi_paths_chunk : N;
-  const size_t head = paths ? (size_t)k * pl.S * (size_t)Nc : 2 * (size_t)K * nd;
+  const size_t head = paths ? (size_t)(k + pl.path_con) * pl.S * (size_t)Nc : 2 * (size_t)K * nd;
   const size_t doubles = head + nd + (nd + 1) / 2 + (sobol ? nd * args.d : 0);
   if ((rc = grow_dev(ctx, ctx->work, (doubles ? doubles : 1) * sizeof(double), "chain workspace"))) return rc;
   if (paths && N > 0) {
@@ -612,7 +640,7 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
     // acquisition launches too (the stages alternate on one stream).
     for (int64_t c0 = 0; c0 < N && e == hipSuccess; c0 += Nc) {
       const int64_t nc = (N - c0) < Nc ? (N - c0) : Nc;
-      e = launch_paths_eval(ctx->stream, pa, k, ctx->obj[0].kind, ctx->paths_libcos, Xc + c0 * args.d, nc, nc, mu);
+      e = launch_paths_eval(ctx->stream, pa, k + pl.path_con, ctx->obj[0].kind, ctx->paths_libcos, Xc + c0 * args.d, nc, nc, mu);
       if (e == hipSuccess && c0 + nc == N) e = mark(2);
       if (e == hipSuccess && (rc = run_hvi_paths(ctx, pl, mu, nc, nc, vals + c0, "fused chain (hvi_paths)"))) return rc;
     }
@@ -1040,6 +1068,21 @@ int omb_hvi_paths(omb_ctx* ctx, int k, int S, const double* y_dev, int64_t ld, i
   return run_hvi_paths(ctx, pl, y_dev, ld, N, out_dev, "hvi_paths");
 }
 
+int omb_hvi_paths_con(omb_ctx* ctx, int k, int S, int n_con, const double* y_dev, int64_t ld, int64_t N,
+                      const double* coords_dev, int C, const int32_t* box_off_host, const uint16_t* boxes_dev,
+                      double eta, unsigned flags, double* out_dev, double* u_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  Plan pl;
+  if ((rc = describe_hvi_paths_con(ctx, k, S, n_con, y_dev, ld, N, coords_dev, C, box_off_host, boxes_dev, eta, flags,
+                                   out_dev, u_dev, &pl)))
+    return rc;
+  if (N == 0) return OMB_OK;
+  pl.geo = coords_dev;
+  pl.boxes = boxes_dev;
+  return run_hvi_paths(ctx, pl, y_dev, ld, N, out_dev, "hvi_paths_con", u_dev);
+}
+
 // Candidates per pass of omb_hvi_paths_grad: bounds its workspace at S·(k + 1)·chunk doubles (every lane's work
 // depends on its candidate alone, so the chunking leaves every bit as it is)
 constexpr int64_t kHviPathsGradChunk = 1 << 16;
@@ -1274,6 +1317,19 @@ int omb_plan_hvi_paths(omb_ctx* ctx, int k, int S, const double* coords_host, in
                       sizeof(uint16_t) * 2 * (size_t)k * (size_t)box_off_host[S]);
 }
 
+int omb_plan_hvi_paths_con(omb_ctx* ctx, int k, int S, int n_con, double eta, const double* coords_host, int C,
+                           const int32_t* box_off_host, const uint16_t* boxes_host) {
+  int rc = plan_enter(ctx);
+  if (rc) return rc;
+  Plan pl;
+  if ((rc = describe_hvi_paths_con(ctx, k, S, n_con, nullptr, 0, 0, coords_host, C, box_off_host, boxes_host, eta, 0u,
+                                   nullptr, nullptr, &pl)))
+    return rc;
+  if ((rc = check_box_lists(E(ctx), k, S, C, box_off_host, boxes_host))) return rc;
+  return install_plan(ctx, pl, coords_host, sizeof(double) * (size_t)S * k * C, boxes_host,
+                      sizeof(uint16_t) * 2 * (size_t)k * (size_t)box_off_host[S]);
+}
+
 int omb_plan_constraints(omb_ctx* ctx, int n_con, double pof_eps) {
   int rc = enter(ctx);
   if (rc) return rc;
@@ -1282,6 +1338,9 @@ int omb_plan_constraints(omb_ctx* ctx, int n_con, double pof_eps) {
   // the weight needs posterior moments of the constraint slots; the sampled-front chain computes none
   if (ctx->plan.kind == PLAN_HVI_PATHS && n_con > 0)
     return fail(ctx, OMB_EUNSUP, "the sampled-front improvement (noisy EHVI / EI) plan takes no constraints");
+  if (ctx->plan.kind == PLAN_HVI_PATHS_CON && n_con > 0)
+    return fail(ctx, OMB_EUNSUP, "the constrained sampled-front improvement plan carries its own constraints "
+                                 "(omb_plan_hvi_paths_con's n_con)");
   ctx->plan.n_con = n_con;
   ctx->plan.con_eps = n_con ? pof_eps : 0.0;
   return OMB_OK;
@@ -1298,6 +1357,7 @@ static const char* log_refused(const Plan& pl) {
     case PLAN_EXPDEC: return "expected decomposition";
     case PLAN_MES: return "max-value entropy search";
     case PLAN_HVI_PATHS: return "sampled-front improvement (noisy EHVI / EI)";
+    case PLAN_HVI_PATHS_CON: return "constrained sampled-front improvement (noisy EHVI / EI)";
     default: return "unknown";
   }
 }

@@ -197,7 +197,8 @@ int check_plan_mes(std::string* err, int k, int S, const double* ystar) {
 
 // check_hvi_paths' OMB_EINVAL refusals, then its OMB_EUNSUP ones (check_hvi_paths_grad puts its own between them)
 static int check_hvi_paths_args(std::string* err, int k, int S, const void* y, int64_t ld, int64_t N,
-                                const void* coords, const int32_t* box_off, const void* boxes, const void* out) {
+                                const void* coords, const int32_t* box_off, const void* boxes, const void* out,
+                                bool out_optional = false) {
   if (k < 1 || k > OMB_MAX_OBJ)
     return errf(err, OMB_EINVAL, "the sampled-front improvement needs 1 <= k <= %d objectives (k=%d)", OMB_MAX_OBJ, k);
   if (S < 1 || S > kPathsMaxS) return errf(err, OMB_EINVAL, "S=%d paths outside [1, %d]", S, kPathsMaxS);
@@ -208,7 +209,7 @@ static int check_hvi_paths_args(std::string* err, int k, int S, const void* y, i
     if (box_off[s + 1] <= box_off[s])
       return errf(err, OMB_EINVAL, "box_off[%d]=%d, box_off[%d]=%d: list %d is empty or the offsets decrease", s,
                   box_off[s], s + 1, box_off[s + 1], s);
-  if (N > 0 && (!y || !out)) return errf(err, OMB_EINVAL, "null device pointer");
+  if (N > 0 && (!y || (!out && !out_optional))) return errf(err, OMB_EINVAL, "null device pointer");
   if (((uintptr_t)y | (uintptr_t)coords | (uintptr_t)out) & 7)
     return errf(err, OMB_EINVAL, "path values, grids or output not 8-byte aligned");
   if ((uintptr_t)boxes & 3) return errf(err, OMB_EINVAL, "box lists not 4-byte aligned");
@@ -244,6 +245,26 @@ int check_hvi_paths_grad(std::string* err, int k, int S, int d, const void* y, c
   if (((uintptr_t)dy | (uintptr_t)grad | (uintptr_t)t | (uintptr_t)tgrad) & 7)
     return errf(err, OMB_EINVAL, "path gradients or gradient outputs not 8-byte aligned");
   return check_hvi_paths_limits(err, k, S, C, box_off);
+}
+
+int check_hvi_paths_con(std::string* err, int k, int S, int n_con, const void* y, int64_t ld, int64_t N,
+                        const void* coords, int C, const int32_t* box_off, const void* boxes, double eta,
+                        unsigned flags, const void* out, const void* u) {
+  int rc = check_hvi_paths_args(err, k, S, y, ld, N, coords, box_off, boxes, out, true);
+  if (!rc) rc = check_hvi_paths_limits(err, k, S, C, box_off);
+  if (rc) return rc;
+  if (n_con < 0) return errf(err, OMB_EINVAL, "n_con=%d < 0", n_con);
+  if (!(eta >= 0.0 && eta <= 1.79769313486231570815e308))
+    return errf(err, OMB_EINVAL, "eta=%g is negative or not finite", eta);
+  if (flags & ~(unsigned)OMB_CON_VIOLATION) return errf(err, OMB_EINVAL, "unknown flag bits 0x%x", flags);
+  if ((flags & OMB_CON_VIOLATION) && eta > 0.0)
+    return errf(err, OMB_EINVAL, "OMB_CON_VIOLATION needs eta = 0 (eta=%g)", eta);
+  if (N > 0 && !out && !u) return errf(err, OMB_EINVAL, "null outputs: neither the mean nor the per-path values");
+  if ((uintptr_t)u & 7) return errf(err, OMB_EINVAL, "per-path output not 8-byte aligned");
+  if ((int64_t)k + n_con > OMB_MAX_OBJ)   // n_con up to INT_MAX: the sum in 64 bits
+    return errf(err, OMB_EUNSUP, "k=%d objectives and n_con=%d constraints need %lld slots, above %d", k, n_con,
+                (long long)k + n_con, OMB_MAX_OBJ);
+  return OMB_OK;
 }
 
 int check_box_lists(std::string* err, int k, int S, int C, const int32_t* box_off, const uint16_t* boxes) {

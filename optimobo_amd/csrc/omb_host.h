@@ -121,6 +121,13 @@ int check_hvi_paths(std::string* err, int k, int S, const void* y, int64_t ld, i
 int check_hvi_paths_grad(std::string* err, int k, int S, int d, const void* y, const void* dy, int64_t ld, int64_t N,
                          const void* coords, int C, const int32_t* box_off, const void* boxes, const void* out,
                          const void* grad, const void* t, const void* tgrad);
+// omb_hvi_paths_con (and, with y = out = u = null, N = 0 and flags = 0, omb_plan_hvi_paths_con): check_hvi_paths'
+// refusals in its order, a null out allowed; then OMB_EINVAL for n_con < 0, eta negative or not finite, flag bits
+// other than OMB_CON_VIOLATION, that flag with eta > 0, (N > 0) out and u both null, or u off its 8-byte alignment;
+// then OMB_EUNSUP for k + n_con > OMB_MAX_OBJ.
+int check_hvi_paths_con(std::string* err, int k, int S, int n_con, const void* y, int64_t ld, int64_t N,
+                        const void* coords, int C, const int32_t* box_off, const void* boxes, double eta,
+                        unsigned flags, const void* out, const void* u);
 // check_box_list over every list of a host (box_off[S], 2k) list whose offsets passed check_hvi_paths.
 int check_box_lists(std::string* err, int k, int S, int C, const int32_t* box_off, const uint16_t* boxes);
 // Candidates per pass of the fused chain under an omb_plan_hvi_paths plan (the default of OMB_DEBUG_HVI_PATHS_CHUNK):

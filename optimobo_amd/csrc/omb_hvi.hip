@@ -252,6 +252,145 @@ hipError_t launch_hvi_paths(hipStream_t stream, int k, int S, const double* y, i
 }
 
 // ---------------------------------------------------------------------------------------
+// omb_hvi_paths_con: omb_hvi_paths with constraints through sample paths.  Rows (K + j)·S + s of y hold
+// path s of constraint j (g ≤ 0 feasible), n_con of them behind the K objectives:
+//   ω(g)   = 1[g ≤ 0] (eta = 0), or the sigmoid 1/(1 + e^{g/η}) written without overflow on either side (eta > 0)
+//   w_s    = ((1·ω(g_0s))·ω(g_1s))·…,  u_s = t_s·w_s, exactly 0.0 where w_s == 0.0,  out = ((0 + u_0) + … + u_{S−1}) / S
+// and with OMB_CON_VIOLATION (eta = 0) u_s = −((0 + max(g_0s, 0)) + max(g_1s, 0) + …) where w_s == 0.
+//   * hvi_paths_kernel's lane, staging, barriers and two launch forms; t_s is its t_s (hvi_slice / hvi_slice1 over the
+//     same slices), so at n_con = 0 every bit is omb_hvi_paths'.
+//   * The lane forms w_s before the box loop (a running product and a running sum: no per-constraint registers, so
+//     n_con stays a runtime value).  A wavefront none of whose lanes needs t_s (w_s == 0, a NaN, or past N) skips
+//     the box loop on a ballot; the skipped u_s is the defined value, so the skip changes no bit.  The barriers stand
+//     outside the skipped region.
+//   * A NaN among the K + n_con values of path s makes u_s, and so out, NaN.
+//   * u (S, ld), when given, takes every u_s; out may then be null.
+//   * SOFT is eta > 0: the indicator's instantiations carry no exponential and keep hvi_paths_kernel's occupancy.
+template <int K, bool SPLIT, bool SOFT>
+__global__ __launch_bounds__(kHviThreads) void hvi_paths_con_kernel(const double* __restrict__ y, int64_t ld, int64_t N,
+                                                                    int S, int n_con, const double* __restrict__ coords,
+                                                                    int C, const uint32_t* __restrict__ boxes,
+                                                                    HviPathOff po, double eta, int violation,
+                                                                    double* __restrict__ out, double* __restrict__ u) {
+#pragma clang fp contract(off)
+  extern __shared__ double hvi_paths_grid[];
+  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+  const int s0 = SPLIT ? (int)blockIdx.y : 0, s1 = SPLIT ? s0 + 1 : S;
+  // the tile loop is uniform over the workgroup: every lane reaches the barriers
+  for (int64_t base = (int64_t)blockIdx.x * kHviThreads; base < N; base += (int64_t)gridDim.x * kHviThreads) {
+    const int64_t i = base + threadIdx.x;
+    double total = 0.0;
+    for (int s = s0; s < s1; ++s) {
+      __syncthreads();   // the previous path's grid is read to the end
+      const double* g = coords + (size_t)s * K * C;
+      for (int t = threadIdx.x; t < K * C; t += kHviThreads) hvi_paths_grid[t] = g[t];
+      __syncthreads();
+      double w = 1.0, viol = 0.0;
+      bool nan = false;
+      if (i < N) {
+        for (int j = 0; j < n_con; ++j) {
+          const double gv = y[((int64_t)(K + j) * S + s) * ld + i];
+          nan |= gv != gv;
+          double om;
+          if constexpr (SOFT) {
+            if (gv <= 0.0) om = 1.0 / (1.0 + exp(gv / eta));
+            else {
+              const double e = exp(-gv / eta);
+              om = e / (1.0 + e);
+            }
+          } else {
+            om = gv <= 0.0 ? 1.0 : 0.0;
+          }
+          w = w * om;
+          viol = viol + fmax(gv, 0.0);
+        }
+      }
+      double yv[K];
+      if (i < N) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+          yv[j] = y[((int64_t)j * S + s) * ld + i];
+          nan |= yv[j] != yv[j];
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < K; ++j) yv[j] = 0.0;
+      }
+      const bool need = i < N && !nan && w != 0.0;
+      double ts = 0.0;
+      if (__ballot(need) != 0ull) {   // wave-uniform: a wavefront of infeasible candidates walks no box
+        if (need) {
+          const int B = po.off[s + 1] - po.off[s];
+          const uint32_t* bl = boxes + (size_t)po.off[s] * K;
+          const int slices = (B + kHviSlice - 1) / kHviSlice;
+          for (int c = 0; c < slices; ++c) {
+            double p;
+            if constexpr (K == 1) p = hvi_slice1(yv[0], hvi_paths_grid, C, bl, c * kHviSlice, min(B, (c + 1) * kHviSlice));
+            else p = hvi_slice<K>(yv, hvi_paths_grid, C, bl, c * kHviSlice, min(B, (c + 1) * kHviSlice));
+            ts += p;
+          }
+        }
+      }
+      if (i < N) {
+        double us;
+        if (nan) us = 0.0 + qnan;
+        else if (w == 0.0) us = violation ? -viol : 0.0;
+        else us = ts * w;
+        if (u) u[(int64_t)s * ld + i] = us;
+        if constexpr (SPLIT) {
+          if (out) out[(int64_t)s * N + i] = us;
+        } else {
+          total += us;
+        }
+      }
+    }
+    if constexpr (!SPLIT)
+      if (i < N && out) out[i] = total / (double)S;
+  }
+}
+
+hipError_t launch_hvi_paths_con(hipStream_t stream, int k, int S, int n_con, const double* y, int64_t ld, int64_t N,
+                                const double* coords, int C, const uint16_t* boxes, const int32_t* box_off, double eta,
+                                int violation, double* out, double* u, double* ws) {
+  if (N < 1 || S < 1 || S > kPathsMaxS || C < 2 || (int64_t)k * C > kMaxLdsDoubles || n_con < 0 ||
+      k + n_con > OMB_MAX_OBJ || (!out && !u) || ld < N || (reinterpret_cast<uintptr_t>(boxes) & 3))
+    return hipErrorInvalidValue;
+  HviPathOff po;
+  for (int s = 0; s <= kPathsMaxS; ++s) po.off[s] = box_off[s < S ? s : S];
+  const bool split = ws != nullptr && hvi_paths_ws_doubles(N, S) > 0;
+  const size_t shm = sizeof(double) * (size_t)k * C;
+  const int64_t nb = (N + kHviThreads - 1) / kHviThreads;
+  const dim3 g((unsigned)(nb > (1 << 20) ? (1 << 20) : nb), split ? (unsigned)S : 1u), b(kHviThreads);
+  const uint32_t* bw = reinterpret_cast<const uint32_t*>(boxes);
+  double* part = out ? ws : nullptr;   // the split form's u_s for the finish launch: not wanted without out
+  const bool soft = eta > 0.0;
+  switch (k) {
+#define OMB_HVIPC(KV)                                                                                              \
+  case KV:                                                                                                         \
+    if (split && soft)                                                                                             \
+      hipLaunchKernelGGL((hvi_paths_con_kernel<KV, true, true>), g, b, shm, stream, y, ld, N, S, n_con, coords, C, \
+                         bw, po, eta, violation, part, u);                                                         \
+    else if (split)                                                                                                \
+      hipLaunchKernelGGL((hvi_paths_con_kernel<KV, true, false>), g, b, shm, stream, y, ld, N, S, n_con, coords, C, \
+                         bw, po, eta, violation, part, u);                                                         \
+    else if (soft)                                                                                                 \
+      hipLaunchKernelGGL((hvi_paths_con_kernel<KV, false, true>), g, b, shm, stream, y, ld, N, S, n_con, coords, C, \
+                         bw, po, eta, violation, out, u);                                                          \
+    else                                                                                                           \
+      hipLaunchKernelGGL((hvi_paths_con_kernel<KV, false, false>), g, b, shm, stream, y, ld, N, S, n_con, coords,  \
+                         C, bw, po, eta, violation, out, u);                                                       \
+    break;
+    OMB_HVIPC(1) OMB_HVIPC(2) OMB_HVIPC(3) OMB_HVIPC(4) OMB_HVIPC(5) OMB_HVIPC(6) OMB_HVIPC(7) OMB_HVIPC(8)
+#undef OMB_HVIPC
+    default: return hipErrorInvalidValue;
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !split || !out) return e;
+  hipLaunchKernelGGL(hvi_paths_finish_kernel, dim3(g.x), b, 0, stream, ws, S, N, out);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
 // omb_hvi_paths_grad: omb_hvi_paths' value and its gradient through the paths.  Two launches, no atomics:
 //   1. hvi_paths_dy_kernel, one workgroup row per path (blockIdx.y) and one lane per candidate, walks list s as
 //      hvi_paths_kernel does and leaves t_s (its operations, so bitwise its value) and

@@ -120,6 +120,13 @@ int64_t hvi_paths_ws_doubles(int64_t N, int S);
 hipError_t launch_hvi_paths(hipStream_t stream, int k, int S, const double* y, int64_t ld, int64_t N,
                             const double* coords, int C, const uint16_t* boxes, const int32_t* box_off, double* out,
                             double* ws);
+// launch_hvi_paths with n_con constraint slots behind the k objectives (rows (k + j)·S + s of y; omb_hvi_paths_con,
+// DESIGN §26): u_s = t_s·w_s with the per-path feasibility weight w_s (eta = 0: the indicator; eta > 0: the sigmoid),
+// violation != 0 (eta = 0): u_s = −(total violation) where w_s = 0.  out (N) the mean, u (S, ld) the u_s; either may be
+// null, not both.  ws as launch_hvi_paths'.  At n_con = 0 out is bitwise launch_hvi_paths'.
+hipError_t launch_hvi_paths_con(hipStream_t stream, int k, int S, int n_con, const double* y, int64_t ld, int64_t N,
+                                const double* coords, int C, const uint16_t* boxes, const int32_t* box_off, double eta,
+                                int violation, double* out, double* u, double* ws);
 // launch_hvi_paths' out (bitwise) with grad[j·ld + i] = ∂out_i/∂x_j through dy, omb_paths_grad's gradient of the
 // rows of y at the same pitch ((k·S, d, ld)); t_out (S, ld) / tgrad (S, d, ld): the per-path t_s and ∂t_s/∂x, both
 // null or both set.  ws: hvi_paths_grad_ws_doubles(N, k, S) device doubles (the per-path t_s and ∂t_s/∂y).

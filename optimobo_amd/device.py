@@ -272,6 +272,35 @@ class AcqContext:
                                            _ptr(bd), _ptr(out)), "omb_hvi_paths")
         return out
 
+    def hvi_paths_con(self, y, n_con, coords, box_off, boxes, eta=0.0, violation=False, out=None, per_path=False):
+        """omb_hvi_paths_con: ``hvi_paths`` under constraints through sample paths — y (k + n_con, S, N) as
+        ``paths_eval`` returns it over the objectives and then the constraint models (g ≤ 0 feasible); path s of a
+        candidate counts with the weight w_s = Π_j ω(g_js): the indicator at ``eta`` = 0, the sigmoid of −g/eta above.
+        → (N,) the mean of u_s = t_s·w_s; with ``per_path`` → (mean (N,), u (S, N)).  ``violation`` (eta = 0): an
+        infeasible path scores −(its total violation) in place of 0.  At n_con = 0 the mean is bitwise ``hvi_paths``."""
+        c, o, b = self._box_lists_host(coords, box_off, boxes, "hvi_paths_con")
+        S, k, C = c.shape
+        n_con = int(n_con)
+        if not isinstance(y, torch.Tensor) or y.dtype != torch.float64 or y.device != self.device or y.dim() != 3 \
+                or n_con < 0 or tuple(y.shape[:2]) != (k + n_con, S) or (y.shape[2] > 1 and y.stride(2) != 1) \
+                or y.stride(0) != S * y.stride(1) or y.stride(1) < y.shape[2]:
+            raise ValueError(f"hvi_paths_con: y must be a ({k} + n_con, {S}, N) fp64 tensor on {self.device} with unit "
+                             "column stride and evenly pitched rows")
+        N, ld = y.shape[2], y.stride(1)
+        if out is None:
+            out = self._out(None, N)
+        elif out.dtype != torch.float64 or out.device != self.device or out.numel() < N or not out.is_contiguous():
+            raise ValueError(f"hvi_paths_con: out must be a contiguous fp64 tensor of at least {N} values on "
+                             f"{self.device}")
+        u = torch.empty((S, ld), dtype=torch.float64, device=self.device) if per_path else None
+        cd = torch.as_tensor(c, device=self.device)
+        bd = self._boxes_dev(b)
+        self._stream()
+        self._check(self.lib.omb_hvi_paths_con(self._h, k, S, n_con, _ptr(y), ld, N, _ptr(cd), C, _lib.host_ptr(o),
+                                               _ptr(bd), float(eta), _lib.CON_VIOLATION if violation else 0, _ptr(out),
+                                               None if u is None else _ptr(u)), "omb_hvi_paths_con")
+        return (out, u[:, :N]) if per_path else out
+
     def hvpoi(self, mu, var, cells, out=None):
         N = mu.shape[1]
         cells = _dev_f64(cells, self.device)
@@ -458,6 +487,15 @@ class AcqContext:
         c, o, b = self._box_lists_host(coords, box_off, boxes, "plan_hvi_paths")
         self._plan("omb_plan_hvi_paths", c.shape[1], c.shape[0], _lib.host_ptr(c), c.shape[2], _lib.host_ptr(o),
                    _lib.host_ptr(b))
+
+    def plan_hvi_paths_con(self, n_con, coords, box_off, boxes, eta=0.0):
+        """omb_plan_hvi_paths_con: ``hvi_paths_con`` (no violation score) as the chain's plan — every ``eval``
+        evaluates the installed sample paths of slots 0..k+n_con-1 (objectives, then constraint models) and averages
+        the weighted improvement over the S lists.  The plan carries its own constraints: ``plan_constraints`` and
+        ``plan_log`` refuse it (OMB_EUNSUP), ``plan_has_gradient()`` is False."""
+        c, o, b = self._box_lists_host(coords, box_off, boxes, "plan_hvi_paths_con")
+        self._plan("omb_plan_hvi_paths_con", c.shape[1], c.shape[0], int(n_con), float(eta), _lib.host_ptr(c),
+                   c.shape[2], _lib.host_ptr(o), _lib.host_ptr(b))
 
     def plan_constraints(self, n_con, pof_eps=1e-5):
         """omb_plan_constraints: the plan that is set treats objective slots k..k+n_con-1 as constraint models

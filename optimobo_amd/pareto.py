@@ -265,6 +265,29 @@ def threshold_lists(b):
     return [(np.array([[-np.inf, v]]), np.array([2], np.int32), np.array([[0, 1]], np.uint16)) for v in b]
 
 
+def feasible_fronts(F, G, max_point, max_boxes=1 << 20):
+    """Every path's own feasible front: F (k, S, n) the objectives' and G (c, S, n) the constraint models' path values
+    at the same n rows (g ≤ 0 feasible).  Per path s the rows with every G[:, s] ≤ 0, then ``calc_pf`` and
+    ``box_decomposition(PF_s, max_point, max_boxes)``; a path with no feasible row gets the empty front's single box.
+    k = 1 (``max_point`` None): ``threshold_lists`` of the smallest feasible value, and of the path's largest value
+    over all rows where none is feasible (nothing known to beat: a feasible candidate improves on the worst seen).
+    → (fronts, decompositions): S arrays (P_s, k) (k = 1: b (S,)) and the input of ``pack_box_lists``."""
+    F = np.asarray(F, np.float64)
+    G = np.asarray(G, np.float64)
+    if F.ndim != 3 or G.ndim != 3 or G.shape[1:] != F.shape[1:]:
+        raise ValueError(f"feasible_fronts: F {F.shape} and G {G.shape} are not (k, S, n) and (c, S, n)")
+    k, S, _ = F.shape
+    if (k == 1) != (max_point is None):
+        raise ValueError("feasible_fronts: one objective takes max_point=None, several need the reference point")
+    feas = np.all(G <= 0.0, axis=0)                                  # (S, n); a NaN is infeasible
+    if k == 1:
+        b = np.array([F[0, s, feas[s]].min() if feas[s].any() else F[0, s].max() for s in range(S)])
+        return b, threshold_lists(b)
+    fronts = [calc_pf(np.ascontiguousarray(F[:, s, feas[s]].T)) if feas[s].any() else np.zeros((0, k))
+              for s in range(S)]
+    return fronts, [box_decomposition(pf, max_point, max_boxes=max_boxes) for pf in fronts]
+
+
 def pack_box_lists(decomps):
     """S ``box_decomposition`` results (or ``threshold_lists``) of the same k as one input of omb_hvi_paths:
     (coords (S, k, C) f64, box_off (S + 1,) int32, boxes (ΣB, 2k) uint16).  C is the largest grid; a shorter grid is
