@@ -37,6 +37,8 @@ extern "C" {
 #define OMB_MAX_TRAIN 1024 /* n_train handled by the fused posterior kernel */
 #define OMB_MAX_TRAIN_DENSE 16384 /* n_train of the GEMM-based posterior path used above OMB_MAX_TRAIN */
 #define OMB_HVI_PATHS_CHUNK 262144 /* candidates per pass of the fused chain under an omb_plan_hvi_paths plan */
+#define OMB_NONDOM_SETS 16         /* point sets of one omb_nondominated call */
+#define OMB_NONDOM_POINTS 16777216 /* points per set of omb_nondominated (2^24) */
 
 enum {
   OMB_OK = 0,
@@ -316,6 +318,33 @@ int omb_hvi_paths_grad(omb_ctx* ctx, int k, int S, int d, const double* y_dev, c
 int omb_hvi_paths_con(omb_ctx* ctx, int k, int S, int n_con, const double* y_dev, int64_t ld, int64_t N,
                       const double* coords_dev, int C, const int32_t* box_off_host, const uint16_t* boxes_dev,
                       double eta, unsigned flags, double* out_dev, double* u_dev);
+
+/* The non-dominated points of S independent point sets (everything minimised): the Pareto set of the posterior mean
+ * over a candidate set (S = 1: the (k, N) layout of mu_dev) or of every sample path over it.  y_dev has omb_paths_eval's
+ * layout: coordinate j of point i of set s is y_dev[(j·S + s)·ld + i].  a dominates b when a_j ≤ b_j for every j and
+ * a_j < b_j for some j, in IEEE comparisons:
+ *   mask_dev[s·ldm + i] = 1 when no point of set s dominates i and no coordinate of i is NaN, else 0   (i < N)
+ *   count_dev[s]        = the number of ones in row s
+ * Duplicates are all kept; −0.0 equals +0.0; ±∞ are ordinary values; a point with a NaN dominates nobody; k = 1 keeps
+ * every occurrence of the minimum.  Mask bytes at columns ≥ N are not written.  A sieve (omb_pareto.hip): tile passes
+ * drop, workgroup by workgroup, the points that another point of the same 1024 dominates and append the survivors to
+ * a list (a slot counter with atomics: the order of a list changes no result), the final pass tests every remaining
+ * survivor against all of them.  Filtering against survivors alone is exact (dominance on NaN-free points is a strict
+ * partial order), so the mask is a function of the set alone: bitwise the same whatever ld, ldm, the launch shape and
+ * the order of the lists.  N²·k comparisons at worst (every point non-dominated).
+ * SYNCHRONISES: the survivor counts are read back after every tile pass (at most 4) to size the next launch; the
+ * final pass is asynchronous.  Scratch is a context buffer grown on demand (8 bytes per point and set at most).
+ * Touches no plan, no GP state and no paths.
+ *   OMB_EINVAL  k outside [1, OMB_MAX_OBJ], S outside [1, OMB_NONDOM_SETS], N < 0, ld < N or ldm < N, a NULL
+ *               count_dev, a NULL y_dev / mask_dev with N > 0, y_dev or count_dev off 8-byte alignment — in this order
+ *   OMB_EUNSUP  N > OMB_NONDOM_POINTS
+ * N = 0 returns OMB_OK and writes count_dev[s] = 0 only. */
+int omb_nondominated(omb_ctx* ctx, int k, int S, const double* y_dev, int64_t ld, int64_t N, uint8_t* mask_dev,
+                     int64_t ldm, int64_t* count_dev);
+/* The sieve of the last omb_nondominated call on this context: *rounds_host its tile passes (0 before any call, at
+ * most 4) and survivors_host[r] (5 entries; those past *rounds_host are 0) the largest set's survivors after pass r —
+ * what the final pass then tested against itself is the last of them.  Host values; nothing is launched. */
+int omb_nondominated_stats(omb_ctx* ctx, int64_t* survivors_host, int* rounds_host);
 
 /* Hypervolume-based PoI of EMO (emo.py:176-228): cells_dev (C, 2, 2) [upper, lower]. */
 int omb_hvpoi(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,

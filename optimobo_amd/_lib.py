@@ -37,6 +37,8 @@ DEBUG_HVI_PATHS_CHUNK = 15
 MAX_OBJ, MAX_DIM, MAX_TRAIN, MAX_TRAIN_DENSE = 8, 256, 1024, 16384
 CON_VIOLATION = 1              # OMB_CON_VIOLATION: omb_hvi_paths_con's flag (infeasible paths score −violation)
 HVI_PATHS_CHUNK = 1 << 18      # OMB_HVI_PATHS_CHUNK: candidates per pass of the chain under plan_hvi_paths
+NONDOM_SETS = 16               # OMB_NONDOM_SETS: point sets of one omb_nondominated call
+NONDOM_POINTS = 1 << 24        # OMB_NONDOM_POINTS: points per set of omb_nondominated
 
 _p = ctypes.c_void_p
 _d = ctypes.c_double
@@ -66,6 +68,9 @@ SIGNATURES = {
     "omb_hvi_paths": (_i, [_p, _i, _i, _p, _i64, _i64, _p, _i, _p, _p, _p]),
     "omb_hvi_paths_grad": (_i, [_p, _i, _i, _i, _p, _p, _i64, _i64, _p, _i, _p, _p, _p, _p, _p, _p]),
     "omb_hvi_paths_con": (_i, [_p, _i, _i, _i, _p, _i64, _i64, _p, _i, _p, _p, _d, ctypes.c_uint, _p, _p]),
+    # non-dominated filter
+    "omb_nondominated": (_i, [_p, _i, _i, _p, _i64, _i64, _p, _i64, _p]),
+    "omb_nondominated_stats": (_i, [_p, ctypes.POINTER(_i64), ctypes.POINTER(_i)]),
     "omb_hvpoi": (_i, [_p, _p, _p, _i64, _i64, _p, _i, _p]),
     "omb_expdec": (_i, [_p, _i, _p, _p, _i64, _i64, _p, _i, _i, _dp, _dp, _dp, _dp, _d, _p]),
     "omb_ei": (_i, [_p, _p, _p, _i64, _d, _d, _p]),

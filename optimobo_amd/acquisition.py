@@ -174,6 +174,96 @@ class AcquisitionEngine:
         Xc = Xc if isinstance(Xc, torch.Tensor) else self._dev(np.atleast_2d(Xc))
         return self.ctx.paths_eval(Xc, self.n_obj)
 
+    def nondominated(self, Y, S=1):
+        """``AcqContext.nondominated`` over the engine's context: the non-dominated points of Y (k, N) — S = 1 — or
+        (k, S, N), a device tensor or host values → (mask (S, N) bool, counts (S,)) on the device."""
+        Yd = Y if isinstance(Y, torch.Tensor) else self._dev(Y)
+        return self.ctx.nondominated(Yd.to(device=self.device, dtype=torch.float64), S)
+
+    def path_fronts(self, Xc):
+        """The Pareto set of every installed sample path (``sample_paths(S)``) over the candidates Xc (N, d): one
+        ``path_values`` and one ``nondominated`` call over the S sets → a list of S pairs (index (P_s,) int64
+        ascending, values (P_s, n_obj)) of device tensors.  What Pareto-front entropy search, joint entropy search
+        and TSEMO-style batches start from."""
+        Y = self.path_values(Xc)                                    # (n_obj, S, N)
+        mask, _ = self.ctx.nondominated(Y, Y.shape[1])
+        out = []
+        for s in range(Y.shape[1]):
+            idx = torch.nonzero(mask[s]).reshape(-1)
+            out.append((idx, Y[:, s, :].index_select(1, idx).T.contiguous()))
+        return out
+
+    def predicted_front(self, lower, upper, n_candidates=1 << 18, seed=0, n_con=0, min_feasibility=0.5, include=None,
+                        chunk=1 << 18, pof_eps=1e-5):
+        """The model's Pareto set: the non-dominated set of the posterior mean of the first n_obj − ``n_con`` loaded
+        models over a dense candidate set — the answer to "which designs do I keep?" when the observations are noisy
+        (the observed front is made of the luckiest draws and names evaluated points only).
+
+        Candidates: the rows of ``include`` (the training inputs, say), then the first ``n_candidates`` points of the
+        device Sobol' sequence over the box seeded by ``seed``, as ``maximise`` draws them; a candidate's ``index`` is
+        its place in that order.  They are taken in pieces of ``chunk``: ``posterior``; with ``n_con`` > 0 (the last
+        n_con loaded models are constraint models, g ≤ 0 feasible) the candidates whose ``feasibility`` (at
+        ``pof_eps``) is below ``min_feasibility`` are dropped; ``nondominated`` on the means; the survivors go to a
+        pool, and one last ``nondominated`` runs over the pool.  A piece's survivors contain every point of it that
+        nothing dominates, so the result does not depend on ``chunk``.  A candidate with a NaN mean is never kept.
+
+        Returns a dict of numpy arrays in ascending candidate order — ``X`` (P, d), ``mean`` (P, k), ``var`` (P, k),
+        ``index`` (P,) — and ``info``: ``chunk_survivors`` (one count per piece), ``feasible`` (candidates that passed
+        the feasibility threshold; all of them without constraints), ``candidates``.  No feasible candidate gives the
+        empty front with ``info["feasible"] == 0``.  The Sobol' state of the context is overwritten; plans, GP states
+        and paths are left as they are."""
+        lower = np.asarray(lower, np.float64).reshape(-1)
+        upper = np.asarray(upper, np.float64).reshape(-1)
+        d, n_con, n_cand, chunk = lower.size, int(n_con), int(n_candidates), int(chunk)
+        if self.n_obj < 1:
+            raise RuntimeError("predicted_front: no models loaded (call load_models first)")
+        if not 0 <= n_con < self.n_obj:
+            raise ValueError(f"predicted_front: n_con={n_con} outside [0, {self.n_obj - 1}] (the loaded models less "
+                             "one objective)")
+        if n_cand < 0 or chunk < 1:
+            raise ValueError(f"predicted_front: n_candidates={n_cand} must be >= 0 and chunk={chunk} >= 1")
+        k = self.n_obj - n_con
+        inc = self._dev(np.empty((0, d)) if include is None else np.atleast_2d(np.asarray(include, np.float64)))
+        if inc.shape[1] != d:
+            raise ValueError(f"predicted_front: include has {inc.shape[1]} columns, the box {d}")
+        n_inc = inc.shape[0]
+        total = n_inc + n_cand
+        if n_cand:
+            self.ctx.set_sobol(d, lower, upper, seed=seed)
+        pool_X, pool_mu, pool_var, pool_idx, survivors, feasible = [], [], [], [], [], 0
+        for c0 in range(0, total, chunk):
+            c1 = min(total, c0 + chunk)
+            parts = []
+            if c0 < n_inc:
+                parts.append(inc[c0:min(c1, n_inc)])
+            if c1 > n_inc:
+                s0 = max(c0, n_inc) - n_inc
+                parts.append(self.ctx.sobol(s0, c1 - n_inc - s0))
+            X = parts[0] if len(parts) == 1 else torch.cat(parts)
+            idx = torch.arange(c0, c1, dtype=torch.int64, device=self.device)
+            mu, var = self.posterior(X)
+            if n_con:
+                keep = self.ctx.feasibility(mu[k:], var[k:], float(pof_eps)) >= float(min_feasibility)
+                X, idx = X[keep], idx[keep]
+                mu, var = mu[:, keep], var[:, keep]
+            feasible += int(idx.numel())
+            mu, var = mu[:k].contiguous(), var[:k].contiguous()
+            mask, _ = self.ctx.nondominated(mu)
+            m = mask[0]
+            survivors.append(int(m.sum()))
+            pool_X.append(X[m])
+            pool_mu.append(mu[:, m])
+            pool_var.append(var[:, m])
+            pool_idx.append(idx[m])
+        info = dict(chunk_survivors=survivors, feasible=feasible, candidates=total)
+        if not pool_idx or sum(survivors) == 0:
+            return dict(X=np.empty((0, d)), mean=np.empty((0, k)), var=np.empty((0, k)), index=np.empty(0, np.int64),
+                        info=info)
+        X, mu, var, idx = torch.cat(pool_X), torch.cat(pool_mu, 1), torch.cat(pool_var, 1), torch.cat(pool_idx)
+        m = self.ctx.nondominated(mu.contiguous())[0][0]
+        return dict(X=X[m].cpu().numpy(), mean=mu[:, m].T.contiguous().cpu().numpy(),
+                    var=var[:, m].T.contiguous().cpu().numpy(), index=idx[m].cpu().numpy(), info=info)
+
     def path_values_and_grad(self, Xc):
         """The installed sample paths and their gradients at Xc (N, d) → device tensors (vals (n_obj, S, N), grad
         (n_obj, S, d, N)) (AcqContext.paths_grad); vals are bitwise ``path_values``'."""

@@ -31,6 +31,10 @@ class BODriver:
     thompson_features = 1024
     thompson_refine_rounds = 2
     path_gradients = False       # the keyword's default (an instance attribute only where it is True)
+    model_front = False          # likewise; _model_front: whether the driver takes model_front=True
+    model_front_candidates = 1 << 18
+    _model_front = False
+    model_front_min_feasibility = 0.5    # constraints: the probability of feasibility a member of the model front needs
     # constraints="paths": the width of the sigmoid that stands for the feasibility indicator in the noisy EHVI / EI
     # (0.0: the indicator itself; a Thompson batch always takes the indicator)
     paths_eta = 0.0
@@ -38,7 +42,8 @@ class BODriver:
     def __init__(self, test_problem, ideal_point=None, max_point=None, mode="reference", n_candidates=1 << 14,
                  refine_rounds=2, seed=None, device=None, polish=True, starts=None, noise=0.0, batch_size=1,
                  constraints=None, batch_strategy="believer", thompson_sampler="joint", log_acquisition=False,
-                 acquisition=None, mes_samples=8, mes_candidates=1 << 16, path_gradients=False):
+                 acquisition=None, mes_samples=8, mes_candidates=1 << 16, path_gradients=False, model_front=False,
+                 model_front_candidates=1 << 18):
         self.test_problem = test_problem
         self.max_point = max_point
         self.ideal_point = ideal_point
@@ -122,6 +127,21 @@ class BODriver:
                                  f"(n_var={self.n_vars})")
         if path_gradients:      # False stays the class attribute: the instance is the one built without the keyword
             self.path_gradients = True
+        # report the model's Pareto set next to the observed one (not in the reference): after its loop ``solve`` fits
+        # the surrogates once more on everything evaluated and filters their posterior mean over the evaluated inputs
+        # and ``model_front_candidates`` Sobol' points of the box (AcquisitionEngine.predicted_front) — under noise the
+        # observed front is made of the luckiest draws.  False fits and draws nothing more: the run without it.
+        if not isinstance(model_front, (bool, np.bool_)):
+            raise ValueError(f"model_front must be True or False, not {model_front!r}")
+        if model_front:
+            if not self._model_front:
+                raise ValueError(f"{type(self).__name__} does not support model_front=True (MultiSurrogateOptimiser "
+                                 "does: its surrogates model the objectives themselves)")
+            if isinstance(model_front_candidates, bool) or not isinstance(model_front_candidates, (int, np.integer)) \
+                    or model_front_candidates < 1:
+                raise ValueError(f"model_front_candidates must be an integer >= 1, not {model_front_candidates!r}")
+            self.model_front = True
+            self.model_front_candidates = int(model_front_candidates)
         self.thompson_fallbacks = 0   # Thompson iterations that fell back to the believer batch
         self._iteration = 0
         self._mes_picks = 0
@@ -390,6 +410,20 @@ class BODriver:
         indicies = [i for i, item in enumerate(ysample) if item in pf_approx]
         return Res(pf_approx, Xsample[indicies], ysample, Xsample, hypervolume_convergence, self.n_obj,
                    n_init_samples)
+
+    def _with_model_front(self, res, Xsample, Y):
+        """model_front=True: one more fit of the surrogates on all evaluated data — the columns of ``Y``: the
+        objectives, then the constraints under constraints="pof" / "paths" — and the model's Pareto set over the
+        evaluated inputs and ``model_front_candidates`` Sobol' points (AcquisitionEngine.predicted_front), set on
+        ``res`` as ``model_pf_inputs`` (P, n_var), ``model_pf_mean`` and ``model_pf_var`` (P, n_obj)."""
+        if not self.model_front:
+            return res
+        eng = engine_for(self._fit_many(Xsample, Y), self.device)
+        front = eng.predicted_front(self.test_problem.xl, self.test_problem.xu, n_candidates=self.model_front_candidates,
+                                    seed=self._search_seed(), n_con=Y.shape[1] - self.n_obj,
+                                    min_feasibility=self.model_front_min_feasibility, include=Xsample)
+        res.model_pf_inputs, res.model_pf_mean, res.model_pf_var = front["X"], front["mean"], front["var"]
+        return res
 
     def _initial_samples(self, n_init_samples):
         ranges = list(zip(self.test_problem.xl, self.test_problem.xu))

@@ -35,6 +35,7 @@ class MultiSurrogateOptimiser(BODriver):
     _batch_strategies = ("believer", "thompson")
     _log_acquisition_modes = ("textbook",)     # the exact EHVI over boxes; reference mode plans EHVI-2D / Monte-Carlo
     _acquisitions = ("mes", "nehvi")           # MESMO / the noisy EHVI in place of EHVI, in either mode
+    _model_front = True                        # model_front=True: the posterior mean's Pareto set on the result
 
     def _get_cached_samples(self, dimensions, sample_exponent):
         """optimisers.py:121-141 — scrambled Sobol mapped through the normal ppf."""
@@ -120,7 +121,11 @@ class MultiSurrogateOptimiser(BODriver):
         feasibility alone (``_maximise_feasibility``).  Without the keyword G has no columns: every row is feasible.
 
         ``log_acquisition=True`` (textbook mode, ``acquisition_func`` None): every pick maximises the logarithm of
-        the exact EHVI (plus log F under ``constraints="pof"``; log F alone while no row is feasible)."""
+        the exact EHVI (plus log F under ``constraints="pof"``; log F alone while no row is feasible).
+
+        ``model_front=True``: after the loop the surrogates (the constraint models too) are fitted once more on
+        everything evaluated and the result carries the model's Pareto set — ``model_pf_inputs``, ``model_pf_mean``,
+        ``model_pf_var`` (``_with_model_front``); the samples are the run's without it, bit for bit."""
         if self.acquisition is not None and acquisition_func is not None:
             raise ValueError(f"acquisition={self.acquisition!r} takes the place of the EHVI (acquisition_func=None), "
                              "not of a scalarised expected decomposition")
@@ -182,8 +187,10 @@ class MultiSurrogateOptimiser(BODriver):
             gsample = np.vstack((gsample, self._constraint_values(picks)))
             done += b
         if con:
-            return self._constrained_result(ysample, Xsample, gsample, hypervolume_convergence, n_init_samples)
-        return self._result(ysample, Xsample, hypervolume_convergence, n_init_samples)
+            res = self._constrained_result(ysample, Xsample, gsample, hypervolume_convergence, n_init_samples)
+        else:
+            res = self._result(ysample, Xsample, hypervolume_convergence, n_init_samples)
+        return self._with_model_front(res, Xsample, np.hstack((ysample[:, :k], gsample)))
 
 
 class MonoSurrogateOptimiser(BODriver):

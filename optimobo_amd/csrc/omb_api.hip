@@ -114,6 +114,10 @@ struct omb_ctx {
   DevBuf aws;    // omb_gp_append: the bordered state (AppendWs)
   DevBuf hws;    // omb_hvi_boxes: the slices' sums of a small batch (hvi_ws_doubles)
   DevBuf pws;    // omb_paths_min: the first launch's per-workgroup (value, index) pairs
+  DevBuf nws;    // omb_nondominated: slot counters | final-pass counts | the first survivor list (S, N)
+  DevBuf nws2;   // omb_nondominated: the second survivor list (S, survivors of the first pass)
+  int nd_rounds = 0;                              // omb_nondominated_stats: the last call's tile passes
+  int64_t nd_survivors[kNdMaxRounds + 1] = {};    // and the largest set's survivors after each
   // device fault word (pinned, mapped host memory): kernels mark it, enter() reports it
   int* fault_host = nullptr;
   int* fault_dev = nullptr;
@@ -719,7 +723,7 @@ int omb_destroy(omb_ctx* ctx) {
   if (ctx->result_host) (void)hipHostFree(ctx->result_host);
   if (ctx->info_host) (void)hipHostFree(ctx->info_host);
   for (DevBuf* b : {&ctx->geo, &ctx->work, &ctx->tws, &ctx->ichol, &ctx->sws, &ctx->ews, &ctx->fws, &ctx->dws, &ctx->gws,
-                    &ctx->aws, &ctx->hws, &ctx->pws})
+                    &ctx->aws, &ctx->hws, &ctx->pws, &ctx->nws, &ctx->nws2})
     if (b->p) (void)hipFree(b->p);
   if (ctx->stage) (void)hipHostFree(ctx->stage);
   if (ctx->sob) (void)hipFree(ctx->sob);
@@ -1109,6 +1113,71 @@ int omb_hvi_paths_grad(omb_ctx* ctx, int k, int S, int d, const double* y_dev, c
                                          ctx->hws.as<double>());
     if (e != hipSuccess) return hip_fail(ctx, e, "hvi_paths_grad");
   }
+  return OMB_OK;
+}
+
+int omb_nondominated(omb_ctx* ctx, int k, int S, const double* y_dev, int64_t ld, int64_t N, uint8_t* mask_dev,
+                     int64_t ldm, int64_t* count_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if ((rc = check_nondominated(E(ctx), k, S, y_dev, ld, N, mask_dev, ldm, count_dev))) return rc;
+  ctx->nd_rounds = 0;
+  memset(ctx->nd_survivors, 0, sizeof(ctx->nd_survivors));
+  if (N == 0) {
+    OMB_HIP(ctx, hipMemsetAsync(count_dev, 0, sizeof(int64_t) * (size_t)S, ctx->stream));
+    return OMB_OK;
+  }
+  // nws: (kNdMaxRounds + 1)·kNdMaxS slot counters | S·nd_final_blocks(N) final-pass counts | list A (S, N)
+  constexpr size_t kCnt = (size_t)(kNdMaxRounds + 1) * kNdMaxS;
+  const size_t nbc = (size_t)S * (size_t)nd_final_blocks(N);
+  if ((rc = grow_dev(ctx, ctx->nws, sizeof(int32_t) * (kCnt + nbc + (size_t)S * (size_t)N), "non-dominated lists")))
+    return rc;
+  int32_t* cnt = ctx->nws.as<int32_t>();
+  int32_t* blockcnt = cnt + kCnt;
+  int32_t* listA = blockcnt + nbc;
+  OMB_HIP(ctx, hipMemsetAsync(cnt, 0, sizeof(int32_t) * kCnt, ctx->stream));
+  // the tile passes: the points themselves into A, then A → B → A → B while a pass still halves the list
+  const int32_t* in = nullptr;
+  const int32_t* in_cnt = nullptr;
+  int64_t in_pitch = 0, before = N;
+  int32_t host_cnt[kNdMaxS];
+  for (int r = 0;; ++r) {
+    int32_t* out = listA;
+    int64_t out_pitch = N;
+    if (r & 1) {
+      if ((rc = grow_dev(ctx, ctx->nws2, sizeof(int32_t) * (size_t)S * (size_t)before, "non-dominated lists")))
+        return rc;
+      out = ctx->nws2.as<int32_t>();
+      out_pitch = before;
+    }
+    int32_t* out_cnt = cnt + (size_t)r * kNdMaxS;
+    hipError_t e = launch_nd_tile(ctx->stream, k, S, y_dev, ld, N, in, in_pitch, in_cnt, before, out, out_pitch,
+                                  out_cnt, mask_dev, ldm);
+    if (e != hipSuccess) return hip_fail(ctx, e, "nondominated tile pass");
+    OMB_HIP(ctx, hipMemcpyAsync(host_cnt, out_cnt, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, ctx->stream));
+    OMB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    int64_t now = 0;
+    for (int s = 0; s < S; ++s) now = host_cnt[s] > now ? host_cnt[s] : now;
+    ctx->nd_rounds = r + 1;
+    ctx->nd_survivors[r] = now;
+    in = out;
+    in_cnt = out_cnt;
+    in_pitch = out_pitch;
+    const bool more = nd_another_round(r + 1, before, now);
+    before = now;
+    if (!more) break;
+  }
+  hipError_t e = launch_nd_final(ctx->stream, k, S, y_dev, ld, in, in_pitch, in_cnt, before, mask_dev, ldm, blockcnt,
+                                 count_dev);
+  if (e != hipSuccess) return hip_fail(ctx, e, "nondominated final pass");
+  return OMB_OK;
+}
+
+int omb_nondominated_stats(omb_ctx* ctx, int64_t* survivors_host, int* rounds_host) {
+  if (!ctx) return OMB_EINVAL;
+  if (!survivors_host || !rounds_host) return fail(ctx, OMB_EINVAL, "null output");
+  for (int r = 0; r <= kNdMaxRounds; ++r) survivors_host[r] = ctx->nd_survivors[r];
+  *rounds_host = ctx->nd_rounds;
   return OMB_OK;
 }
 

@@ -267,6 +267,21 @@ int check_hvi_paths_con(std::string* err, int k, int S, int n_con, const void* y
   return OMB_OK;
 }
 
+int check_nondominated(std::string* err, int k, int S, const void* y, int64_t ld, int64_t N, const void* mask,
+                       int64_t ldm, const void* count) {
+  if (k < 1 || k > OMB_MAX_OBJ) return errf(err, OMB_EINVAL, "k=%d outside [1, %d]", k, OMB_MAX_OBJ);
+  if (S < 1 || S > kNdMaxS) return errf(err, OMB_EINVAL, "S=%d outside [1, %d]", S, kNdMaxS);
+  if (N < 0) return errf(err, OMB_EINVAL, "N=%lld < 0", (long long)N);
+  if (ld < N || ldm < N)
+    return errf(err, OMB_EINVAL, "ld=%lld or ldm=%lld < N=%lld", (long long)ld, (long long)ldm, (long long)N);
+  if (!count) return errf(err, OMB_EINVAL, "null count pointer");
+  if (N > 0 && (!y || !mask)) return errf(err, OMB_EINVAL, "null point or mask pointer");
+  if (((uintptr_t)y & 7) || ((uintptr_t)count & 7)) return errf(err, OMB_EINVAL, "y or count not 8-byte aligned");
+  if (N > kNdMaxN)
+    return errf(err, OMB_EUNSUP, "N=%lld above %lld points per set", (long long)N, (long long)kNdMaxN);
+  return OMB_OK;
+}
+
 int check_box_lists(std::string* err, int k, int S, int C, const int32_t* box_off, const uint16_t* boxes) {
   for (int s = 0; s < S; ++s) {
     std::string one;

@@ -128,6 +128,22 @@ int check_hvi_paths_grad(std::string* err, int k, int S, int d, const void* y, c
 int check_hvi_paths_con(std::string* err, int k, int S, int n_con, const void* y, int64_t ld, int64_t N,
                         const void* coords, int C, const int32_t* box_off, const void* boxes, double eta,
                         unsigned flags, const void* out, const void* u);
+// Non-dominated filter (omb_nondominated, omb_pareto.hip).
+constexpr int kNdMaxS = OMB_NONDOM_SETS;        // point sets of one call (omb_paths_eval's S)
+constexpr int64_t kNdMaxN = OMB_NONDOM_POINTS;  // points per set
+constexpr int kNdTile = 1024;                   // points of one LDS tile = lanes of its workgroup (64 KiB at k = 8)
+constexpr int kNdMaxRounds = 4;                 // tile passes before the final pass
+// omb_nondominated, in this order: OMB_EINVAL for k outside [1, OMB_MAX_OBJ], S outside [1, kNdMaxS], N < 0, ld < N or
+// ldm < N, a null count, (N > 0) a null y / mask, or y / count off 8-byte alignment; OMB_EUNSUP for N > kNdMaxN.
+int check_nondominated(std::string* err, int k, int S, const void* y, int64_t ld, int64_t N, const void* mask,
+                       int64_t ldm, const void* count);
+// Whether another tile pass follows one that left `now` survivors (the largest set's) of `before`: while the list is
+// longer than one tile, the last pass at least halved it and fewer than kNdMaxRounds passes have run.
+inline bool nd_another_round(int rounds_done, int64_t before, int64_t now) {
+  return rounds_done < kNdMaxRounds && now > kNdTile && 2 * now <= before;
+}
+// Workgroups per set of the final pass over at most M survivors (at least one: an empty set still writes its count).
+inline int64_t nd_final_blocks(int64_t M) { return M < 1 ? 1 : (M + kNdTile - 1) / kNdTile; }
 // check_box_list over every list of a host (box_off[S], 2k) list whose offsets passed check_hvi_paths.
 int check_box_lists(std::string* err, int k, int S, int C, const int32_t* box_off, const uint16_t* boxes);
 // Candidates per pass of the fused chain under an omb_plan_hvi_paths plan (the default of OMB_DEBUG_HVI_PATHS_CHUNK):

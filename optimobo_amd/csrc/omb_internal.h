@@ -177,6 +177,20 @@ hipError_t launch_mes(hipStream_t stream, int k, const double* mu, const double*
 hipError_t launch_mes_grad(hipStream_t stream, int k, const double* mu, const double* var, int64_t ld, int64_t N,
                            const double* ystar, int S, double* dadm, double* dadv);
 
+// Non-dominated filter (omb_pareto.hip; omb_nondominated) over S point sets y[(j·S + s)·ld + i], 1 ≤ k ≤ OMB_MAX_OBJ.
+//   launch_nd_tile   one tile pass: in == nullptr runs over the points 0..N-1 themselves (Mmax = N), clears mask
+//                    bytes 0..N-1 of every row and drops the NaN rows; else over the in_cnt[s] ≤ Mmax indices of
+//                    in + s·in_pitch.  Survivors are appended to out + s·out_pitch (out_pitch ≥ Mmax) at slots taken
+//                    from out_cnt[s], which the caller zeroed.
+//   launch_nd_final  the cnt[s] ≤ Mmax survivors of list + s·pitch against one another: sets the mask bytes of those
+//                    nothing dominates, then count[s]; blockcnt holds S·nd_final_blocks(Mmax) ints.
+hipError_t launch_nd_tile(hipStream_t stream, int k, int S, const double* y, int64_t ld, int64_t N, const int32_t* in,
+                          int64_t in_pitch, const int32_t* in_cnt, int64_t Mmax, int32_t* out, int64_t out_pitch,
+                          int32_t* out_cnt, uint8_t* mask, int64_t ldm);
+hipError_t launch_nd_final(hipStream_t stream, int k, int S, const double* y, int64_t ld, const int32_t* list,
+                           int64_t pitch, const int32_t* cnt, int64_t Mmax, uint8_t* mask, int64_t ldm,
+                           int32_t* blockcnt, int64_t* count);
+
 // Deterministic arg-max; `partials` must hold kArgmaxMaxBlocks (val, idx) pairs followed by one zeroed ticket word
 // (one_pass: both passes in one launch, the last workgroup to arrive reducing; it leaves the word zeroed again).
 constexpr int kArgmaxMaxBlocks = 1024;

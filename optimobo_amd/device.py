@@ -301,6 +301,49 @@ class AcqContext:
                                                None if u is None else _ptr(u)), "omb_hvi_paths_con")
         return (out, u[:, :N]) if per_path else out
 
+    def nondominated(self, Y, S=1, out=None):
+        """omb_nondominated: the non-dominated points (minimisation) of S independent point sets — Y (k, N) with
+        S = 1 (the layout of ``posterior``'s mean) or (k, S, N) as ``paths_eval`` returns it (rows may be pitched) →
+        (mask (S, N) bool, counts (S,) int64), both on the device.  mask[s, i] is True when no point of set s
+        dominates point i and none of its coordinates is NaN; duplicates are all kept, −0.0 equals +0.0, ±inf are
+        ordinary values.  On NaN-free input it is ``pareto.nondominated_mask``, bit for bit.  ``out``: a uint8
+        (S, ldm ≥ N) tensor with unit column stride to take the mask (columns past N stay untouched).  The call
+        synchronises the stream (it reads the sieve's survivor counts to size its later passes)."""
+        if not isinstance(Y, torch.Tensor) or Y.dtype != torch.float64 or Y.device != self.device:
+            raise ValueError(f"nondominated: Y must be an fp64 tensor on {self.device}")
+        S = int(S)
+        if Y.dim() == 2 and S == 1:
+            Y = Y[:, None, :]
+        if Y.dim() != 3 or Y.shape[1] != S and S != 1:
+            raise ValueError(f"nondominated: Y {tuple(Y.shape)} is not (k, N) with S = 1 or (k, S, N)")
+        k, S, N = Y.shape
+        # row j·S + s at pitch ld: the set stride where there are several sets, else the coordinate stride
+        ld = Y.stride(1) if S > 1 else (Y.stride(0) if k > 1 else max(N, 1))
+        if N > 0 and ((N > 1 and Y.stride(2) != 1) or ld < N or (S > 1 and k > 1 and Y.stride(0) != S * ld)):
+            raise ValueError("nondominated: Y needs unit column stride and evenly pitched rows (row j·S + s at pitch ld)")
+        ld = max(int(ld), N, 1) if N == 0 else int(ld)
+        if out is None:
+            out = torch.empty((S, N), dtype=torch.uint8, device=self.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != self.device \
+                or out.dim() != 2 or out.shape[0] != S or out.shape[1] < N or (out.shape[1] > 1 and out.stride(1) != 1) \
+                or (S > 1 and out.stride(0) < N):
+            raise ValueError(f"nondominated: out must be a uint8 ({S}, ldm >= {N}) tensor on {self.device} with unit "
+                             "column stride")
+        ldm = out.stride(0) if S > 1 else max(out.shape[1], 1)
+        counts = torch.empty(S, dtype=torch.int64, device=self.device)
+        self._stream()
+        self._check(self.lib.omb_nondominated(self._h, k, S, _ptr(Y), int(ld), N, _ptr(out), int(ldm), _ptr(counts)),
+                    "omb_nondominated")
+        return out[:, :N].view(torch.bool), counts
+
+    def nondominated_stats(self):
+        """omb_nondominated_stats: the sieve of the last ``nondominated`` call → the largest set's survivors after
+        each of its tile passes (a list of 1 to 4 counts; empty before any call or after an empty one)."""
+        surv = (ctypes.c_int64 * 5)()
+        rounds = ctypes.c_int()
+        self._check(self.lib.omb_nondominated_stats(self._h, surv, ctypes.byref(rounds)), "omb_nondominated_stats")
+        return [int(v) for v in surv[:rounds.value]]
+
     def hvpoi(self, mu, var, cells, out=None):
         N = mu.shape[1]
         cells = _dev_f64(cells, self.device)

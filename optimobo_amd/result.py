@@ -5,6 +5,12 @@ import numpy as np
 class Res:
     """Outcome of ``solve()``: Pareto approximation, its inputs, the archive and the HV trace."""
 
+    # MultiSurrogateOptimiser(model_front=True): the model's Pareto set — inputs (P, n_var), posterior mean and
+    # variance (P, n_obj) of the non-dominated candidates (AcquisitionEngine.predicted_front); None otherwise
+    model_pf_inputs = None
+    model_pf_mean = None
+    model_pf_var = None
+
     def __init__(self, pf_approx, pf_inputs, ysample, Xsample, hypervolume_convergence, n_obj, n_init_samples):
         self.pf_approx = pf_approx
         self.pf_inputs = pf_inputs
