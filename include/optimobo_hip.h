@@ -696,7 +696,7 @@ int omb_gp_lml_grad(omb_ctx* ctx, int kernel, int n, int d, const double* X_dev,
  * optimisers.py:186): problem p has targets y_dev[p] (device pointer, n), lengthscales
  * lengthscale_host[p·d .. p·d + d − 1] and variance_host[p]; its results go to lml[p], grad_host[p·(d+1) ..],
  * jitter_used[p] (may be NULL) and status[p] (OMB_OK or OMB_ENOTPD, per problem: one non-positive-definite
- * problem does not fail the others).  Each problem's results are exactly omb_gp_lml_grad's: for n ≤ 96
+ * problem does not fail the others).  Each problem's results are exactly omb_gp_lml_grad's: for n ≤ 128
  * and n_var ≤ 8 they run as one launch (one workgroup each) and one synchronisation, otherwise one after
  * another through omb_gp_lml_grad.  Replaces GPy
  * model.optimize's per-objective evaluations (optimisers.py:231).  Returns OMB_OK unless an argument or the

@@ -2002,10 +2002,10 @@ static int gp_lml_grad_batch_impl(omb_ctx* ctx, int kernel, int k, int n, int d,
     if (!(noise_host[p] >= 0.0)) return fail(ctx, OMB_EINVAL, "noise must be >= 0");
   }
   const int DP = pad_dim(d);
-  // n ≤ 96, n_var ≤ 8: one launch.  (Batching up to the one-workgroup kernel's n ≤ 128 was 17% faster on
-  // config 1, but between n = 97 and 128 a single evaluation takes the blocked path, and on ill-conditioned
-  // K the two agree only to ~1e-7 in log p(y) — enough for the concurrent and sequential fits to reach
-  // different optima; every problem here gives exactly what omb_gp_lml_grad gives.)
+  // gp_lml_small_fits (n ≤ 128, n_var ≤ 8): one launch, a workgroup per problem.  The batch routes exactly as
+  // omb_gp_lml_grad does, so every problem gives bitwise what its own omb_gp_lml_grad gives (the concurrent and the
+  // sequential fits then walk the same L-BFGS-B path).  The one-workgroup and the blocked route do differ in the
+  // last digits; both are within what a LAPACK evaluation in fp64 achieves on ill-conditioned K.
   if (!gp_lml_small_fits(n, DP)) {
     // blocked path: the problems one after another, each exactly omb_gp_lml_grad
     for (int p = 0; p < k; ++p) {

@@ -118,8 +118,9 @@ def test_gp_fit_errors(ctx):
 @pytest.mark.parametrize("n", [40, 96, 97])
 def test_lml_grad_small_and_blocked_paths_agree_with_jitter(ctx, n):
     """Exact duplicate inputs with σ_f² = 1e10 (the 1e-8 jitter is below half an ulp of the diagonal)
-    make K + 1e-8·I singular in fp64: both the one-workgroup path (n ≤ 128) and the blocked path must
-    take GPy jitchol's jitter retries, and match the host evaluation at the jitter they report."""
+    make K + 1e-8·I singular in fp64: the evaluation must take GPy jitchol's jitter retries, and match the host
+    evaluation at the jitter it reports.  All three sizes take the one-workgroup route (gp_lml_small_fits:
+    n ≤ 128, n_var ≤ 8), with 3, 6 and 7 tiles; the name dates from a threshold of 96."""
     rng = np.random.default_rng(n)
     base = rng.uniform(0, 1, (6, 2))
     X = base[np.arange(n) % 6]
@@ -147,7 +148,8 @@ def test_lml_grad_small_path_deterministic(ctx):
 def test_concurrent_fits_match_sequential(n):
     """gp.fit_concurrently (the drivers' per-objective fits in lockstep, each round of evaluations one
     batched C call) gives bitwise the hyperparameters and predictions of fitting the same models one
-    after another (n ≤ 96: one launch per round; n = 119: the blocked path, problem after problem)."""
+    after another (all four sizes are within gp_lml_small_fits, n ≤ 128 and n_var ≤ 8: one launch per round, a
+    workgroup per fit)."""
     from optimobo_amd.gp import GPRegression, Matern52, fit_concurrently
     rng = np.random.default_rng(n)
     X = rng.uniform(-2, 2, (n, 2))
@@ -178,7 +180,8 @@ def test_concurrent_fits_match_sequential(n):
 @pytest.mark.parametrize("n,d", [(20, 2), (60, 3), (96, 8), (119, 2), (40, 12)])
 def test_lml_grad_batch_matches_single(ctx, n, d):
     """omb_gp_lml_grad_batch: every problem bitwise equal to its own omb_gp_lml_grad (one launch with a
-    workgroup per problem for n ≤ 96, n_var ≤ 8; the blocked path one problem after another)."""
+    workgroup per problem for n ≤ 128 and n_var ≤ 8, which (119, 2) is too; (40, 12): the blocked path, one problem
+    after another)."""
     rng = np.random.default_rng(n + d)
     X = torch.as_tensor(rng.uniform(0, 1, (n, d)), device="cuda:0")
     k = 3
