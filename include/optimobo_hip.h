@@ -140,7 +140,13 @@ const char* omb_last_error(const omb_ctx* ctx);
  * cosine is measured against (tools/paths_timing.py); values agree to the cosines' rounding.
  * omb_debug_set(ctx, OMB_DEBUG_HVI_PATHS_CHUNK, c) sets the candidates per pass of the fused chain under an
  * omb_plan_hvi_paths plan (default OMB_HVI_PATHS_CHUNK; 0: one pass over all N, whose workspace is the whole
- * (k·S, N) matrix of path values).  Values and arg-max pairs are bit-identical for every c. */
+ * (k·S, N) matrix of path values).  Values and arg-max pairs are bit-identical for every c.
+ * omb_debug_set(ctx, OMB_DEBUG_ARGMAX_PRUNE, m) picks how omb_eval_argmax[_sobol] runs under a reference-mode EHVI-2D
+ * plan with s00 > 0, s01 > 0 and a sorted non-dominated front, no constraint or log modifier, n_var ≤ 8 and
+ * n_train > 128: 1 (default) in two phases from 2^16 candidates on — the means of both objectives for every
+ * candidate, the full posterior and the acquisition for every 16th, an upper bound of the acquisition from the means
+ * for the rest, and the full posterior and the acquisition only for the candidates whose bound reaches the best value
+ * seen; 2 the same at any batch size; 0 the dense chain.  The arg-max pair is bit-identical. */
 enum {
   OMB_DEBUG_SPIN_LIMIT = 1,
   OMB_DEBUG_COV_TABLE = 2,
@@ -155,7 +161,8 @@ enum {
   OMB_DEBUG_POSTERIOR_ALL_VAR = 12,
   OMB_DEBUG_POSTERIOR_MEAN_KERNEL = 13,
   OMB_DEBUG_PATHS_LIBCOS = 14,
-  OMB_DEBUG_HVI_PATHS_CHUNK = 15
+  OMB_DEBUG_HVI_PATHS_CHUNK = 15,
+  OMB_DEBUG_ARGMAX_PRUNE = 16
 };
 int omb_debug_set(omb_ctx* ctx, int what, int64_t value);
 
@@ -345,6 +352,11 @@ int omb_nondominated(omb_ctx* ctx, int k, int S, const double* y_dev, int64_t ld
  * most 4) and survivors_host[r] (5 entries; those past *rounds_host are 0) the largest set's survivors after pass r —
  * what the final pass then tested against itself is the last of them.  Host values; nothing is launched. */
 int omb_nondominated_stats(omb_ctx* ctx, int64_t* survivors_host, int* rounds_host);
+/* The last omb_eval_argmax[_sobol] call on this context (OMB_DEBUG_ARGMAX_PRUNE): stats_host[0] = 1 if it took the
+ * two-phase path, 0 if the dense chain; [1] the candidates of its seed sample; [2] the candidates past the seed
+ * whose bound kept them.  [2] is stored by the call's kernels: it is that call's once its result has been waited
+ * for.  All 0 after a dense call.  Host values; nothing is launched and nothing is waited for. */
+int omb_argmax_prune_stats(omb_ctx* ctx, int64_t* stats_host);
 
 /* Hypervolume-based PoI of EMO (emo.py:176-228): cells_dev (C, 2, 2) [upper, lower]. */
 int omb_hvpoi(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,

@@ -757,4 +757,228 @@ hipError_t launch_pof_scale(hipStream_t stream, int c, const double* mu, const d
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------ EHVI-2D arg-max: pruning by a bound
+// DESIGN §29.  In OMB_EHVI_REFERENCE the value is Σ_i p2_i·G_i with σA = σ²₀·s00, σB = σ²₀·s01 (s01 > 0),
+//     p2_i = ψ(y2_i, y2_i, μ₁, σB) = E[(y2_i − Y)⁺] ≥ 0,                 increasing in σB ≥ 0,
+//     G_i  = ψ(a, a, μ₀, σA) − ψ(b, b, μ₀, σA) = E[clip(a − Y, 0, a − b)],  a = y1[i−1] ≥ b = y1[i],
+// and ψ(x, x, μ, σ) = σφ(t) + (x − μ)Φ(t), t = (x − μ)/σ, increases in σ from (x − μ)⁺ at σ = 0.  So over
+// σ²₀ ∈ [0, σ_f²] (the posterior kernels store σ_f² − Σ of squares: never above σ_f²)
+//     value ≤ UB = Σ_i ψ(y2_i, y2_i, μ₁, σ_f²·s01) · [ψ(a, a, μ₀, σ_f²·s00) − (b − μ₀)⁺],
+// from the means alone.  A candidate is dropped only if UB·(1 + 1e-9) + tiny < τ holds, τ the best value of the seed
+// sample (> 0); tiny = 64·2⁻⁵²·Σ_i p2ub_i·(|a − μ₀| + |b − μ₀| + σ_f²·s00) + 1e-300 bounds the rounding of the exact
+// kernel's own sum (each stripe a dozen rounded operations on terms of that size).  A NaN on either side compares
+// false and keeps the candidate; so does τ ≤ 0.  Strict "<": a candidate tied with τ stays.
+
+// One allocation: the pairs, τ, the counts, the two lists, the per-workgroup counts and the flags, 16-byte aligned each.
+static int64_t prune_ws_layout(char* base, int64_t N, PruneWs* ws) {
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) {
+    const int64_t o = off;
+    off += (bytes + 15) / 16 * 16;
+    return base ? base + o : nullptr;
+  };
+  ws->partials = reinterpret_cast<double*>(take(sizeof(double) * 2 * 2 * kArgmaxMaxBlocks));
+  ws->tau = reinterpret_cast<double*>(take(sizeof(double) * 2));
+  ws->counts = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * 4));
+  ws->seed_idx = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * ((N + kPruneStride - 1) / kPruneStride)));
+  ws->surv_idx = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * N));
+  ws->block_cnt = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * ((N + kPruneBlock - 1) / kPruneBlock)));
+  ws->keep = reinterpret_cast<uint8_t*>(take(N));
+  ws->stats_host = nullptr;
+  return off;
+}
+
+int64_t prune_ws_bytes(int64_t N) {
+  PruneWs ws;
+  return prune_ws_layout(nullptr, N, &ws);
+}
+
+void prune_ws_carve(void* base, int64_t N, PruneWs* ws) { prune_ws_layout(static_cast<char*>(base), N, ws); }
+
+__global__ __launch_bounds__(256) void prune_seed_kernel(int64_t ns, int32_t* __restrict__ seed_idx,
+                                                         int32_t* __restrict__ counts) {
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < ns; j += (int64_t)gridDim.x * blockDim.x)
+    seed_idx[j] = (int32_t)(j * kPruneStride);
+  if (blockIdx.x == 0 && threadIdx.x == 0) counts[0] = (int32_t)ns;
+}
+
+hipError_t launch_prune_seed(hipStream_t stream, int64_t N, const PruneWs& ws) {
+  const int64_t ns = (N + kPruneStride - 1) / kPruneStride;
+  hipLaunchKernelGGL(prune_seed_kernel, dim3(acq_grid(ns)), dim3(256), 0, stream, ns, ws.seed_idx, ws.counts);
+  return hipGetLastError();
+}
+
+// One lane per listed candidate (ehvi2d_point<1>: the value does not depend on the lane count), grid-stride over the
+// device-side count; every workgroup writes its pair, {−∞, −1} where it saw nothing comparable.
+__global__ __launch_bounds__(kAcqThreads) void ehvi2d_argmax_list_kernel(
+    const double* __restrict__ mu0_c, const double* __restrict__ var0_c, const double* __restrict__ mu1,
+    const int32_t* __restrict__ idx, const int32_t* __restrict__ count, int64_t cap, const double* __restrict__ pf,
+    int P, double r0, double r1, double s00, double s01, int mode, double* __restrict__ partials) {
+  extern __shared__ double sm[];
+  double* y1 = sm;
+  double* y2 = sm + P + 1;
+  __shared__ double red_v[kAcqThreads / 64];
+  __shared__ long long red_i[kAcqThreads / 64];
+  for (int i = threadIdx.x; i < P; i += blockDim.x) {
+    y1[i + 1] = pf[2 * i];
+    y2[i] = pf[2 * i + 1];
+  }
+  if (threadIdx.x == 0) y1[0] = r0;
+  __syncthreads();
+  const int64_t n = min((int64_t)*count, cap);
+  double bv = -__builtin_inf();
+  long long bi = -1;
+  for (int64_t p = (int64_t)blockIdx.x * kAcqThreads + threadIdx.x; p < n; p += (int64_t)gridDim.x * kAcqThreads) {
+    const long long c = idx[p];
+    const double v = ehvi2d_point<1>(mu0_c[p], mu1[c], var0_c[p], 0.0, y1, y2, P, r1, s00, s01, mode, 0);
+    if (v == v && v > -__builtin_inf() && argmax_better(v, c, bv, bi)) {
+      bv = v;
+      bi = c;
+    }
+  }
+  argmax_wave_block(bv, bi, red_v, red_i);
+  if (threadIdx.x == 0) {
+    partials[2 * blockIdx.x] = bv;
+    partials[2 * blockIdx.x + 1] = __builtin_bit_cast(double, bi);
+  }
+}
+
+int prune_list_blocks(int64_t cap) {
+  const int64_t b = (cap + kAcqThreads - 1) / kAcqThreads;
+  return (int)(b < 1 ? 1 : (b > kArgmaxMaxBlocks ? kArgmaxMaxBlocks : b));
+}
+
+hipError_t launch_ehvi2d_argmax_list(hipStream_t stream, const double* mu0_c, const double* var0_c, const double* mu1,
+                                     const int32_t* idx, const int32_t* count, int64_t cap, const double* pf, int P,
+                                     double r0, double r1, double s00, double s01, int mode, double* partials) {
+  if (mode != OMB_EHVI_REFERENCE) return hipErrorInvalidValue;   // σ²₁ is not gathered
+  const size_t shm = sizeof(double) * (2 * P + 1);
+  hipLaunchKernelGGL(ehvi2d_argmax_list_kernel, dim3(prune_list_blocks(cap)), dim3(kAcqThreads), shm, stream, mu0_c,
+                     var0_c, mu1, idx, count, cap, pf, P, r0, r1, s00, s01, mode, partials);
+  return hipGetLastError();
+}
+
+// The keep flag of candidates blockIdx.x·kPruneBlock + threadIdx.x (seed candidates: 0, they are evaluated already)
+// and the workgroup's count of them.
+__global__ __launch_bounds__(kPruneBlock) void prune_bound_kernel(const double* __restrict__ mu0,
+                                                                  const double* __restrict__ mu1, int64_t N,
+                                                                  const double* __restrict__ pf, int P, double r0,
+                                                                  double sA, double sB, const double* __restrict__ tau,
+                                                                  uint8_t* __restrict__ keep,
+                                                                  int32_t* __restrict__ block_cnt) {
+#pragma clang fp contract(off)
+  extern __shared__ double sm[];
+  double* y1 = sm;
+  double* y2 = sm + P + 1;
+  __shared__ int wave_cnt[kPruneBlock / 64];
+  for (int i = threadIdx.x; i < P; i += blockDim.x) {
+    y1[i + 1] = pf[2 * i];
+    y2[i] = pf[2 * i + 1];
+  }
+  if (threadIdx.x == 0) y1[0] = r0;
+  __syncthreads();
+  const int64_t c = (int64_t)blockIdx.x * kPruneBlock + threadIdx.x;
+  const double t = tau[0];
+  bool k = false;
+  if (c < N && (c % kPruneStride) != 0) {
+    k = true;
+    if (t > 0.0) {
+      const double m0 = mu0[c], m1 = mu1[c];
+      const double iA = 1.0 / sA, iB = 1.0 / sB;
+      double ub = 0.0, scale = 0.0;
+      double da = y1[0] - m0;
+      double ta = da * iA;
+      double psi_a = sA * npdf_fast(ta) + da * ndtr_fast(ta);       // ψ(a, a, μ₀, σ_f²·s00)
+      for (int i = 1; i <= P; ++i) {
+        const double db = y1[i] - m0, dy = y2[i - 1] - m1;
+        const double g = fmax(psi_a - fmax(db, 0.0), 0.0);
+        const double u = dy * iB;
+        const double p2 = fmax(sB * npdf_fast(u) + dy * ndtr_fast(u), 0.0);   // ψ(y2_i, y2_i, μ₁, σ_f²·s01)
+        ub += p2 * g;
+        scale += p2 * (fabs(da) + fabs(db) + sA);
+        da = db;
+        ta = da * iA;
+        psi_a = sA * npdf_fast(ta) + da * ndtr_fast(ta);
+      }
+      const double tiny = 64.0 * 0x1p-52 * scale + 1e-300;
+      if (ub * (1.0 + 1e-9) + tiny < t) k = false;
+    }
+  }
+  if (c < N) keep[c] = k ? 1 : 0;
+  const int nw = __popcll(__ballot(k));
+  if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = nw;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int s = 0;
+    for (int w = 0; w < kPruneBlock / 64; ++w) s += wave_cnt[w];
+    block_cnt[blockIdx.x] = s;
+  }
+}
+
+// block_cnt → its exclusive prefix sums in place, the total to counts[1] and (a system-scope store to pinned host
+// memory, as the fault word's) to *stats_host.  One workgroup; nb ≤ 2^23.
+__global__ __launch_bounds__(1024) void prune_scan_kernel(int32_t* __restrict__ block_cnt, int nb,
+                                                          int32_t* __restrict__ counts, int64_t* stats_host) {
+  __shared__ int buf[1024];
+  __shared__ int carry;
+  if (threadIdx.x == 0) carry = 0;
+  __syncthreads();
+  for (int base = 0; base < nb; base += 1024) {
+    const int i = base + threadIdx.x;
+    const int v = i < nb ? block_cnt[i] : 0;
+    buf[threadIdx.x] = v;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+      const int a = threadIdx.x >= off ? buf[threadIdx.x - off] : 0;
+      __syncthreads();
+      buf[threadIdx.x] += a;
+      __syncthreads();
+    }
+    const int c0 = carry;
+    if (i < nb) block_cnt[i] = c0 + buf[threadIdx.x] - v;
+    __syncthreads();
+    if (threadIdx.x == 1023) carry = c0 + buf[1023];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    counts[1] = carry;
+    if (stats_host)
+      __hip_atomic_store(reinterpret_cast<long long*>(stats_host), (long long)carry, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+// The kept candidates of workgroup b, in ascending order, to surv_idx[block_off[b] ..].
+__global__ __launch_bounds__(kPruneBlock) void prune_compact_kernel(const uint8_t* __restrict__ keep, int64_t N,
+                                                                    const int32_t* __restrict__ block_off,
+                                                                    int32_t* __restrict__ surv_idx) {
+  __shared__ int wave_cnt[kPruneBlock / 64];
+  const int64_t c = (int64_t)blockIdx.x * kPruneBlock + threadIdx.x;
+  const bool k = c < N && keep[c] != 0;
+  const unsigned long long b = __ballot(k);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) wave_cnt[wave] = __popcll(b);
+  __syncthreads();
+  int pos = block_off[blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));
+  for (int w = 0; w < wave; ++w) pos += wave_cnt[w];
+  if (k) surv_idx[pos] = (int32_t)c;
+}
+
+hipError_t launch_prune_bound(hipStream_t stream, const double* mu0, const double* mu1, int64_t N, const double* pf,
+                              int P, double r0, double s00, double s01, double sf2, const PruneWs& ws) {
+  const int64_t nb = (N + kPruneBlock - 1) / kPruneBlock;
+  if (N < 1 || nb > (1 << 23)) return hipErrorInvalidValue;
+  const size_t shm = sizeof(double) * (2 * P + 1);
+  hipLaunchKernelGGL(prune_bound_kernel, dim3((unsigned)nb), dim3(kPruneBlock), shm, stream, mu0, mu1, N, pf, P, r0,
+                     sf2 * s00, sf2 * s01, ws.tau, ws.keep, ws.block_cnt);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(1024), 0, stream, ws.block_cnt, (int)nb, ws.counts,
+                     ws.stats_host);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(prune_compact_kernel, dim3((unsigned)nb), dim3(kPruneBlock), 0, stream, ws.keep, N, ws.block_cnt,
+                     ws.surv_idx);
+  return hipGetLastError();
+}
+
 }  // namespace omb

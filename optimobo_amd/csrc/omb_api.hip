@@ -1,6 +1,7 @@
 // C-ABI of liboptimobo_hip.so (declared in include/optimobo_hip.h): context, GP state,
 // argument validation and dispatch to the kernels.  No exception crosses this boundary.
 #include <math.h>
+#include <cmath>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -67,6 +68,9 @@ struct Plan {
   // omb_plan_log: the value is the logarithm of the acquisition (PLAN_EI plain / constrained, PLAN_EHVI_BOXES), and the
   // constraints' weight is added as log F.  var_mask is the linear plan's.
   bool log = false;
+  // omb_plan_ehvi2d: the arg-max chain may prune by the upper bound of DESIGN §29 — OMB_EHVI_REFERENCE, s00 > 0,
+  // s01 > 0, every number finite and the stripes' f1 non-increasing from r0 (a sorted non-dominated front)
+  bool prune_ok = false;
 };
 
 // A device buffer that the context owns and grow_dev enlarges on demand.
@@ -116,6 +120,13 @@ struct omb_ctx {
   DevBuf pws;    // omb_paths_min: the first launch's per-workgroup (value, index) pairs
   DevBuf nws;    // omb_nondominated: slot counters | final-pass counts | the first survivor list (S, N)
   DevBuf nws2;   // omb_nondominated: the second survivor list (S, survivors of the first pass)
+  DevBuf prws;   // the arg-max chain's two-phase path: lists, flags, counts and pairs (PruneWs)
+  // omb_argmax_prune_stats: whether the last arg-max chain took the two-phase path, its seed sample, and the survivor
+  // count its scan kernel stores (pinned, device-mapped)
+  int prune_taken = 0;
+  int64_t prune_seed = 0;
+  int64_t* prune_stats_host = nullptr;
+  int64_t* prune_stats_dev = nullptr;
   int nd_rounds = 0;                              // omb_nondominated_stats: the last call's tile passes
   int64_t nd_survivors[kNdMaxRounds + 1] = {};    // and the largest set's survivors after each
   // device fault word (pinned, mapped host memory): kernels mark it, enter() reports it
@@ -142,6 +153,7 @@ struct omb_ctx {
   int hvi_paths_chunk = (int)kHviPathsChunk;   // OMB_DEBUG_HVI_PATHS_CHUNK: candidates per pass of a sampled-front chain
   int posterior_all_var = 0;     // OMB_DEBUG_POSTERIOR_ALL_VAR: the chain computes σ² of every objective
   int posterior_mean_kernel = kMeanKernelAfter;   // OMB_DEBUG_POSTERIOR_MEAN_KERNEL: masked objectives' μ in a launch of its own
+  int argmax_prune = 1;          // OMB_DEBUG_ARGMAX_PRUNE: 0 dense, 1 two-phase from kPruneMinN candidates, 2 always
 };
 
 namespace {
@@ -554,6 +566,12 @@ int chain_paths(omb_ctx* ctx, const Plan& pl, PathArgs* pa) {
   return OMB_OK;
 }
 
+// Batch sizes of the arg-max chain's two-phase path.  Below 2^16 candidates the dense step is a sixteenth of config
+// 3's or less (0.34 ms at n_train 512) and the path's nine extra launches are a tenth of that or more; the lists hold
+// 32-bit indices.
+constexpr int64_t kPruneMinN = 1 << 16;
+constexpr int64_t kPruneMaxN = 1ll << 30;
+
 // The fused chain: [Sobol →] posterior(0..k-1) → planned acquisition → [arg-max].  Under a sampled-front plan
 // (PLAN_HVI_PATHS) the posterior stage is the evaluation of the installed sample paths, in passes of Nc candidates.  The posterior computes σ² of the
 // objectives in the plan's var_mask only (the others' slots of the workspace keep whatever they held); all_var (the
@@ -602,6 +620,18 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
     const int64_t wsd = wsa > wsb ? wsa : wsb;
     if (wsd && (rc = grow_dev(ctx, ctx->hws, sizeof(double) * (size_t)wsd, "HVI path workspace"))) return rc;
   }
+  // The two-phase arg-max where the plan has a bound, nothing comes between the acquisition and the
+  // arg-max, posterior_mean_kernel and a ring kernel exist for the shape, and the batch is large enough for the
+  // launches it adds (kPruneMinN; OMB_DEBUG_ARGMAX_PRUNE 2: any size).  Everything else keeps the dense chain.
+  const bool two_phase = result_dev && !vals_out && !acq_raw && !all_var && !ctx->posterior_all_var && !paths &&
+                         pl.kind == PLAN_EHVI2D && pl.prune_ok && pl.n_con == 0 && !pl.log && k == 2 &&
+                         posterior_gather_fits(args, max_R) && N >= 1 && N <= kPruneMaxN &&
+                         (ctx->argmax_prune == 2 || (ctx->argmax_prune == 1 && N >= kPruneMinN));
+  if (two_phase && (rc = grow_dev(ctx, ctx->prws, (size_t)prune_ws_bytes(N), "arg-max pruning workspace"))) return rc;
+  if (result_dev) {
+    ctx->prune_taken = two_phase ? 1 : 0;
+    ctx->prune_seed = two_phase ? (N + kPruneStride - 1) / kPruneStride : 0;
+  }
   double* mu = ctx->work.as<double>();
   double* var = mu + (size_t)K * nd;
   double* vals = vals_out ? vals_out : mu + head;
@@ -649,11 +679,42 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
       if (e == hipSuccess && (rc = run_hvi_paths(ctx, pl, mu, nc, nc, vals + c0, "fused chain (hvi_paths)"))) return rc;
     }
     if (e == hipSuccess && N == 0) e = mark(2);
+  } else if (two_phase) {
+    // both means for all N, the full posterior and the acquisition for the seed sample, the bound for the
+    // rest against the seed's best value, then the full posterior and the acquisition for the survivors alone; the
+    // arg-max over both sets of pairs compares original indices, so the pair is the dense chain's.  All on the stream,
+    // the counts stay on the device.
+    PruneWs ws;
+    prune_ws_carve(ctx->prws.p, N, &ws);
+    ws.stats_host = ctx->prune_stats_dev;
+    const int64_t ns = (N + kPruneStride - 1) / kPruneStride, nv = N - ns;
+    const int nbs = prune_list_blocks(ns), nbv = nv > 0 ? prune_list_blocks(nv) : 0;
+    double* mu_c = var;                 // the workspace's σ² rows: the gathered launches' compacted μ₀ | σ²₀
+    double* var_c = var + nd;
+    const double sf2 = args.gp[0].variance;
+    if (e == hipSuccess) e = launch_posterior_means(ctx->stream, args, 3u, Xc, N, mu);
+    if (e == hipSuccess) e = launch_prune_seed(ctx->stream, N, ws);
+    if (e == hipSuccess)
+      e = launch_posterior_gather(ctx->stream, args, max_R, Xc, ws.seed_idx, ws.counts, ns, mu_c, var_c);
+    if (e == hipSuccess)
+      e = launch_ehvi2d_argmax_list(ctx->stream, mu_c, var_c, mu + nd, ws.seed_idx, ws.counts, ns, pl.geo, pl.P,
+                                    pl.r[0], pl.r[1], pl.s00, pl.s01, pl.mode, ws.partials);
+    if (e == hipSuccess) e = launch_argmax_reduce(ctx->stream, ws.partials, nbs, 0, ws.tau);
+    if (e == hipSuccess)
+      e = launch_prune_bound(ctx->stream, mu, mu + nd, N, pl.geo, pl.P, pl.r[0], pl.s00, pl.s01, sf2, ws);
+    if (e == hipSuccess && nv > 0)
+      e = launch_posterior_gather(ctx->stream, args, max_R, Xc, ws.surv_idx, ws.counts + 1, nv, mu_c, var_c);
+    if (e == hipSuccess) e = mark(2);
+    if (e == hipSuccess && nv > 0)
+      e = launch_ehvi2d_argmax_list(ctx->stream, mu_c, var_c, mu + nd, ws.surv_idx, ws.counts + 1, nv, pl.geo, pl.P,
+                                    pl.r[0], pl.r[1], pl.s00, pl.s01, pl.mode, ws.partials + 2 * nbs);
+    if (e == hipSuccess) e = mark(3);
+    if (e == hipSuccess) e = launch_argmax_reduce(ctx->stream, ws.partials, nbs + nbv, offset, result_dev);
   } else if (e == hipSuccess && N > 0) {
     e = posterior_any(ctx, args, Ld, K, max_R, Xc, N, mu, var);
   }
-  if (e == hipSuccess && !paths) e = mark(2);
-  if (e == hipSuccess && N > 0 && !paths) {
+  if (e == hipSuccess && !paths && !two_phase) e = mark(2);
+  if (e == hipSuccess && N > 0 && !paths && !two_phase) {
     if (acq_argmax) {
       unsigned* ticket = ctx->fused_chain == 1 ? reinterpret_cast<unsigned*>(ctx->partials + 2 * kArgmaxMaxBlocks)
                                                : nullptr;
@@ -666,8 +727,8 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
       e = (pl.log ? launch_log_pof : launch_pof_scale)(ctx->stream, pl.n_con, mu + (size_t)k * nd,
                                                        var + (size_t)k * nd, N, N, pl.con_eps, acq, vals);
   }
-  if (e == hipSuccess) e = mark(3);
-  if (e == hipSuccess && result_dev && !acq_argmax)
+  if (e == hipSuccess && !two_phase) e = mark(3);
+  if (e == hipSuccess && result_dev && !acq_argmax && !two_phase)
     e = launch_argmax(ctx->stream, vals, N, offset, ctx->partials, result_dev, ctx->argmax_one_pass);
   if (e == hipSuccess) e = mark(4);
   if (e != hipSuccess) return hip_fail(ctx, e, "fused chain");
@@ -700,11 +761,16 @@ int omb_create(int device, omb_ctx** out) {
       hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->fault_dev), ctx->fault_host, 0) != hipSuccess ||
       hipHostMalloc(&ctx->fit_host, sizeof(double) * (OMB_MAX_DIM + 8), hipHostMallocMapped | hipHostMallocCoherent) !=
           hipSuccess ||
-      hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->fit_dev), ctx->fit_host, 0) != hipSuccess) {
+      hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->fit_dev), ctx->fit_host, 0) != hipSuccess ||
+      hipHostMalloc(&ctx->prune_stats_host, sizeof(int64_t) * 2, hipHostMallocMapped | hipHostMallocCoherent) !=
+          hipSuccess ||
+      hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->prune_stats_dev), ctx->prune_stats_host, 0) !=
+          hipSuccess) {
     omb_destroy(ctx);
     return OMB_ENOMEM;
   }
   *ctx->fault_host = 0;
+  ctx->prune_stats_host[0] = 0;
   ctx->stream = ctx->own_stream;
   *out = ctx;
   return OMB_OK;
@@ -723,12 +789,13 @@ int omb_destroy(omb_ctx* ctx) {
   if (ctx->result_host) (void)hipHostFree(ctx->result_host);
   if (ctx->info_host) (void)hipHostFree(ctx->info_host);
   for (DevBuf* b : {&ctx->geo, &ctx->work, &ctx->tws, &ctx->ichol, &ctx->sws, &ctx->ews, &ctx->fws, &ctx->dws, &ctx->gws,
-                    &ctx->aws, &ctx->hws, &ctx->pws, &ctx->nws, &ctx->nws2})
+                    &ctx->aws, &ctx->hws, &ctx->pws, &ctx->nws, &ctx->nws2, &ctx->prws})
     if (b->p) (void)hipFree(b->p);
   if (ctx->stage) (void)hipHostFree(ctx->stage);
   if (ctx->sob) (void)hipFree(ctx->sob);
   if (ctx->fault_host) (void)hipHostFree(ctx->fault_host);
   if (ctx->fit_host) (void)hipHostFree(ctx->fit_host);
+  if (ctx->prune_stats_host) (void)hipHostFree(ctx->prune_stats_host);
   for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   delete ctx;
@@ -777,6 +844,8 @@ static const DebugSwitch kDebugSwitches[] = {
     {OMB_DEBUG_HVI_PATHS_CHUNK, &omb_ctx::hvi_paths_chunk, 0, 0x7fffffff,
      "sampled-front chain chunk %lld outside [0, 2^31) (0: one pass)"},
     {OMB_DEBUG_POSTERIOR_ALL_VAR, &omb_ctx::posterior_all_var, 0, 1, nullptr},
+    {OMB_DEBUG_ARGMAX_PRUNE, &omb_ctx::argmax_prune, 0, 2,
+     "arg-max pruning %lld (0 dense, 1 two-phase for large batches, 2 two-phase at any size)"},
 };
 
 int omb_debug_set(omb_ctx* ctx, int what, int64_t value) {
@@ -1181,6 +1250,15 @@ int omb_nondominated_stats(omb_ctx* ctx, int64_t* survivors_host, int* rounds_ho
   return OMB_OK;
 }
 
+int omb_argmax_prune_stats(omb_ctx* ctx, int64_t* stats_host) {
+  if (!ctx) return OMB_EINVAL;
+  if (!stats_host) return fail(ctx, OMB_EINVAL, "null output");
+  stats_host[0] = ctx->prune_taken;
+  stats_host[1] = ctx->prune_seed;
+  stats_host[2] = ctx->prune_taken ? __atomic_load_n(ctx->prune_stats_host, __ATOMIC_ACQUIRE) : 0;
+  return OMB_OK;
+}
+
 int omb_hvpoi(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
               const double* cells_dev, int C, double* out_dev) {
   int rc = enter(ctx);
@@ -1293,6 +1371,16 @@ int omb_plan_ehvi2d(omb_ctx* ctx, const double* pf_sorted_host, int P, const dou
   Plan pl;
   if ((rc = describe_ehvi2d(ctx, P, r_host, s00, s01, mode, &pl))) return rc;
   if (!pf_sorted_host) return fail(ctx, OMB_EINVAL, "null Pareto front");
+  // the arg-max chain's bound holds for a = y1[i−1] ≥ b = y1[i] and σB ≥ 0 only
+  bool ok = mode == OMB_EHVI_REFERENCE && s00 > 0.0 && s01 > 0.0 && std::isfinite(s00) && std::isfinite(s01) &&
+            std::isfinite(r_host[0]);
+  double prev = r_host[0];
+  for (int i = 0; ok && i < P; ++i) {
+    const double f1 = pf_sorted_host[2 * i], f2 = pf_sorted_host[2 * i + 1];
+    ok = std::isfinite(f1) && std::isfinite(f2) && f1 <= prev;
+    prev = f1;
+  }
+  pl.prune_ok = ok;
   return install_plan(ctx, pl, pf_sorted_host, sizeof(double) * 2 * (size_t)P);
 }
 

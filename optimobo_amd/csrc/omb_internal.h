@@ -45,6 +45,11 @@ struct GPArgs {
   // non-zero: the launch covers the objectives whose bits are set and blockIdx.y counts them in ascending order (set
   // by launch_posterior where it gives the masked objectives' μ a launch of its own); 0: objective blockIdx.y
   unsigned obj_sel;
+  // non-null (launch_posterior_gather only): the launch covers candidates idx[0 .. *count − 1] of Xc and writes μ, σ²
+  // compacted (slot p of the list at p, pitch N = the list's capacity); workgroups past *count exit at once.  null: the
+  // identity, candidates 0..N-1 (every other launch)
+  const int32_t* idx;
+  const int32_t* count;
 };
 
 // launch_posterior's mean_kernel argument (OMB_DEBUG_POSTERIOR_MEAN_KERNEL): μ of the objectives in var_skip by
@@ -69,6 +74,48 @@ hipError_t launch_kernel_block(hipStream_t stream, const GPArgs& args, int obj, 
 
 hipError_t launch_posterior(hipStream_t stream, const GPArgs& args, int n_obj, int max_R, const double* Xc,
                             int64_t N, double* mu, double* var, int mean_kernel = kMeanKernelAfter);
+
+// The arg-max chain's two-phase path (run_chain).
+//   launch_posterior_means   μ of the objectives in `objs` (bits) for all N candidates by posterior_mean_kernel
+//                            (n_var ≤ 8, n_train > 128: posterior_gather_fits), rows o·N of mu; the ring kernels' bits
+//   launch_posterior_gather  μ, σ² of objective 0 alone for the candidates idx[0 .. *count − 1] (device list and count,
+//                            count ≤ cap) by the ring instantiation max_R picks for a dense launch, written compacted
+//                            to mu_c / var_c (cap each)
+bool posterior_gather_fits(const GPArgs& args, int max_R);
+hipError_t launch_posterior_means(hipStream_t stream, const GPArgs& args, unsigned objs, const double* Xc, int64_t N,
+                                  double* mu);
+hipError_t launch_posterior_gather(hipStream_t stream, const GPArgs& args, int max_R, const double* Xc,
+                                   const int32_t* idx, const int32_t* count, int64_t cap, double* mu_c, double* var_c);
+
+// Pruning of the EHVI-2D arg-max in OMB_EHVI_REFERENCE (omb_acquisition.hip).  A list is int32 indices into the batch
+// with a device-side count; "seed" is the strided sample 0, kPruneStride, 2·kPruneStride, ….
+constexpr int kPruneStride = 16;
+constexpr int kPruneBlock = 256;   // candidates per workgroup of the bound / compaction kernels
+struct PruneWs {
+  int32_t* seed_idx;     // ⌈N/kPruneStride⌉
+  int32_t* surv_idx;     // N
+  int32_t* counts;       // [0] seed count, [1] survivor count
+  int32_t* block_cnt;    // ⌈N/kPruneBlock⌉ survivors per workgroup, then (in place) their exclusive prefix sums
+  uint8_t* keep;         // N flags
+  double* partials;      // 2 × kArgmaxMaxBlocks (value, index) pairs: the seed's, then the survivors'
+  double* tau;           // {τ, its index}: the seed sample's arg-max
+  int64_t* stats_host;   // pinned, device-mapped: [0] the survivor count of the last call (a system-scope store)
+};
+int64_t prune_ws_bytes(int64_t N);
+void prune_ws_carve(void* base, int64_t N, PruneWs* ws);
+// seed_idx and counts[0]
+hipError_t launch_prune_seed(hipStream_t stream, int64_t N, const PruneWs& ws);
+// EHVI-2D (ehvi2d_point: the dense kernels' bits) of the candidates idx[0 .. *count − 1] — μ₀ and σ²₀ compacted (slot
+// p), μ₁ at mu1[idx[p]] — and their arg-max by original index into `partials` (prune_list_blocks(cap) pairs, all
+// written)
+int prune_list_blocks(int64_t cap);
+hipError_t launch_ehvi2d_argmax_list(hipStream_t stream, const double* mu0_c, const double* var0_c, const double* mu1,
+                                     const int32_t* idx, const int32_t* count, int64_t cap, const double* pf, int P,
+                                     double r0, double r1, double s00, double s01, int mode, double* partials);
+// keep flags of the non-seed candidates from the upper bound of the acquisition over σ²₀ ∈ [0, sf2] against *tau, the
+// ordered compaction of the kept indices into surv_idx, counts[1] and *stats_host
+hipError_t launch_prune_bound(hipStream_t stream, const double* mu0, const double* mu1, int64_t N, const double* pf,
+                              int P, double r0, double s00, double s01, double sf2, const PruneWs& ws);
 
 // EHVI-2D and the arg-max in one launch (omb_acquisition.hip): each workgroup's (value, index) pair goes to
 // `partials` (2 doubles per workgroup, ehvi2d_argmax_blocks(N) ≤ kArgmaxMaxBlocks); the last workgroup to finish (an

@@ -748,10 +748,26 @@ __device__ __forceinline__ void generate_tile(const GPDev& g, const ExpCoef& ec,
       [&](int, int k, int kofs) { return load_row_val<DP, KIND, ABL>(rs.al, g.alpha, lane, k, kofs); }, sink);
 }
 
-template <int RT, int CT, int DP, int KIND, int NW = 8, int ABL = 0, int WPE = NW / 4>
+// GATHER (launch_posterior_gather, an instantiation of its own so that the dense launches keep their code): the
+// workgroup's candidates are Xc rows args.idx[c0 .. c0 + BN − 1] of a device-side list of *args.count entries, its μ
+// and σ² go to slots c0.. (N is the list's capacity and the outputs' pitch), and a workgroup past the count leaves
+// before it touches LDS.  A candidate's values do not depend on its place in a workgroup, so they are the dense
+// launch's bits.
+template <int RT, int CT, int DP, int KIND, int NW = 8, int ABL = 0, int WPE = NW / 4, bool GATHER = false>
 __global__ __launch_bounds__(64 * NW, WPE) void posterior_kernel(GPArgs args, const double* __restrict__ Xc,
                                                                      int64_t N, double* __restrict__ mu_out,
                                                                      double* __restrict__ var_out) {
+  int64_t n_cand = N;   // candidates of the launch: the clamp of the loads and the guard of the stores
+  if constexpr (GATHER) {
+    n_cand = min((int64_t)*args.count, N);
+    if ((int64_t)blockIdx.x * (16 * CT) >= n_cand) return;
+  }
+  // row of Xc of the launch's candidate c (clamped to the last one)
+  auto cand_row = [&](int64_t c) -> int64_t {
+    const int64_t cc = min(c, n_cand - 1);
+    if constexpr (GATHER) return (int64_t)args.idx[cc];
+    return cc;
+  };
   constexpr int NT = 64 * NW;                 // threads per workgroup
   constexpr int G = NW / 4;                   // waves sharing one SIMD
   constexpr int BN = 16 * CT;                 // candidates per workgroup
@@ -791,14 +807,14 @@ __global__ __launch_bounds__(64 * NW, WPE) void posterior_kernel(GPArgs args, co
   if constexpr (kCandLds) {
     for (int e = tid; e < DP * BN; e += NT) {
       const int j = e / BN, c = e % BN;
-      const int64_t cc = min(c0 + c, N - 1);
+      const int64_t cc = cand_row(c0 + c);
       cand[e] = (j < d) ? Xc[cc * d + j] / g.ls[j] : 0.0;
     }
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < DP; ++j) csq += cand[j * BN + cg] * cand[j * BN + cg];
   } else {
-    const int64_t ci = min(c0 + cg, N - 1);
+    const int64_t ci = cand_row(c0 + cg);
 #pragma unroll
     for (int j = 0; j < DP; ++j) {
       b[j] = (j < d) ? Xc[ci * d + j] / g.ls[j] : 0.0;
@@ -822,7 +838,7 @@ __global__ __launch_bounds__(64 * NW, WPE) void posterior_kernel(GPArgs args, co
   double bfr[kMfmaGen ? KSD : 1];
   double csq_m = 0.0;
   if constexpr (kMfmaGen) {
-    const int64_t ci = min(c0 + 16 * mg_ct + (lane & 15), N - 1);
+    const int64_t ci = cand_row(c0 + 16 * mg_ct + (lane & 15));
     auto coord = [&](int j) -> double {
       if constexpr (kCandLds) return cand[j * BN + 16 * mg_ct + (lane & 15)];
       return (j < d) ? Xc[ci * d + j] / g.ls[j] : 0.0;
@@ -1098,7 +1114,7 @@ __global__ __launch_bounds__(64 * NW, WPE) void posterior_kernel(GPArgs args, co
         double m = 0.0;
         for (int w = tid >> 4; w < NW; w += CT) m += redmu[w * 16 + (tid & 15)];
         const int64_t c = c0 + tid;
-        if (c < N) mu_out[(int64_t)obj * N + c] = m;
+        if (c < n_cand) mu_out[(int64_t)obj * N + c] = m;
       }
       return;
     }
@@ -1210,7 +1226,7 @@ __global__ __launch_bounds__(64 * NW, WPE) void posterior_kernel(GPArgs args, co
       for (int t = tid; t < NT; t += BN) m += redmu[t];
     }
     const int64_t c = c0 + tid;
-    if (c < N) {
+    if (c < n_cand) {
       mu_out[(int64_t)obj * N + c] = m;
       var_out[(int64_t)obj * N + c] = g.variance - s;
     }
@@ -1968,6 +1984,79 @@ hipError_t launch_posterior(hipStream_t stream, const GPArgs& args_in, int n_obj
   if (args.gp[0].kind == OMB_KERNEL_RBF)
     return launch_posterior_kind<OMB_KERNEL_RBF>(stream, args, n_obj, max_R, Xc, N, mu, var, mean_kernel);
   return launch_posterior_kind<OMB_KERNEL_MATERN52>(stream, args, n_obj, max_R, Xc, N, mu, var, mean_kernel);
+}
+
+// ----------------------------------------------------------------------------- the arg-max chain's two-phase path
+// The shapes where posterior_mean_kernel exists and launch_posterior_dp runs a ring kernel: n_var ≤ 8, n_train > 128.
+bool posterior_gather_fits(const GPArgs& args, int max_R) {
+  const int RTneed = ((max_R + 3) / 4 + 1) / 2;
+  return args.DP <= 8 && RTneed > 1 && RTneed <= 8 && 16 * max_R <= OMB_MAX_TRAIN;
+}
+
+template <int DP, int KIND>
+static hipError_t launch_posterior_gather_dp(hipStream_t stream, const GPArgs& args, int max_R, const double* Xc,
+                                             int64_t cap, double* mu_c, double* var_c) {
+  // the instantiation launch_posterior_dp picks for max_R, with the list in front of the candidates; the grid covers
+  // the list's capacity, and the workgroups past its device-side count exit
+  const int RTneed = ((max_R + 3) / 4 + 1) / 2;
+  const dim3 grid((unsigned)((cap + 31) / 32), 1);
+  if (RTneed <= 2)
+    hipLaunchKernelGGL((posterior_kernel<2, 2, DP, KIND, 8, 0, 6, true>), grid, dim3(kBlockThreads), 0, stream, args, Xc,
+                       cap, mu_c, var_c);
+  else if (RTneed <= 4)
+    hipLaunchKernelGGL((posterior_kernel<4, 2, DP, KIND, 8, 0, 4, true>), grid, dim3(kBlockThreads), 0, stream, args, Xc,
+                       cap, mu_c, var_c);
+  else
+    hipLaunchKernelGGL((posterior_kernel<8, 2, DP, KIND, 8, 0, 2, true>), grid, dim3(kBlockThreads), 0, stream, args, Xc,
+                       cap, mu_c, var_c);
+  return hipGetLastError();
+}
+
+template <int KIND>
+static hipError_t launch_posterior_two_phase(hipStream_t stream, const GPArgs& args, int max_R, unsigned objs,
+                                             const double* Xc, int64_t N, double* mu, double* var) {
+  // objs != 0: the means of those objectives over all N; else the gathered ring launch (N the capacity)
+  switch (args.DP) {
+    case 2:
+      return objs ? launch_posterior_mean<2, KIND>(stream, args, objs, Xc, N, mu)
+                  : launch_posterior_gather_dp<2, KIND>(stream, args, max_R, Xc, N, mu, var);
+    case 4:
+      return objs ? launch_posterior_mean<4, KIND>(stream, args, objs, Xc, N, mu)
+                  : launch_posterior_gather_dp<4, KIND>(stream, args, max_R, Xc, N, mu, var);
+    case 6:
+      return objs ? launch_posterior_mean<6, KIND>(stream, args, objs, Xc, N, mu)
+                  : launch_posterior_gather_dp<6, KIND>(stream, args, max_R, Xc, N, mu, var);
+    case 8:
+      return objs ? launch_posterior_mean<8, KIND>(stream, args, objs, Xc, N, mu)
+                  : launch_posterior_gather_dp<8, KIND>(stream, args, max_R, Xc, N, mu, var);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t launch_posterior_means(hipStream_t stream, const GPArgs& args_in, unsigned objs, const double* Xc, int64_t N,
+                                  double* mu) {
+  if (objs == 0) return hipErrorInvalidValue;
+  GPArgs args = args_in;
+  args.ec = exp_coef();
+  args.idx = nullptr;
+  args.count = nullptr;
+  if (args.gp[0].kind == OMB_KERNEL_RBF)
+    return launch_posterior_two_phase<OMB_KERNEL_RBF>(stream, args, 0, objs, Xc, N, mu, nullptr);
+  return launch_posterior_two_phase<OMB_KERNEL_MATERN52>(stream, args, 0, objs, Xc, N, mu, nullptr);
+}
+
+hipError_t launch_posterior_gather(hipStream_t stream, const GPArgs& args_in, int max_R, const double* Xc,
+                                   const int32_t* idx, const int32_t* count, int64_t cap, double* mu_c, double* var_c) {
+  if (!posterior_gather_fits(args_in, max_R) || !idx || !count || cap < 1) return hipErrorInvalidValue;
+  GPArgs args = args_in;
+  args.ec = exp_coef();
+  args.var_skip = 0;
+  args.obj_sel = 1u;   // objective 0 alone: blockIdx.y = 0
+  args.idx = idx;
+  args.count = count;
+  if (args.gp[0].kind == OMB_KERNEL_RBF)
+    return launch_posterior_two_phase<OMB_KERNEL_RBF>(stream, args, max_R, 0, Xc, cap, mu_c, var_c);
+  return launch_posterior_two_phase<OMB_KERNEL_MATERN52>(stream, args, max_R, 0, Xc, cap, mu_c, var_c);
 }
 
 template <int KIND>

@@ -100,7 +100,9 @@ class AcqContext:
         of its own after it (default) / in that kernel before it (bit-identical values); ("paths_libcos", 0/1)
         evaluates the sample paths' features with the kernel's own cosine (default) / the device library's;
         ("hvi_paths_chunk", c) evaluates a ``plan_hvi_paths`` chain in passes of c candidates (default
-        ``_lib.HVI_PATHS_CHUNK``; 0: one pass; bit-identical values)."""
+        ``_lib.HVI_PATHS_CHUNK``; 0: one pass; bit-identical values); ("argmax_prune", 0/1/2) runs the arg-max chain
+        of a reference-mode EHVI-2D plan densely / in two phases from 2^16 candidates on (default) / in two phases
+        at any size (bit-identical pair; see ``argmax_prune_stats``)."""
         code = getattr(_lib, "DEBUG_" + str(what).upper(), None)
         if code is None:
             raise KeyError(what)
@@ -343,6 +345,15 @@ class AcqContext:
         rounds = ctypes.c_int()
         self._check(self.lib.omb_nondominated_stats(self._h, surv, ctypes.byref(rounds)), "omb_nondominated_stats")
         return [int(v) for v in surv[:rounds.value]]
+
+    def argmax_prune_stats(self):
+        """omb_argmax_prune_stats: the last ``eval_argmax`` / ``eval_argmax_sobol`` call → (two_phase, seed,
+        survivors): whether it took the two-phase path, the candidates of its seed sample and those past the seed
+        that its bound kept (the call's own once its result has been waited for).  (False, 0, 0) after a dense
+        call."""
+        st = (ctypes.c_int64 * 3)()
+        self._check(self.lib.omb_argmax_prune_stats(self._h, st), "omb_argmax_prune_stats")
+        return bool(st[0]), int(st[1]), int(st[2])
 
     def hvpoi(self, mu, var, cells, out=None):
         N = mu.shape[1]
