@@ -146,7 +146,12 @@ const char* omb_last_error(const omb_ctx* ctx);
  * n_train > 128: 1 (default) in two phases from 2^16 candidates on — the means of both objectives for every
  * candidate, the full posterior and the acquisition for every 16th, an upper bound of the acquisition from the means
  * for the rest, and the full posterior and the acquisition only for the candidates whose bound reaches the best value
- * seen; 2 the same at any batch size; 0 the dense chain.  The arg-max pair is bit-identical. */
+ * seen; 2 the same at any batch size; 0 the dense chain.  The arg-max pair is bit-identical.
+ * omb_debug_set(ctx, OMB_DEBUG_ARGMAX_SCREEN, m) picks where that two-phase path takes the means its bound reads: 1
+ * (default) from omb_posterior_screen's fp32-transform means with their margins folded into the bound as intervals, the
+ * fp64 mean of objective 1 then computed only for the seed sample and the survivors; 0 from fp64 means of both
+ * objectives for every candidate (for a model so ill-conditioned that the margins keep everything).  The arg-max pair
+ * is bit-identical: only the fp64 kernels' values reach it. */
 enum {
   OMB_DEBUG_SPIN_LIMIT = 1,
   OMB_DEBUG_COV_TABLE = 2,
@@ -162,7 +167,8 @@ enum {
   OMB_DEBUG_POSTERIOR_MEAN_KERNEL = 13,
   OMB_DEBUG_PATHS_LIBCOS = 14,
   OMB_DEBUG_HVI_PATHS_CHUNK = 15,
-  OMB_DEBUG_ARGMAX_PRUNE = 16
+  OMB_DEBUG_ARGMAX_PRUNE = 16,
+  OMB_DEBUG_ARGMAX_SCREEN = 17
 };
 int omb_debug_set(omb_ctx* ctx, int what, int64_t value);
 
@@ -188,6 +194,14 @@ int omb_kernel_block(omb_ctx* ctx, int obj, const double* Xc_dev, int64_t N, dou
  * an FP64-MFMA GEMM V = L^-1 K* and a column reduction. */
 int omb_posterior(omb_ctx* ctx, int n_obj, const double* Xc_dev, int64_t N, double* mu_dev,
                   double* var_dev);
+
+/* Screened posterior mean of objectives 0..n_obj-1 at N candidates (n_var ≤ 8): mu_out_dev (n_obj, N) is μ̃, the mean
+ * with the kernel transform of the fp64 squared distance evaluated in fp32 (native square root and exponential) and
+ * summed in fp64 against the fp64 woodbury vector; eps_out_dev (n_obj, N) is a rigorous margin, |μ̃ − μ| ≤ ε against
+ * omb_posterior's μ, finite and positive for finite inputs.  About half the cost of the fp64 mean; the arg-max chain's
+ * two-phase path prunes with it (OMB_DEBUG_ARGMAX_SCREEN). */
+int omb_posterior_screen(omb_ctx* ctx, const double* Xc_dev, int64_t N, int n_obj, double* mu_out_dev,
+                          double* eps_out_dev);
 
 /* EHVI for 2 objectives (util_functions.py:136-167 + EHVI_2D_aux :81-128).
  *   pf_sorted_dev (P, 2): Pareto front sorted by f2 ascending (util_functions.py:98)

@@ -769,7 +769,8 @@ hipError_t launch_pof_scale(hipStream_t stream, int c, const double* mu, const d
 // kernel's own sum (each stripe a dozen rounded operations on terms of that size).  A NaN on either side compares
 // false and keeps the candidate; so does τ ≤ 0.  Strict "<": a candidate tied with τ stays.
 
-// One allocation: the pairs, τ, the counts, the two lists, the per-workgroup counts and the flags, 16-byte aligned each.
+// One allocation: the pairs, τ, the counts, the two lists, the per-workgroup counts, the flags and the screen's μ̃ and ε
+// rows, 16-byte aligned each.
 static int64_t prune_ws_layout(char* base, int64_t N, PruneWs* ws) {
   int64_t off = 0;
   auto take = [&](int64_t bytes) {
@@ -784,6 +785,8 @@ static int64_t prune_ws_layout(char* base, int64_t N, PruneWs* ws) {
   ws->surv_idx = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * N));
   ws->block_cnt = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * ((N + kPruneBlock - 1) / kPruneBlock)));
   ws->keep = reinterpret_cast<uint8_t*>(take(N));
+  ws->scr_mu = reinterpret_cast<double*>(take(sizeof(double) * 2 * N));
+  ws->scr_eps = reinterpret_cast<double*>(take(sizeof(double) * 2 * N));
   ws->stats_host = nullptr;
   return off;
 }
@@ -860,8 +863,16 @@ hipError_t launch_ehvi2d_argmax_list(hipStream_t stream, const double* mu0_c, co
 
 // The keep flag of candidates blockIdx.x·kPruneBlock + threadIdx.x (seed candidates: 0, they are evaluated already)
 // and the workgroup's count of them.
+// INTERVAL: the means are known to ±ε only, μ₀ ∈ [μ̃₀ − ε₀, μ̃₀ + ε₀], μ₁ ∈ [μ̃₁ − ε₁, μ̃₁ + ε₁].
+// ψ(x, x, μ, σ) decreases in μ and −(b − μ)⁺ increases in μ, so each factor takes the end that makes it largest:
+//     UB = Σ_i ψ(y2_i, y2_i, μ̃₁ − ε₁, σ_f²·s01) · max(ψ(a, a, μ̃₀ − ε₀, σ_f²·s00) − (b − μ̃₀ − ε₀)⁺, 0),
+// and tiny is taken with |a − μ̃₀| + ε₀ and |b − μ̃₀| + ε₀.  A NaN or an infinity in μ̃ or ε makes UB NaN or +∞ and
+// keeps the candidate.  The plain instantiation is the same arithmetic with ε = 0.
+template <bool INTERVAL>
 __global__ __launch_bounds__(kPruneBlock) void prune_bound_kernel(const double* __restrict__ mu0,
-                                                                  const double* __restrict__ mu1, int64_t N,
+                                                                  const double* __restrict__ mu1,
+                                                                  const double* __restrict__ eps0,
+                                                                  const double* __restrict__ eps1, int64_t N,
                                                                   const double* __restrict__ pf, int P, double r0,
                                                                   double sA, double sB, const double* __restrict__ tau,
                                                                   uint8_t* __restrict__ keep,
@@ -883,7 +894,13 @@ __global__ __launch_bounds__(kPruneBlock) void prune_bound_kernel(const double* 
   if (c < N && (c % kPruneStride) != 0) {
     k = true;
     if (t > 0.0) {
-      const double m0 = mu0[c], m1 = mu1[c];
+      double m0 = mu0[c], m1 = mu1[c];   // the low ends μ̃ − ε under INTERVAL
+      double e0 = 0.0;
+      if constexpr (INTERVAL) {
+        e0 = eps0[c];
+        m0 -= e0;
+        m1 -= eps1[c];
+      }
       const double iA = 1.0 / sA, iB = 1.0 / sB;
       double ub = 0.0, scale = 0.0;
       double da = y1[0] - m0;
@@ -891,11 +908,12 @@ __global__ __launch_bounds__(kPruneBlock) void prune_bound_kernel(const double* 
       double psi_a = sA * npdf_fast(ta) + da * ndtr_fast(ta);       // ψ(a, a, μ₀, σ_f²·s00)
       for (int i = 1; i <= P; ++i) {
         const double db = y1[i] - m0, dy = y2[i - 1] - m1;
-        const double g = fmax(psi_a - fmax(db, 0.0), 0.0);
+        // (b − μ̃₀ − ε₀)⁺ = (db − 2ε₀)⁺; |a − μ̃₀| + ε₀ ≤ |da| + 2ε₀, and so for b
+        const double g = fmax(psi_a - fmax(INTERVAL ? db - 2.0 * e0 : db, 0.0), 0.0);
         const double u = dy * iB;
         const double p2 = fmax(sB * npdf_fast(u) + dy * ndtr_fast(u), 0.0);   // ψ(y2_i, y2_i, μ₁, σ_f²·s01)
         ub += p2 * g;
-        scale += p2 * (fabs(da) + fabs(db) + sA);
+        scale += p2 * (INTERVAL ? fabs(da) + fabs(db) + 4.0 * e0 + sA : fabs(da) + fabs(db) + sA);
         da = db;
         ta = da * iA;
         psi_a = sA * npdf_fast(ta) + da * ndtr_fast(ta);
@@ -965,12 +983,17 @@ __global__ __launch_bounds__(kPruneBlock) void prune_compact_kernel(const uint8_
 }
 
 hipError_t launch_prune_bound(hipStream_t stream, const double* mu0, const double* mu1, int64_t N, const double* pf,
-                              int P, double r0, double s00, double s01, double sf2, const PruneWs& ws) {
+                              int P, double r0, double s00, double s01, double sf2, const PruneWs& ws,
+                              const double* eps0, const double* eps1) {
   const int64_t nb = (N + kPruneBlock - 1) / kPruneBlock;
-  if (N < 1 || nb > (1 << 23)) return hipErrorInvalidValue;
+  if (N < 1 || nb > (1 << 23) || !eps0 != !eps1) return hipErrorInvalidValue;
   const size_t shm = sizeof(double) * (2 * P + 1);
-  hipLaunchKernelGGL(prune_bound_kernel, dim3((unsigned)nb), dim3(kPruneBlock), shm, stream, mu0, mu1, N, pf, P, r0,
-                     sf2 * s00, sf2 * s01, ws.tau, ws.keep, ws.block_cnt);
+  if (eps0)
+    hipLaunchKernelGGL(prune_bound_kernel<true>, dim3((unsigned)nb), dim3(kPruneBlock), shm, stream, mu0, mu1, eps0,
+                       eps1, N, pf, P, r0, sf2 * s00, sf2 * s01, ws.tau, ws.keep, ws.block_cnt);
+  else
+    hipLaunchKernelGGL(prune_bound_kernel<false>, dim3((unsigned)nb), dim3(kPruneBlock), shm, stream, mu0, mu1, eps0,
+                       eps1, N, pf, P, r0, sf2 * s00, sf2 * s01, ws.tau, ws.keep, ws.block_cnt);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(1024), 0, stream, ws.block_cnt, (int)nb, ws.counts,

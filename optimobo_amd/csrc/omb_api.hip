@@ -154,6 +154,7 @@ struct omb_ctx {
   int posterior_all_var = 0;     // OMB_DEBUG_POSTERIOR_ALL_VAR: the chain computes σ² of every objective
   int posterior_mean_kernel = kMeanKernelAfter;   // OMB_DEBUG_POSTERIOR_MEAN_KERNEL: masked objectives' μ in a launch of its own
   int argmax_prune = 1;          // OMB_DEBUG_ARGMAX_PRUNE: 0 dense, 1 two-phase from kPruneMinN candidates, 2 always
+  int argmax_screen = 1;         // OMB_DEBUG_ARGMAX_SCREEN: the two-phase path's bound from 1 the fp32 screen, 0 fp64 means
 };
 
 namespace {
@@ -692,18 +693,30 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
     double* mu_c = var;                 // the workspace's σ² rows: the gathered launches' compacted μ₀ | σ²₀
     double* var_c = var + nd;
     const double sf2 = args.gp[0].variance;
-    if (e == hipSuccess) e = launch_posterior_means(ctx->stream, args, 3u, Xc, N, mu);
+    // DESIGN §30 (OMB_DEBUG_ARGMAX_SCREEN 1): no dense fp64 mean pass.  The bound reads the screen's μ̃ ± ε; μ₁ of the
+    // seed and of the survivors comes from the gathered mean launch, at the candidates' original slots, where the list
+    // EHVI reads it.  0: the fp64 means of §29 for all N.
+    const bool screen = ctx->argmax_screen != 0;
+    if (e == hipSuccess && !screen) e = launch_posterior_means(ctx->stream, args, 3u, Xc, N, mu);
     if (e == hipSuccess) e = launch_prune_seed(ctx->stream, N, ws);
     if (e == hipSuccess)
       e = launch_posterior_gather(ctx->stream, args, max_R, Xc, ws.seed_idx, ws.counts, ns, mu_c, var_c);
+    if (e == hipSuccess && screen)
+      e = launch_posterior_mean_gather(ctx->stream, args, 1, Xc, ws.seed_idx, ws.counts, ns, mu + nd);
     if (e == hipSuccess)
       e = launch_ehvi2d_argmax_list(ctx->stream, mu_c, var_c, mu + nd, ws.seed_idx, ws.counts, ns, pl.geo, pl.P,
                                     pl.r[0], pl.r[1], pl.s00, pl.s01, pl.mode, ws.partials);
     if (e == hipSuccess) e = launch_argmax_reduce(ctx->stream, ws.partials, nbs, 0, ws.tau);
-    if (e == hipSuccess)
+    if (e == hipSuccess && screen) e = launch_posterior_screen(ctx->stream, args, 3u, Xc, N, ws.scr_mu, ws.scr_eps);
+    if (e == hipSuccess && screen)
+      e = launch_prune_bound(ctx->stream, ws.scr_mu, ws.scr_mu + nd, N, pl.geo, pl.P, pl.r[0], pl.s00, pl.s01, sf2, ws,
+                             ws.scr_eps, ws.scr_eps + nd);
+    if (e == hipSuccess && !screen)
       e = launch_prune_bound(ctx->stream, mu, mu + nd, N, pl.geo, pl.P, pl.r[0], pl.s00, pl.s01, sf2, ws);
     if (e == hipSuccess && nv > 0)
       e = launch_posterior_gather(ctx->stream, args, max_R, Xc, ws.surv_idx, ws.counts + 1, nv, mu_c, var_c);
+    if (e == hipSuccess && nv > 0 && screen)
+      e = launch_posterior_mean_gather(ctx->stream, args, 1, Xc, ws.surv_idx, ws.counts + 1, nv, mu + nd);
     if (e == hipSuccess) e = mark(2);
     if (e == hipSuccess && nv > 0)
       e = launch_ehvi2d_argmax_list(ctx->stream, mu_c, var_c, mu + nd, ws.surv_idx, ws.counts + 1, nv, pl.geo, pl.P,
@@ -846,6 +859,7 @@ static const DebugSwitch kDebugSwitches[] = {
     {OMB_DEBUG_POSTERIOR_ALL_VAR, &omb_ctx::posterior_all_var, 0, 1, nullptr},
     {OMB_DEBUG_ARGMAX_PRUNE, &omb_ctx::argmax_prune, 0, 2,
      "arg-max pruning %lld (0 dense, 1 two-phase for large batches, 2 two-phase at any size)"},
+    {OMB_DEBUG_ARGMAX_SCREEN, &omb_ctx::argmax_screen, 0, 1, nullptr},
 };
 
 int omb_debug_set(omb_ctx* ctx, int what, int64_t value) {
@@ -1050,6 +1064,23 @@ int omb_posterior(omb_ctx* ctx, int n_obj, const double* Xc_dev, int64_t N, doub
   gather_Ld(ctx, n_obj, Ld);
   hipError_t e = posterior_any(ctx, args, Ld, n_obj, max_R, Xc_dev, N, mu_dev, var_dev);
   if (e != hipSuccess) return hip_fail(ctx, e, "posterior");
+  return OMB_OK;
+}
+
+int omb_posterior_screen(omb_ctx* ctx, const double* Xc_dev, int64_t N, int n_obj, double* mu_out_dev,
+                          double* eps_out_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (N < 0 || (N > 0 && (!Xc_dev || !mu_out_dev || !eps_out_dev)))
+    return fail(ctx, OMB_EINVAL, "bad candidate/output arguments");
+  GPArgs args;
+  int max_R = 0;
+  if ((rc = gather_gp(ctx, n_obj, &args, &max_R))) return rc;
+  if (args.DP > 8) return fail(ctx, OMB_EUNSUP, "the screened mean needs n_var <= 8 (n_var=%d)", args.d);
+  if (N == 0) return OMB_OK;
+  if ((N + 15) / 16 > 0x7fffffffLL) return fail(ctx, OMB_EUNSUP, "N=%lld too large", (long long)N);
+  hipError_t e = launch_posterior_screen(ctx->stream, args, all_objectives(n_obj), Xc_dev, N, mu_out_dev, eps_out_dev);
+  if (e != hipSuccess) return hip_fail(ctx, e, "posterior_screen");
   return OMB_OK;
 }
 

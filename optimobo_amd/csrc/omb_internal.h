@@ -86,6 +86,16 @@ hipError_t launch_posterior_means(hipStream_t stream, const GPArgs& args, unsign
                                   double* mu);
 hipError_t launch_posterior_gather(hipStream_t stream, const GPArgs& args, int max_R, const double* Xc,
                                    const int32_t* idx, const int32_t* count, int64_t cap, double* mu_c, double* var_c);
+// The screened path, n_var ≤ 8.
+//   launch_posterior_mean_gather  μ of objective `obj` for the listed candidates by posterior_mean_kernel's gathered
+//                                 instantiation, to mu_row[idx[p]] (the objective's own row: original slots), the
+//                                 dense launch's bits
+//   launch_posterior_screen       μ̃ (fp32 transform of the fp64 r², fp64 sum) and a margin ε ≥ |μ̃ − μ| of the
+//                                 objectives in `objs` for all N candidates, rows o·N of mu and eps
+hipError_t launch_posterior_mean_gather(hipStream_t stream, const GPArgs& args, int obj, const double* Xc,
+                                        const int32_t* idx, const int32_t* count, int64_t cap, double* mu_row);
+hipError_t launch_posterior_screen(hipStream_t stream, const GPArgs& args, unsigned objs, const double* Xc, int64_t N,
+                                   double* mu, double* eps);
 
 // Pruning of the EHVI-2D arg-max in OMB_EHVI_REFERENCE (omb_acquisition.hip).  A list is int32 indices into the batch
 // with a device-side count; "seed" is the strided sample 0, kPruneStride, 2·kPruneStride, ….
@@ -97,6 +107,8 @@ struct PruneWs {
   int32_t* counts;       // [0] seed count, [1] survivor count
   int32_t* block_cnt;    // ⌈N/kPruneBlock⌉ survivors per workgroup, then (in place) their exclusive prefix sums
   uint8_t* keep;         // N flags
+  double* scr_mu;        // (2, N) the screen's μ̃
+  double* scr_eps;       // (2, N) its margins ε
   double* partials;      // 2 × kArgmaxMaxBlocks (value, index) pairs: the seed's, then the survivors'
   double* tau;           // {τ, its index}: the seed sample's arg-max
   int64_t* stats_host;   // pinned, device-mapped: [0] the survivor count of the last call (a system-scope store)
@@ -114,8 +126,11 @@ hipError_t launch_ehvi2d_argmax_list(hipStream_t stream, const double* mu0_c, co
                                      double r0, double r1, double s00, double s01, int mode, double* partials);
 // keep flags of the non-seed candidates from the upper bound of the acquisition over σ²₀ ∈ [0, sf2] against *tau, the
 // ordered compaction of the kept indices into surv_idx, counts[1] and *stats_host
+// eps0 / eps1 non-null: the interval form — mu0, mu1 are known to ±eps0, ±eps1 and every factor of the
+// bound is taken at the end of its interval that makes it largest
 hipError_t launch_prune_bound(hipStream_t stream, const double* mu0, const double* mu1, int64_t N, const double* pf,
-                              int P, double r0, double s00, double s01, double sf2, const PruneWs& ws);
+                              int P, double r0, double s00, double s01, double sf2, const PruneWs& ws,
+                              const double* eps0 = nullptr, const double* eps1 = nullptr);
 
 // EHVI-2D and the arg-max in one launch (omb_acquisition.hip): each workgroup's (value, index) pair goes to
 // `partials` (2 doubles per workgroup, ehvi2d_argmax_blocks(N) ≤ kArgmaxMaxBlocks); the last workgroup to finish (an

@@ -1252,11 +1252,16 @@ __global__ __launch_bounds__(64 * NW, WPE) void posterior_kernel(GPArgs args, co
 // Four waves per workgroup (one per SIMD).  The register budget is that of 4 waves per SIMD — with the next tile's
 // operands in flight that is enough to keep the FP64 pipe fed — and of 3 at n_var 7, 8, whose three k-steps
 // of fragments, held twice, spilled at 128 VGPRs.
+// GATHER (launch_posterior_mean_gather, an instantiation of its own as posterior_kernel's): the columns are 16 entries
+// each of the device-side list args.idx[0 .. *args.count − 1] (N is the list's capacity), one objective per launch,
+// and μ goes to the candidate's *original* slot mu_out[idx] (mu_out is the objective's own row).  A wave past the
+// count leaves.  A candidate's value does not depend on its column, so it has the dense launch's bits.
 constexpr int kMeanWaves = 4;
-template <int DP, int KIND>
+template <int DP, int KIND, bool GATHER = false>
 __global__ __launch_bounds__(64 * kMeanWaves, DP == 8 ? 3 : 4) void posterior_mean_kernel(
     GPArgs args, const double* __restrict__ Xc, int64_t N, double* __restrict__ mu_out) {
   static_assert(DP <= 8, "the candidates' B fragments live in registers");
+  if constexpr (GATHER) N = min((int64_t)*args.count, N);
   using GS = GenShape<DP, KIND, 0>;
   constexpr int KSD = GS::KSD;
   __shared__ double etab[GS::kTabN];
@@ -1285,7 +1290,8 @@ __global__ __launch_bounds__(64 * kMeanWaves, DP == 8 ? 3 : 4) void posterior_me
     lsl[s] = g.ls[jl[s]];
   }
   auto load_raw = [&](int64_t c, double (&x)[KSD]) {
-    const int64_t ci = min(16 * c + (lane & 15), N - 1);
+    int64_t ci = min(16 * c + (lane & 15), N - 1);
+    if constexpr (GATHER) ci = args.idx[ci];
 #pragma unroll
     for (int s = 0; s < KSD; ++s) x[s] = Xc[ci * d + jl[s]];
   };
@@ -1342,7 +1348,154 @@ __global__ __launch_bounds__(64 * kMeanWaves, DP == 8 ? 3 : 4) void posterior_me
       m += s;
     }
     const int64_t c = 16 * col + lane;
-    if (lane < 16 && c < N) mu_out[(int64_t)obj * N + c] = m;
+    if constexpr (GATHER) {
+      if (lane < 16 && c < N) mu_out[args.idx[c]] = m;
+    } else {
+      if (lane < 16 && c < N) mu_out[(int64_t)obj * N + c] = m;
+    }
+  }
+}
+
+// ----------------------------------------------------------------------------- posterior mean, screened in fp32
+// μ̃ ≈ μ with a rigorous margin ε ≥ |μ̃ − μ| per candidate: what the arg-max chain's bound needs of the
+// 99.7 % of the candidates it throws away.  The structure is posterior_mean_kernel's (a wave per column of 16
+// candidates, grid-stride, the next column's and the next tile's operands in flight, no LDS, no barrier) and r² has
+// compute_tile's bits: the same fp64 fragments through the same MFMA k-steps, the same clamp.  It is then rounded once
+// to fp32 and the transform runs on the native fp32 square root and exponential:
+//     Matern 5/2   f̃ = (1 + √5 r̃ + (5/3) s̃)·2^(−√5·log₂e·r̃),  s̃ = fl32(r²), r̃ = √s̃       w = 9 + 11 r̃
+//     RBF          f̃ = 2^(−(log₂e/2)·s̃)                                                  w = 2.25 + 1.625 s̃
+// with |f̃ − f| ≤ 2⁻²⁴·f̃·w (§30 derives w term by term), or ≤ 2⁻¹⁰⁷ where the exponential was flushed.  μ̃ is summed in
+// fp64 against the fp64 α (the terms cancel: an fp32 sum's error would be n·2⁻²⁴·Σ|α_k k_k|), the margin sum
+// S = Σ_k |α_k|·(f̃_k·w_k + 2⁻⁶⁰) in fp32, and ε = 2⁻²⁴(1 + 2⁻¹⁰)·σ_f²·S + 2⁻⁶⁴·σ_f²: the factor covers S's own
+// rounding (n·2⁻²⁴), the 2⁻⁶⁰ the flushed values, the last term the rows whose |α_k|·2⁻⁶⁰ is itself flushed.
+//
+// The clamp: s̃ = min(fl32(|r²|), 160000) has the bits of fl32(r2_clamp(r²)) for every r² — rounding is monotone, 160000
+// is an fp32 number, and the clamp's + 10⁻³⁰⁰ changes r² only below 10⁻²⁸⁴, where fl32 gives 0 either way (a NaN
+// gives 160000 in both) — for one fp32 instruction and a source modifier instead of two fp64 instructions.
+// The tile's four values go through the transform stage by stage, a scheduling barrier after each, so that the square
+// roots and exponentials of one tile issue back to back instead of each waiting for its own chain (left to itself the
+// compiler runs the four chains one after the other: 81 VGPRs against 71, 0.667 against 0.656 ms at config 3).
+template <int KIND>
+__device__ __forceinline__ void screen_tile(const d4& cr, const double (&al)[4], double& acc, float& S) {
+  auto stage = [] { __builtin_amdgcn_sched_barrier(0); };
+  float s[4], f[4], w[4];
+  constexpr float kMax = KIND == OMB_KERNEL_MATERN52 ? (float)kMaternR2Max : (float)kRbfR2Max;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) s[i] = __builtin_fminf((float)fabs(cr[i]), kMax);
+  stage();
+  if constexpr (KIND == OMB_KERNEL_MATERN52) {
+    float r[4], e[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = __builtin_amdgcn_sqrtf(s[i]);
+    stage();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) e[i] = __builtin_amdgcn_exp2f(-(3.2259642f * r[i]));   // √5·log₂e
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      f[i] = __builtin_fmaf(s[i], 1.6666666f, __builtin_fmaf(r[i], 2.236068f, 1.0f));
+      w[i] = __builtin_fmaf(r[i], 11.0f, 9.0f);
+    }
+    stage();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f[i] *= e[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      f[i] = __builtin_amdgcn_exp2f(-(0.72134752f * s[i]));                            // log₂e/2
+      w[i] = __builtin_fmaf(s[i], 1.625f, 2.25f);
+    }
+    stage();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    acc = fma(al[i], (double)f[i], acc);
+    S = __builtin_fmaf((float)fabs(al[i]), __builtin_fmaf(f[i], w[i], 0x1p-60f), S);
+  }
+}
+
+template <int DP, int KIND>
+__global__ __launch_bounds__(64 * kMeanWaves, DP == 8 ? 3 : 4) void posterior_screen_kernel(
+    GPArgs args, const double* __restrict__ Xc, int64_t N, double* __restrict__ mu_out, double* __restrict__ eps_out) {
+  static_assert(DP <= 8, "the candidates' B fragments live in registers");
+  using GS = GenShape<DP, KIND, 0>;
+  constexpr int KSD = GS::KSD;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int obj = launch_objective(args.obj_sel);
+  const GPDev g = args.gp[obj];
+  const int d = args.d;
+  const int Q = (g.R + 3) >> 2;
+  const GenRsrc rs = gen_rsrc<DP>(g, Q);
+  const int64_t ncols = (N + 15) >> 4;
+  const int64_t stride = (int64_t)gridDim.x * kMeanWaves;
+  int64_t col = (int64_t)blockIdx.x * kMeanWaves + wave;
+
+  // the B fragments exactly as posterior_mean_kernel builds them
+  int jl[KSD];
+  double lsl[KSD];
+#pragma unroll
+  for (int s = 0; s < KSD; ++s) {
+    jl[s] = min(4 * s + (lane >> 4), d - 1);
+    lsl[s] = g.ls[jl[s]];
+  }
+  auto load_raw = [&](int64_t c, double (&x)[KSD]) {
+    const int64_t ci = min(16 * c + (lane & 15), N - 1);
+#pragma unroll
+    for (int s = 0; s < KSD; ++s) x[s] = Xc[ci * d + jl[s]];
+  };
+  d2 ta[2][(KSD + 1) / 2];
+  double tal[2][4];
+  auto load_tile = [&](int kc, int t, d2 (&a)[(KSD + 1) / 2], double (&al)[4]) {
+    load_tile_a<DP, KIND, 0>(g, rs, lane, kc, t, a);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int kofs = kc * kChunkRows + 16 * t + 4 * i;
+      al[i] = load_row_val<DP, KIND, 0>(rs.al, g.alpha, lane, kofs + (lane >> 4), kofs);
+    }
+  };
+  double xraw[KSD];
+  if (col < ncols) load_raw(col, xraw);
+  for (; col < ncols; col += stride) {
+    load_tile(0, 0, ta[0], tal[0]);
+    double q[KSD];
+#pragma unroll
+    for (int s = 0; s < KSD; ++s) q[s] = (4 * s + (lane >> 4) < d) ? xraw[s] / lsl[s] : 0.0;
+    if (col + stride < ncols) load_raw(col + stride, xraw);
+    double csq = 0.0;
+#pragma unroll
+    for (int j = 0; j < DP; ++j) {
+      const double c = __shfl(q[j >> 2], 16 * (j & 3) + (lane & 15));
+      csq = fma(c, c, csq);
+    }
+    double bfr[KSD];
+#pragma unroll
+    for (int s = 0; s < KSD; ++s) {
+      const int j = 4 * s + (lane >> 4);
+      bfr[s] = (j < d) ? -2.0 * q[s] : (j == d ? 1.0 : (j == d + 1 ? csq : 0.0));
+    }
+    double acc = 0.0;
+    float S = 0.0f;
+    for (int kc = 0; kc < Q; ++kc) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int cur = t & 1, nxt = cur ^ 1;
+        load_tile(kc + (t + 1) / 4, (t + 1) & 3, ta[nxt], tal[nxt]);
+        d4 cr = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < KSD; ++s)
+          cr = __builtin_amdgcn_mfma_f64_16x16x4f64((s & 1) ? ta[cur][s >> 1].y : ta[cur][s >> 1].x, bfr[s], cr, 0, 0, 0);
+        screen_tile<KIND>(cr, tal[cur], acc, S);
+      }
+    }
+    acc += __shfl_xor(acc, 16);
+    acc += __shfl_xor(acc, 32);
+    S += __shfl_xor(S, 16);
+    S += __shfl_xor(S, 32);
+    const int64_t c = 16 * col + lane;
+    if (lane < 16 && c < N) {
+      mu_out[(int64_t)obj * N + c] = g.variance * acc;
+      eps_out[(int64_t)obj * N + c] = fma(0x1p-24 * (1.0 + 0x1p-10) * g.variance, (double)S, 0x1p-64 * g.variance);
+    }
   }
 }
 
@@ -2010,6 +2163,94 @@ static hipError_t launch_posterior_gather_dp(hipStream_t stream, const GPArgs& a
     hipLaunchKernelGGL((posterior_kernel<8, 2, DP, KIND, 8, 0, 2, true>), grid, dim3(kBlockThreads), 0, stream, args, Xc,
                        cap, mu_c, var_c);
   return hipGetLastError();
+}
+
+// posterior_mean_kernel<…, GATHER> for the one objective in args.obj_sel over the list args.idx / args.count (capacity
+// cap): μ to mu_row[idx]; and posterior_screen_kernel over the objectives in args.obj_sel for all N.  Resident grids as
+// launch_posterior_mean's.
+template <int DP, int KIND>
+static hipError_t launch_posterior_mean_gather_dp(hipStream_t stream, const GPArgs& args, const double* Xc,
+                                                  int64_t cap, double* mu_row) {
+  static int per_cu = 0;
+  if (per_cu == 0) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, posterior_mean_kernel<DP, KIND, true>, 64 * kMeanWaves, 0) !=
+            hipSuccess || nb <= 0)
+      nb = 4;
+    per_cu = nb;
+  }
+  const int64_t wgs = ((cap + 15) / 16 + kMeanWaves - 1) / kMeanWaves;
+  const int64_t resident = (int64_t)per_cu * device_cu_count();
+  const dim3 grid((unsigned)std::max<int64_t>(1, std::min(wgs, resident)), 1);
+  hipLaunchKernelGGL((posterior_mean_kernel<DP, KIND, true>), grid, dim3(64 * kMeanWaves), 0, stream, args, Xc, cap,
+                     mu_row);
+  return hipGetLastError();
+}
+
+template <int DP, int KIND>
+static hipError_t launch_posterior_screen_dp(hipStream_t stream, const GPArgs& args, const double* Xc, int64_t N,
+                                             double* mu, double* eps) {
+  static int per_cu = 0;
+  if (per_cu == 0) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, posterior_screen_kernel<DP, KIND>, 64 * kMeanWaves, 0) !=
+            hipSuccess || nb <= 0)
+      nb = 4;
+    per_cu = nb;
+  }
+  const int n_sel = __builtin_popcount(args.obj_sel);
+  const int64_t wgs = ((N + 15) / 16 + kMeanWaves - 1) / kMeanWaves;
+  const int64_t resident = std::max<int64_t>(1, ((int64_t)per_cu * device_cu_count()) / n_sel);
+  const dim3 grid((unsigned)std::max<int64_t>(1, std::min(wgs, resident)), (unsigned)n_sel);
+  hipLaunchKernelGGL((posterior_screen_kernel<DP, KIND>), grid, dim3(64 * kMeanWaves), 0, stream, args, Xc, N, mu, eps);
+  return hipGetLastError();
+}
+
+// which = 0: the gathered mean launch (N the list's capacity, mu the objective's row); 1: the screen (eps its margins)
+template <int KIND>
+static hipError_t launch_posterior_screen_kind(hipStream_t stream, const GPArgs& args, int which, const double* Xc,
+                                               int64_t N, double* mu, double* eps) {
+  switch (args.DP) {
+    case 2:
+      return which ? launch_posterior_screen_dp<2, KIND>(stream, args, Xc, N, mu, eps)
+                   : launch_posterior_mean_gather_dp<2, KIND>(stream, args, Xc, N, mu);
+    case 4:
+      return which ? launch_posterior_screen_dp<4, KIND>(stream, args, Xc, N, mu, eps)
+                   : launch_posterior_mean_gather_dp<4, KIND>(stream, args, Xc, N, mu);
+    case 6:
+      return which ? launch_posterior_screen_dp<6, KIND>(stream, args, Xc, N, mu, eps)
+                   : launch_posterior_mean_gather_dp<6, KIND>(stream, args, Xc, N, mu);
+    case 8:
+      return which ? launch_posterior_screen_dp<8, KIND>(stream, args, Xc, N, mu, eps)
+                   : launch_posterior_mean_gather_dp<8, KIND>(stream, args, Xc, N, mu);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t launch_posterior_mean_gather(hipStream_t stream, const GPArgs& args_in, int obj, const double* Xc,
+                                        const int32_t* idx, const int32_t* count, int64_t cap, double* mu_row) {
+  if (args_in.DP > 8 || obj < 0 || obj >= OMB_MAX_OBJ || !idx || !count || cap < 1) return hipErrorInvalidValue;
+  GPArgs args = args_in;
+  args.ec = exp_coef();
+  args.obj_sel = 1u << obj;
+  args.idx = idx;
+  args.count = count;
+  if (args.gp[obj].kind == OMB_KERNEL_RBF)
+    return launch_posterior_screen_kind<OMB_KERNEL_RBF>(stream, args, 0, Xc, cap, mu_row, nullptr);
+  return launch_posterior_screen_kind<OMB_KERNEL_MATERN52>(stream, args, 0, Xc, cap, mu_row, nullptr);
+}
+
+hipError_t launch_posterior_screen(hipStream_t stream, const GPArgs& args_in, unsigned objs, const double* Xc, int64_t N,
+                                   double* mu, double* eps) {
+  if (args_in.DP > 8 || objs == 0 || N < 1) return hipErrorInvalidValue;
+  GPArgs args = args_in;
+  args.ec = exp_coef();
+  args.obj_sel = objs;
+  args.idx = nullptr;
+  args.count = nullptr;
+  if (args.gp[0].kind == OMB_KERNEL_RBF)
+    return launch_posterior_screen_kind<OMB_KERNEL_RBF>(stream, args, 1, Xc, N, mu, eps);
+  return launch_posterior_screen_kind<OMB_KERNEL_MATERN52>(stream, args, 1, Xc, N, mu, eps);
 }
 
 template <int KIND>

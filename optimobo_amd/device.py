@@ -102,7 +102,8 @@ class AcqContext:
         ("hvi_paths_chunk", c) evaluates a ``plan_hvi_paths`` chain in passes of c candidates (default
         ``_lib.HVI_PATHS_CHUNK``; 0: one pass; bit-identical values); ("argmax_prune", 0/1/2) runs the arg-max chain
         of a reference-mode EHVI-2D plan densely / in two phases from 2^16 candidates on (default) / in two phases
-        at any size (bit-identical pair; see ``argmax_prune_stats``)."""
+        at any size (bit-identical pair; see ``argmax_prune_stats``); ("argmax_screen", 0/1) feeds that path's bound
+        fp64 means of every candidate / ``posterior_screen``'s means and margins (default; bit-identical pair)."""
         code = getattr(_lib, "DEBUG_" + str(what).upper(), None)
         if code is None:
             raise KeyError(what)
@@ -160,6 +161,20 @@ class AcqContext:
         self._stream()
         self._check(self.lib.omb_posterior(self._h, n_obj, _ptr(Xc), N, _ptr(mu), _ptr(var)), "omb_posterior")
         return mu, var
+
+    def posterior_screen(self, Xc, n_obj=None, out=None):
+        """omb_posterior_screen: (μ̃, ε), each fp64 (n_obj, N) — the posterior mean with the kernel transform in
+        fp32 and a rigorous margin, |μ̃ − μ| ≤ ε against ``posterior``'s μ (n_var ≤ 8).  What the arg-max chain's
+        two-phase path prunes with ("argmax_screen")."""
+        Xc = _dev_f64(Xc, self.device)
+        self._check_width(Xc)
+        n_obj = n_obj if n_obj is not None else len(self.gp_info)
+        N = Xc.shape[0]
+        mu, eps = out if out is not None else (self._out(None, (n_obj, N)), self._out(None, (n_obj, N)))
+        self._stream()
+        self._check(self.lib.omb_posterior_screen(self._h, _ptr(Xc), N, n_obj, _ptr(mu), _ptr(eps)),
+                    "omb_posterior_screen")
+        return mu, eps
 
     # ------------------------------------------------------------------ acquisitions
     def ehvi2d(self, mu, var, pf_sorted, r, s00, s01, mode="reference", out=None):
