@@ -143,10 +143,12 @@ const char* omb_last_error(const omb_ctx* ctx);
  * (k·S, N) matrix of path values).  Values and arg-max pairs are bit-identical for every c.
  * omb_debug_set(ctx, OMB_DEBUG_ARGMAX_PRUNE, m) picks how omb_eval_argmax[_sobol] runs under a reference-mode EHVI-2D
  * plan with s00 > 0, s01 > 0 and a sorted non-dominated front, no constraint or log modifier, n_var ≤ 8 and
- * n_train > 128: 1 (default) in two phases from 2^16 candidates on — the means of both objectives for every
- * candidate, the full posterior and the acquisition for every 16th, an upper bound of the acquisition from the means
- * for the rest, and the full posterior and the acquisition only for the candidates whose bound reaches the best value
- * seen; 2 the same at any batch size; 0 the dense chain.  The arg-max pair is bit-identical.
+ * n_train > 128: 1 (default) in two phases from 2^16 candidates on — the means of both objectives and from them an
+ * upper bound of the acquisition for every candidate, the full posterior and the acquisition for the seed (the
+ * candidate with the largest bound in each run of 256 consecutive candidates), and then only for the candidates
+ * whose bound reaches the seed's best value; 3 the same at any batch size; 2 the earlier order at any batch size — the
+ * seed is every 16th candidate, evaluated before the bound of the rest; 0 the dense chain.  The arg-max pair is
+ * bit-identical.
  * omb_debug_set(ctx, OMB_DEBUG_ARGMAX_SCREEN, m) picks where that two-phase path takes the means its bound reads: 1
  * (default) from omb_posterior_screen's fp32-transform means with their margins folded into the bound as intervals, the
  * fp64 mean of objective 1 then computed only for the seed sample and the survivors; 0 from fp64 means of both
@@ -367,9 +369,9 @@ int omb_nondominated(omb_ctx* ctx, int k, int S, const double* y_dev, int64_t ld
  * what the final pass then tested against itself is the last of them.  Host values; nothing is launched. */
 int omb_nondominated_stats(omb_ctx* ctx, int64_t* survivors_host, int* rounds_host);
 /* The last omb_eval_argmax[_sobol] call on this context (OMB_DEBUG_ARGMAX_PRUNE): stats_host[0] = 1 if it took the
- * two-phase path, 0 if the dense chain; [1] the candidates of its seed sample; [2] the candidates past the seed
- * whose bound kept them.  [2] is stored by the call's kernels: it is that call's once its result has been waited
- * for.  All 0 after a dense call.  Host values; nothing is launched and nothing is waited for. */
+ * two-phase path, 0 if the dense chain; [1] the candidates of its seed (⌈N/256⌉, or ⌈N/16⌉ under the value 2); [2]
+ * the candidates past the seed whose bound kept them.  [2] is stored by the call's kernels: it is that call's once
+ * its result has been waited for.  All 0 after a dense call.  Host values; nothing is launched and nothing is waited for. */
 int omb_argmax_prune_stats(omb_ctx* ctx, int64_t* stats_host);
 
 /* Hypervolume-based PoI of EMO (emo.py:176-228): cells_dev (C, 2, 2) [upper, lower]. */

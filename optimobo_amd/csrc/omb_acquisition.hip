@@ -769,8 +769,8 @@ hipError_t launch_pof_scale(hipStream_t stream, int c, const double* mu, const d
 // kernel's own sum (each stripe a dozen rounded operations on terms of that size).  A NaN on either side compares
 // false and keeps the candidate; so does τ ≤ 0.  Strict "<": a candidate tied with τ stays.
 
-// One allocation: the pairs, τ, the counts, the two lists, the per-workgroup counts, the flags and the screen's μ̃ and ε
-// rows, 16-byte aligned each.
+// One allocation: the pairs, τ, the counts, the two lists, the per-workgroup counts, the flags, the margined bounds and
+// the screen's μ̃ and ε rows, 16-byte aligned each.
 static int64_t prune_ws_layout(char* base, int64_t N, PruneWs* ws) {
   int64_t off = 0;
   auto take = [&](int64_t bytes) {
@@ -785,6 +785,7 @@ static int64_t prune_ws_layout(char* base, int64_t N, PruneWs* ws) {
   ws->surv_idx = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * N));
   ws->block_cnt = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * ((N + kPruneBlock - 1) / kPruneBlock)));
   ws->keep = reinterpret_cast<uint8_t*>(take(N));
+  ws->ubm = reinterpret_cast<double*>(take(sizeof(double) * N));
   ws->scr_mu = reinterpret_cast<double*>(take(sizeof(double) * 2 * N));
   ws->scr_eps = reinterpret_cast<double*>(take(sizeof(double) * 2 * N));
   ws->stats_host = nullptr;
@@ -861,13 +862,40 @@ hipError_t launch_ehvi2d_argmax_list(hipStream_t stream, const double* mu0_c, co
   return hipGetLastError();
 }
 
-// The keep flag of candidates blockIdx.x·kPruneBlock + threadIdx.x (seed candidates: 0, they are evaluated already)
-// and the workgroup's count of them.
+// The margined bound ub·(1 + 1e-9) + tiny of one candidate from the low ends m0 = μ̃₀ − ε₀, m1 = μ̃₁ − ε₁ (ε = 0: the
+// means themselves); y1, y2: the stripes in LDS.  Both bound kernels compare or store this one expression.
 // INTERVAL: the means are known to ±ε only, μ₀ ∈ [μ̃₀ − ε₀, μ̃₀ + ε₀], μ₁ ∈ [μ̃₁ − ε₁, μ̃₁ + ε₁].
 // ψ(x, x, μ, σ) decreases in μ and −(b − μ)⁺ increases in μ, so each factor takes the end that makes it largest:
 //     UB = Σ_i ψ(y2_i, y2_i, μ̃₁ − ε₁, σ_f²·s01) · max(ψ(a, a, μ̃₀ − ε₀, σ_f²·s00) − (b − μ̃₀ − ε₀)⁺, 0),
 // and tiny is taken with |a − μ̃₀| + ε₀ and |b − μ̃₀| + ε₀.  A NaN or an infinity in μ̃ or ε makes UB NaN or +∞ and
 // keeps the candidate.  The plain instantiation is the same arithmetic with ε = 0.
+template <bool INTERVAL>
+__device__ __forceinline__ double prune_ubm(double m0, double m1, double e0, const double* y1, const double* y2, int P,
+                                            double sA, double sB) {
+#pragma clang fp contract(off)
+  const double iA = 1.0 / sA, iB = 1.0 / sB;
+  double ub = 0.0, scale = 0.0;
+  double da = y1[0] - m0;
+  double ta = da * iA;
+  double psi_a = sA * npdf_fast(ta) + da * ndtr_fast(ta);       // ψ(a, a, μ₀, σ_f²·s00)
+  for (int i = 1; i <= P; ++i) {
+    const double db = y1[i] - m0, dy = y2[i - 1] - m1;
+    // (b − μ̃₀ − ε₀)⁺ = (db − 2ε₀)⁺; |a − μ̃₀| + ε₀ ≤ |da| + 2ε₀, and so for b
+    const double g = fmax(psi_a - fmax(INTERVAL ? db - 2.0 * e0 : db, 0.0), 0.0);
+    const double u = dy * iB;
+    const double p2 = fmax(sB * npdf_fast(u) + dy * ndtr_fast(u), 0.0);   // ψ(y2_i, y2_i, μ₁, σ_f²·s01)
+    ub += p2 * g;
+    scale += p2 * (INTERVAL ? fabs(da) + fabs(db) + 4.0 * e0 + sA : fabs(da) + fabs(db) + sA);
+    da = db;
+    ta = da * iA;
+    psi_a = sA * npdf_fast(ta) + da * ndtr_fast(ta);
+  }
+  const double tiny = 64.0 * 0x1p-52 * scale + 1e-300;
+  return ub * (1.0 + 1e-9) + tiny;
+}
+
+// The keep flag of candidates blockIdx.x·kPruneBlock + threadIdx.x (seed candidates: 0, they are evaluated already)
+// and the workgroup's count of them, against the strided seed's τ.
 template <bool INTERVAL>
 __global__ __launch_bounds__(kPruneBlock) void prune_bound_kernel(const double* __restrict__ mu0,
                                                                   const double* __restrict__ mu1,
@@ -901,28 +929,85 @@ __global__ __launch_bounds__(kPruneBlock) void prune_bound_kernel(const double* 
         m0 -= e0;
         m1 -= eps1[c];
       }
-      const double iA = 1.0 / sA, iB = 1.0 / sB;
-      double ub = 0.0, scale = 0.0;
-      double da = y1[0] - m0;
-      double ta = da * iA;
-      double psi_a = sA * npdf_fast(ta) + da * ndtr_fast(ta);       // ψ(a, a, μ₀, σ_f²·s00)
-      for (int i = 1; i <= P; ++i) {
-        const double db = y1[i] - m0, dy = y2[i - 1] - m1;
-        // (b − μ̃₀ − ε₀)⁺ = (db − 2ε₀)⁺; |a − μ̃₀| + ε₀ ≤ |da| + 2ε₀, and so for b
-        const double g = fmax(psi_a - fmax(INTERVAL ? db - 2.0 * e0 : db, 0.0), 0.0);
-        const double u = dy * iB;
-        const double p2 = fmax(sB * npdf_fast(u) + dy * ndtr_fast(u), 0.0);   // ψ(y2_i, y2_i, μ₁, σ_f²·s01)
-        ub += p2 * g;
-        scale += p2 * (INTERVAL ? fabs(da) + fabs(db) + 4.0 * e0 + sA : fabs(da) + fabs(db) + sA);
-        da = db;
-        ta = da * iA;
-        psi_a = sA * npdf_fast(ta) + da * ndtr_fast(ta);
-      }
-      const double tiny = 64.0 * 0x1p-52 * scale + 1e-300;
-      if (ub * (1.0 + 1e-9) + tiny < t) k = false;
+      if (prune_ubm<INTERVAL>(m0, m1, e0, y1, y2, P, sA, sB) < t) k = false;
     }
   }
   if (c < N) keep[c] = k ? 1 : 0;
+  const int nw = __popcll(__ballot(k));
+  if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = nw;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int s = 0;
+    for (int w = 0; w < kPruneBlock / 64; ++w) s += wave_cnt[w];
+    block_cnt[blockIdx.x] = s;
+  }
+}
+
+// The bound with no τ: one workgroup per seed group of kPruneSeedGroup consecutive candidates, thread t
+// takes the group's candidates t, t + kPruneBlock, ….  ubm[c] for every c < N — the expression prune_bound_kernel
+// compares, no stride skipped — and the group's seed: the largest ubm among those with ubm == ubm (+∞ included), the
+// lowest index on ties, the group's first candidate where none compares.  Any candidate is a valid seed: τ only has to
+// be a value that some candidate attains.
+template <bool INTERVAL>
+__global__ __launch_bounds__(kPruneBlock) void prune_bound_seed_kernel(
+    const double* __restrict__ mu0, const double* __restrict__ mu1, const double* __restrict__ eps0,
+    const double* __restrict__ eps1, int64_t N, const double* __restrict__ pf, int P, double r0, double sA, double sB,
+    double* __restrict__ ubm, int32_t* __restrict__ seed_idx, int32_t* __restrict__ counts) {
+  extern __shared__ double sm[];
+  double* y1 = sm;
+  double* y2 = sm + P + 1;
+  __shared__ double red_v[kPruneBlock / 64];
+  __shared__ long long red_i[kPruneBlock / 64];
+  for (int i = threadIdx.x; i < P; i += blockDim.x) {
+    y1[i + 1] = pf[2 * i];
+    y2[i] = pf[2 * i + 1];
+  }
+  if (threadIdx.x == 0) y1[0] = r0;
+  __syncthreads();
+  const int64_t first = (int64_t)blockIdx.x * kPruneSeedGroup;
+  double bv = -__builtin_inf();
+  long long bi = -1;
+#pragma unroll 1
+  for (int j = 0; j < kPruneSeedGroup / kPruneBlock; ++j) {
+    const int64_t c = first + j * kPruneBlock + threadIdx.x;
+    if (c < N) {
+      double m0 = mu0[c], m1 = mu1[c];   // the low ends μ̃ − ε under INTERVAL
+      double e0 = 0.0;
+      if constexpr (INTERVAL) {
+        e0 = eps0[c];
+        m0 -= e0;
+        m1 -= eps1[c];
+      }
+      const double v = prune_ubm<INTERVAL>(m0, m1, e0, y1, y2, P, sA, sB);
+      ubm[c] = v;
+      if (v == v && argmax_better(v, c, bv, bi)) {
+        bv = v;
+        bi = c;
+      }
+    }
+  }
+  argmax_wave_block(bv, bi, red_v, red_i);
+  if (threadIdx.x == 0) {
+    seed_idx[blockIdx.x] = (int32_t)(bi < 0 ? first : bi);   // first < N: the grid is ⌈N/kPruneSeedGroup⌉
+    if (blockIdx.x == 0) counts[0] = (int32_t)gridDim.x;
+  }
+}
+
+// keep[c] of the seed by bound and the workgroup's count: the parent's decision for the same τ — strict
+// "<", false on a NaN, τ ≤ 0, −∞ or NaN keeps everything — with the group's seed, which is evaluated already, left out.
+__global__ __launch_bounds__(kPruneBlock) void prune_threshold_kernel(const double* __restrict__ ubm,
+                                                                      const int32_t* __restrict__ seed_idx,
+                                                                      const double* __restrict__ tau, int64_t N,
+                                                                      uint8_t* __restrict__ keep,
+                                                                      int32_t* __restrict__ block_cnt) {
+  __shared__ int wave_cnt[kPruneBlock / 64];
+  const int64_t c = (int64_t)blockIdx.x * kPruneBlock + threadIdx.x;
+  const double t = tau[0];
+  bool k = false;
+  if (c < N) {
+    k = c != (int64_t)seed_idx[c / kPruneSeedGroup] && !(t > 0.0 && ubm[c] < t);
+    keep[c] = k ? 1 : 0;
+  }
   const int nw = __popcll(__ballot(k));
   if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = nw;
   __syncthreads();
@@ -982,6 +1067,18 @@ __global__ __launch_bounds__(kPruneBlock) void prune_compact_kernel(const uint8_
   if (k) surv_idx[pos] = (int32_t)c;
 }
 
+// keep and block_cnt → surv_idx, counts[1] and *stats_host
+static hipError_t launch_prune_compact(hipStream_t stream, int64_t N, const PruneWs& ws) {
+  const int64_t nb = (N + kPruneBlock - 1) / kPruneBlock;
+  hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(1024), 0, stream, ws.block_cnt, (int)nb, ws.counts,
+                     ws.stats_host);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(prune_compact_kernel, dim3((unsigned)nb), dim3(kPruneBlock), 0, stream, ws.keep, N, ws.block_cnt,
+                     ws.surv_idx);
+  return hipGetLastError();
+}
+
 hipError_t launch_prune_bound(hipStream_t stream, const double* mu0, const double* mu1, int64_t N, const double* pf,
                               int P, double r0, double s00, double s01, double sf2, const PruneWs& ws,
                               const double* eps0, const double* eps1) {
@@ -994,14 +1091,32 @@ hipError_t launch_prune_bound(hipStream_t stream, const double* mu0, const doubl
   else
     hipLaunchKernelGGL(prune_bound_kernel<false>, dim3((unsigned)nb), dim3(kPruneBlock), shm, stream, mu0, mu1, eps0,
                        eps1, N, pf, P, r0, sf2 * s00, sf2 * s01, ws.tau, ws.keep, ws.block_cnt);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(1024), 0, stream, ws.block_cnt, (int)nb, ws.counts,
-                     ws.stats_host);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(prune_compact_kernel, dim3((unsigned)nb), dim3(kPruneBlock), 0, stream, ws.keep, N, ws.block_cnt,
-                     ws.surv_idx);
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? e : launch_prune_compact(stream, N, ws);
+}
+
+hipError_t launch_prune_bound_seed(hipStream_t stream, const double* mu0, const double* mu1, int64_t N,
+                                   const double* pf, int P, double r0, double s00, double s01, double sf2,
+                                   const PruneWs& ws, const double* eps0, const double* eps1) {
+  const int64_t ng = (N + kPruneSeedGroup - 1) / kPruneSeedGroup;
+  if (N < 1 || ng > (1 << 23) || !eps0 != !eps1) return hipErrorInvalidValue;
+  const size_t shm = sizeof(double) * (2 * P + 1);
+  if (eps0)
+    hipLaunchKernelGGL(prune_bound_seed_kernel<true>, dim3((unsigned)ng), dim3(kPruneBlock), shm, stream, mu0, mu1,
+                       eps0, eps1, N, pf, P, r0, sf2 * s00, sf2 * s01, ws.ubm, ws.seed_idx, ws.counts);
+  else
+    hipLaunchKernelGGL(prune_bound_seed_kernel<false>, dim3((unsigned)ng), dim3(kPruneBlock), shm, stream, mu0, mu1,
+                       eps0, eps1, N, pf, P, r0, sf2 * s00, sf2 * s01, ws.ubm, ws.seed_idx, ws.counts);
   return hipGetLastError();
+}
+
+hipError_t launch_prune_threshold(hipStream_t stream, int64_t N, const PruneWs& ws) {
+  const int64_t nb = (N + kPruneBlock - 1) / kPruneBlock;
+  if (N < 1 || nb > (1 << 23)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(prune_threshold_kernel, dim3((unsigned)nb), dim3(kPruneBlock), 0, stream, ws.ubm, ws.seed_idx,
+                     ws.tau, N, ws.keep, ws.block_cnt);
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? e : launch_prune_compact(stream, N, ws);
 }
 
 }  // namespace omb

@@ -153,7 +153,8 @@ struct omb_ctx {
   int hvi_paths_chunk = (int)kHviPathsChunk;   // OMB_DEBUG_HVI_PATHS_CHUNK: candidates per pass of a sampled-front chain
   int posterior_all_var = 0;     // OMB_DEBUG_POSTERIOR_ALL_VAR: the chain computes σ² of every objective
   int posterior_mean_kernel = kMeanKernelAfter;   // OMB_DEBUG_POSTERIOR_MEAN_KERNEL: masked objectives' μ in a launch of its own
-  int argmax_prune = 1;          // OMB_DEBUG_ARGMAX_PRUNE: 0 dense, 1 two-phase from kPruneMinN candidates, 2 always
+  int argmax_prune = 1;          // OMB_DEBUG_ARGMAX_PRUNE: 0 dense, 1 two-phase (seed by bound) from kPruneMinN
+                                 // candidates, 2 the strided seed at any N, 3 the seed by bound at any N
   int argmax_screen = 1;         // OMB_DEBUG_ARGMAX_SCREEN: the two-phase path's bound from 1 the fp32 screen, 0 fp64 means
 };
 
@@ -623,15 +624,18 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
   }
   // The two-phase arg-max where the plan has a bound, nothing comes between the acquisition and the
   // arg-max, posterior_mean_kernel and a ring kernel exist for the shape, and the batch is large enough for the
-  // launches it adds (kPruneMinN; OMB_DEBUG_ARGMAX_PRUNE 2: any size).  Everything else keeps the dense chain.
+  // launches it adds (kPruneMinN; OMB_DEBUG_ARGMAX_PRUNE 2 and 3: any size).  Everything else keeps the dense chain.
   const bool two_phase = result_dev && !vals_out && !acq_raw && !all_var && !ctx->posterior_all_var && !paths &&
                          pl.kind == PLAN_EHVI2D && pl.prune_ok && pl.n_con == 0 && !pl.log && k == 2 &&
                          posterior_gather_fits(args, max_R) && N >= 1 && N <= kPruneMaxN &&
-                         (ctx->argmax_prune == 2 || (ctx->argmax_prune == 1 && N >= kPruneMinN));
+                         (ctx->argmax_prune >= 2 || (ctx->argmax_prune == 1 && N >= kPruneMinN));
+  // The seed: each group's best bound — or, under OMB_DEBUG_ARGMAX_PRUNE 2, the strided sample of §29
+  const bool seed_by_bound = ctx->argmax_prune != 2;
+  const int64_t seed_step = seed_by_bound ? kPruneSeedGroup : kPruneStride;
   if (two_phase && (rc = grow_dev(ctx, ctx->prws, (size_t)prune_ws_bytes(N), "arg-max pruning workspace"))) return rc;
   if (result_dev) {
     ctx->prune_taken = two_phase ? 1 : 0;
-    ctx->prune_seed = two_phase ? (N + kPruneStride - 1) / kPruneStride : 0;
+    ctx->prune_seed = two_phase ? (N + seed_step - 1) / seed_step : 0;
   }
   double* mu = ctx->work.as<double>();
   double* var = mu + (size_t)K * nd;
@@ -681,14 +685,14 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
     }
     if (e == hipSuccess && N == 0) e = mark(2);
   } else if (two_phase) {
-    // both means for all N, the full posterior and the acquisition for the seed sample, the bound for the
-    // rest against the seed's best value, then the full posterior and the acquisition for the survivors alone; the
+    // both means for all N, the full posterior and the acquisition for the seed, the bound of the rest
+    // against the seed's best value τ, then the full posterior and the acquisition for the survivors alone; the
     // arg-max over both sets of pairs compares original indices, so the pair is the dense chain's.  All on the stream,
     // the counts stay on the device.
     PruneWs ws;
     prune_ws_carve(ctx->prws.p, N, &ws);
     ws.stats_host = ctx->prune_stats_dev;
-    const int64_t ns = (N + kPruneStride - 1) / kPruneStride, nv = N - ns;
+    const int64_t ns = (N + seed_step - 1) / seed_step, nv = N - ns;
     const int nbs = prune_list_blocks(ns), nbv = nv > 0 ? prune_list_blocks(nv) : 0;
     double* mu_c = var;                 // the workspace's σ² rows: the gathered launches' compacted μ₀ | σ²₀
     double* var_c = var + nd;
@@ -697,8 +701,18 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
     // seed and of the survivors comes from the gathered mean launch, at the candidates' original slots, where the list
     // EHVI reads it.  0: the fp64 means of §29 for all N.
     const bool screen = ctx->argmax_screen != 0;
+    const double* bm = screen ? ws.scr_mu : mu;   // the bound's means and, under the screen, their margins
+    const double* be0 = screen ? ws.scr_eps : nullptr;
+    const double* be1 = screen ? ws.scr_eps + nd : nullptr;
     if (e == hipSuccess && !screen) e = launch_posterior_means(ctx->stream, args, 3u, Xc, N, mu);
-    if (e == hipSuccess) e = launch_prune_seed(ctx->stream, N, ws);
+    // the means and the bound come first; the seed is each group's best bound, so τ is (nearly) the
+    // maximum and the threshold kernel leaves a handful of survivors.  §29's order: the strided seed, then the bound.
+    if (e == hipSuccess && seed_by_bound && screen)
+      e = launch_posterior_screen(ctx->stream, args, 3u, Xc, N, ws.scr_mu, ws.scr_eps);
+    if (e == hipSuccess && seed_by_bound)
+      e = launch_prune_bound_seed(ctx->stream, bm, bm + nd, N, pl.geo, pl.P, pl.r[0], pl.s00, pl.s01, sf2, ws, be0,
+                                  be1);
+    if (e == hipSuccess && !seed_by_bound) e = launch_prune_seed(ctx->stream, N, ws);
     if (e == hipSuccess)
       e = launch_posterior_gather(ctx->stream, args, max_R, Xc, ws.seed_idx, ws.counts, ns, mu_c, var_c);
     if (e == hipSuccess && screen)
@@ -707,12 +721,11 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
       e = launch_ehvi2d_argmax_list(ctx->stream, mu_c, var_c, mu + nd, ws.seed_idx, ws.counts, ns, pl.geo, pl.P,
                                     pl.r[0], pl.r[1], pl.s00, pl.s01, pl.mode, ws.partials);
     if (e == hipSuccess) e = launch_argmax_reduce(ctx->stream, ws.partials, nbs, 0, ws.tau);
-    if (e == hipSuccess && screen) e = launch_posterior_screen(ctx->stream, args, 3u, Xc, N, ws.scr_mu, ws.scr_eps);
-    if (e == hipSuccess && screen)
-      e = launch_prune_bound(ctx->stream, ws.scr_mu, ws.scr_mu + nd, N, pl.geo, pl.P, pl.r[0], pl.s00, pl.s01, sf2, ws,
-                             ws.scr_eps, ws.scr_eps + nd);
-    if (e == hipSuccess && !screen)
-      e = launch_prune_bound(ctx->stream, mu, mu + nd, N, pl.geo, pl.P, pl.r[0], pl.s00, pl.s01, sf2, ws);
+    if (e == hipSuccess && seed_by_bound) e = launch_prune_threshold(ctx->stream, N, ws);
+    if (e == hipSuccess && !seed_by_bound && screen)
+      e = launch_posterior_screen(ctx->stream, args, 3u, Xc, N, ws.scr_mu, ws.scr_eps);
+    if (e == hipSuccess && !seed_by_bound)
+      e = launch_prune_bound(ctx->stream, bm, bm + nd, N, pl.geo, pl.P, pl.r[0], pl.s00, pl.s01, sf2, ws, be0, be1);
     if (e == hipSuccess && nv > 0)
       e = launch_posterior_gather(ctx->stream, args, max_R, Xc, ws.surv_idx, ws.counts + 1, nv, mu_c, var_c);
     if (e == hipSuccess && nv > 0 && screen)
@@ -857,8 +870,9 @@ static const DebugSwitch kDebugSwitches[] = {
     {OMB_DEBUG_HVI_PATHS_CHUNK, &omb_ctx::hvi_paths_chunk, 0, 0x7fffffff,
      "sampled-front chain chunk %lld outside [0, 2^31) (0: one pass)"},
     {OMB_DEBUG_POSTERIOR_ALL_VAR, &omb_ctx::posterior_all_var, 0, 1, nullptr},
-    {OMB_DEBUG_ARGMAX_PRUNE, &omb_ctx::argmax_prune, 0, 2,
-     "arg-max pruning %lld (0 dense, 1 two-phase for large batches, 2 two-phase at any size)"},
+    {OMB_DEBUG_ARGMAX_PRUNE, &omb_ctx::argmax_prune, 0, 3,
+     "arg-max pruning %lld (0 dense, 1 two-phase for large batches, 2 strided seed at any size, 3 seed by bound at "
+     "any size)"},
     {OMB_DEBUG_ARGMAX_SCREEN, &omb_ctx::argmax_screen, 0, 1, nullptr},
 };
 

@@ -98,15 +98,21 @@ hipError_t launch_posterior_screen(hipStream_t stream, const GPArgs& args, unsig
                                    double* mu, double* eps);
 
 // Pruning of the EHVI-2D arg-max in OMB_EHVI_REFERENCE (omb_acquisition.hip).  A list is int32 indices into the batch
-// with a device-side count; "seed" is the strided sample 0, kPruneStride, 2·kPruneStride, ….
+// with a device-side count; "seed" is the strided sample 0, kPruneStride, 2·kPruneStride, … or,
+// seeded by the bound, the candidate with the largest margined bound of each run of kPruneSeedGroup
+// consecutive candidates.
 constexpr int kPruneStride = 16;
-constexpr int kPruneBlock = 256;   // candidates per workgroup of the bound / compaction kernels
+constexpr int kPruneBlock = 256;   // candidates per workgroup of the bound / threshold / compaction kernels
+constexpr int kPruneSeedGroup = 256;   // a multiple of kPruneBlock, at most 1024
+static_assert(kPruneSeedGroup % kPruneBlock == 0 && kPruneSeedGroup >= kPruneStride && kPruneSeedGroup <= 1024,
+              "seed groups are whole workgroups of the threshold kernel and seed_idx holds ⌈N/kPruneStride⌉ entries");
 struct PruneWs {
-  int32_t* seed_idx;     // ⌈N/kPruneStride⌉
+  int32_t* seed_idx;     // ⌈N/kPruneStride⌉ (the seed by bound uses the first ⌈N/kPruneSeedGroup⌉)
   int32_t* surv_idx;     // N
   int32_t* counts;       // [0] seed count, [1] survivor count
   int32_t* block_cnt;    // ⌈N/kPruneBlock⌉ survivors per workgroup, then (in place) their exclusive prefix sums
   uint8_t* keep;         // N flags
+  double* ubm;           // N margined bounds ub·(1 + 1e-9) + tiny (the seed by bound)
   double* scr_mu;        // (2, N) the screen's μ̃
   double* scr_eps;       // (2, N) its margins ε
   double* partials;      // 2 × kArgmaxMaxBlocks (value, index) pairs: the seed's, then the survivors'
@@ -131,6 +137,16 @@ hipError_t launch_ehvi2d_argmax_list(hipStream_t stream, const double* mu0_c, co
 hipError_t launch_prune_bound(hipStream_t stream, const double* mu0, const double* mu1, int64_t N, const double* pf,
                               int P, double r0, double s00, double s01, double sf2, const PruneWs& ws,
                               const double* eps0 = nullptr, const double* eps1 = nullptr);
+// The seed by bound, in two steps around the seed's evaluation.
+//   launch_prune_bound_seed  the same bound with the same margin for every candidate, with no τ: ws.ubm, the index of
+//                            each group's largest comparable ubm (lowest index on ties; the group's first candidate
+//                            where none compares) to ws.seed_idx — ascending — and counts[0] = ⌈N/kPruneSeedGroup⌉
+//   launch_prune_threshold   keep = not its group's seed and not (τ > 0 and ubm < τ) against *ws.tau, then the scan
+//                            and the compaction of launch_prune_bound: surv_idx, counts[1], *stats_host
+hipError_t launch_prune_bound_seed(hipStream_t stream, const double* mu0, const double* mu1, int64_t N,
+                                   const double* pf, int P, double r0, double s00, double s01, double sf2,
+                                   const PruneWs& ws, const double* eps0 = nullptr, const double* eps1 = nullptr);
+hipError_t launch_prune_threshold(hipStream_t stream, int64_t N, const PruneWs& ws);
 
 // EHVI-2D and the arg-max in one launch (omb_acquisition.hip): each workgroup's (value, index) pair goes to
 // `partials` (2 doubles per workgroup, ehvi2d_argmax_blocks(N) ≤ kArgmaxMaxBlocks); the last workgroup to finish (an

@@ -100,10 +100,12 @@ class AcqContext:
         of its own after it (default) / in that kernel before it (bit-identical values); ("paths_libcos", 0/1)
         evaluates the sample paths' features with the kernel's own cosine (default) / the device library's;
         ("hvi_paths_chunk", c) evaluates a ``plan_hvi_paths`` chain in passes of c candidates (default
-        ``_lib.HVI_PATHS_CHUNK``; 0: one pass; bit-identical values); ("argmax_prune", 0/1/2) runs the arg-max chain
-        of a reference-mode EHVI-2D plan densely / in two phases from 2^16 candidates on (default) / in two phases
-        at any size (bit-identical pair; see ``argmax_prune_stats``); ("argmax_screen", 0/1) feeds that path's bound
-        fp64 means of every candidate / ``posterior_screen``'s means and margins (default; bit-identical pair)."""
+        ``_lib.HVI_PATHS_CHUNK``; 0: one pass; bit-identical values); ("argmax_prune", 0/1/2/3) runs the arg-max
+        chain of a reference-mode EHVI-2D plan densely / in two phases, seeded by each group's best bound, from 2^16
+        candidates on (default) / in two phases with the strided seed at any size / in two phases seeded by the
+        bound at any size (bit-identical pair; see ``argmax_prune_stats``); ("argmax_screen", 0/1) feeds that path's
+        bound fp64 means of every candidate / ``posterior_screen``'s means and margins (default; bit-identical
+        pair)."""
         code = getattr(_lib, "DEBUG_" + str(what).upper(), None)
         if code is None:
             raise KeyError(what)
@@ -363,9 +365,9 @@ class AcqContext:
 
     def argmax_prune_stats(self):
         """omb_argmax_prune_stats: the last ``eval_argmax`` / ``eval_argmax_sobol`` call → (two_phase, seed,
-        survivors): whether it took the two-phase path, the candidates of its seed sample and those past the seed
-        that its bound kept (the call's own once its result has been waited for).  (False, 0, 0) after a dense
-        call."""
+        survivors): whether it took the two-phase path, the candidates of its seed (one per 256, or every 16th
+        under "argmax_prune" 2) and those past the seed that its bound kept (the call's own once its result has been
+        waited for).  (False, 0, 0) after a dense call."""
         st = (ctypes.c_int64 * 3)()
         self._check(self.lib.omb_argmax_prune_stats(self._h, st), "omb_argmax_prune_stats")
         return bool(st[0]), int(st[1]), int(st[2])
