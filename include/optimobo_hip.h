@@ -179,7 +179,10 @@ int omb_debug_set(omb_ctx* ctx, int what, int64_t value);
  *   X_dev     (n, d)  training inputs, unscaled
  *   lengthscale_host (d) ARD lengthscales ℓ;  variance = σ_f²
  *   alpha_dev (n)     woodbury vector (K + 1e-8 I)^-1 y
- *   Linv_dev  (n, n)  row-major inverse of the lower Cholesky factor of K + 1e-8 I
+ *   Linv_dev  (n, n)  row-major inverse of the lower Cholesky factor of K + 1e-8 I.  Only the diagonal and the
+ *                     entries below it are read: what lies above the diagonal (the other half of an in-place LAPACK
+ *                     dpotrf / dtrtri result, say) is ignored by every consumer — posterior, covariance, gradients,
+ *                     sample paths, append — which all see zeros there.
  * The context packs this into its own layout (Lp: MFMA-fragment order) on its stream. */
 int omb_set_gp(omb_ctx* ctx, int obj, int kernel, int n, int d, const double* X_dev,
                const double* lengthscale_host, double variance, const double* alpha_dev,

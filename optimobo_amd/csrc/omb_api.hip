@@ -938,8 +938,9 @@ static hipError_t install_gp(omb_ctx* ctx, ObjState& s, double* buf, int kernel,
   hipError_t e = launch_pack_gp(ctx->stream, n, d, DP, X_dev, lengthscale_host, alpha_dev, Linv_dev, Xs, xsq,
                                 alpha_p, Lp, R_pack, n_pad);
   if (e == hipSuccess) e = launch_pack_x(ctx->stream, d, DP, n_pad, Xs, xsq, Xf);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(Ld, Linv_dev, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToDevice, ctx->stream);
+  // the lower triangle only, zeros above: launch_gemm_tn (w = L⁻ᵀV of the gradients and the sample paths) reads all
+  // of Ld, and the entries above the diagonal of the caller's L⁻¹ are not part of the contract
+  if (e == hipSuccess) e = launch_copy_lower(ctx->stream, n, Linv_dev, Ld);
   if (e == hipSuccess)
     e = hipMemcpyAsync(Xraw, X_dev, sizeof(double) * (size_t)n * d, hipMemcpyDeviceToDevice, ctx->stream);
   if (e != hipSuccess) {

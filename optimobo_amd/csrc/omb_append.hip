@@ -209,10 +209,19 @@ void append_ws_carve(double* base, int m, int d, int DP, AppendWs* ws) {
   ws->DP = DP;
 }
 
+// Both launches below put one matrix row on gridDim.y, which ends at 65535.
+static_assert(OMB_MAX_TRAIN_DENSE <= 65535, "append_restride_kernel: one grid row per matrix row");
+
 hipError_t launch_append_restride(hipStream_t stream, const AppendWs& ws, int n, const double* Ld) {
   const int m = ws.m;
   hipLaunchKernelGGL(append_restride_kernel, dim3((m + kAppThreads - 1) / kAppThreads, m), dim3(kAppThreads), 0,
                      stream, n, m, Ld, ws.L);
+  return hipGetLastError();
+}
+
+hipError_t launch_copy_lower(hipStream_t stream, int n, const double* Linv, double* Ld) {
+  hipLaunchKernelGGL(append_restride_kernel, dim3((n + kAppThreads - 1) / kAppThreads, n), dim3(kAppThreads), 0,
+                     stream, n, n, Linv, Ld);
   return hipGetLastError();
 }
 

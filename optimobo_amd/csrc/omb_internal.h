@@ -483,6 +483,9 @@ int64_t append_ws_doubles(int m, int d, int DP);
 void append_ws_carve(double* base, int m, int d, int DP, AppendWs* ws);
 // ws.L ← the lower triangle of Ld (n, n), re-strided to pitch m, zeros elsewhere
 hipError_t launch_append_restride(hipStream_t stream, const AppendWs& ws, int n, const double* Ld);
+// Ld (n, n) ← the lower triangle of Linv (n, n), zeros above the diagonal (the same kernel at m = n): the installed
+// dense L⁻¹, so that the transposed products (w = L⁻ᵀV) never see what a caller left above the diagonal
+hipError_t launch_copy_lower(hipStream_t stream, int n, const double* Linv, double* Ld);
 // point j of the call (row c = n + j of ws.Xs / ws.xsq, already scaled) joins the c points of ws: row c of ws.L,
 // ws.alpha updated; ynew null = the Kriging believer (y = μ); mu_out[j] = μ, var_out[j] = δ² (either may be null)
 hipError_t launch_append_point(hipStream_t stream, const AppendWs& ws, int kind, double variance, int c, int j,

@@ -187,6 +187,41 @@ def test_dense_paths_read_lower_triangle_of_linv_only(ctx):
     assert torch.equal(mc, mc2) and torch.equal(cov, cov2)
 
 
+@pytest.mark.parametrize("n", [1100, 130], ids=["dense-1100", "ring-130"])
+def test_transposed_products_read_lower_triangle_of_linv_only(ctx, n):
+    """The same contract for the consumers that go through w = L⁻ᵀV, a GEMM with the transposed dense L⁻¹ that has
+    no triangular form: omb_posterior_grad (all four outputs), omb_eval_grad under an EI plan, and omb_paths_set +
+    omb_paths_eval with fixed ω, phase, w and z.  Finite junk above the diagonal of the installed L⁻¹ (what an
+    in-place LAPACK dpotrf / dtrtri pair leaves there) changes no bit of any of them."""
+    from optimobo_amd import paths
+    from optimobo_amd.gp import GPState
+    rng = np.random.default_rng(43 + n)
+    d, N, S, m = 3, 77, 8, 64
+    X = rng.uniform(0, 1, (n, d))
+    y = np.sin(3 * X).sum(1)
+    st = GPState(X, y, np.full(d, 0.7), float(np.var(y)))
+    Xc = dev(np.vstack([rng.uniform(0, 1, (N - 3, d)), X[:3]]))
+    omega, phase, w, z = paths.draw_path_inputs("matern52", n, d, S, m, rng, np.zeros(d), np.ones(d), st.lengthscale)
+
+    def run():
+        ctx.set_gp_state(0, st)
+        ctx.plan_ei(float(np.median(y)), 0.0)
+        out = list(ctx.posterior_grad(Xc, 1)) + list(ctx.eval_grad(Xc))
+        ctx.paths_set(0, omega, phase, w, z, noise=0.0)
+        out.append(ctx.paths_eval(Xc, 1))
+        return [o.clone() for o in out]
+
+    clean = run()
+    assert all(bool(torch.isfinite(o).all()) for o in clean)
+    assert bool((clean[2][0].abs().amax(1) > 0).all()) and bool((clean[3][0].abs().amax(1) > 0).all())
+    assert np.all(np.triu(st.Linv, 1) == 0)
+    st.Linv = st.Linv + np.triu(rng.uniform(-1e3, 1e3, (n, n)), 1)
+    junk = run()
+    names = ["mu", "var", "dmu", "dvar", "eval_grad value", "eval_grad gradient", "paths_eval"]
+    for name, a, b in zip(names, clean, junk):
+        assert torch.equal(a, b), f"{name} changed with junk above the diagonal of L^-1 (max |diff| {float((a - b).abs().max()):.3e})"
+
+
 def test_dense_path_in_fused_chain(ctx):
     """The fused chain (plan → eval_argmax) runs the dense path too; same values as per-kernel calls."""
     from optimobo_amd import pareto
