@@ -153,7 +153,15 @@ const char* omb_last_error(const omb_ctx* ctx);
  * (default) from omb_posterior_screen's fp32-transform means with their margins folded into the bound as intervals, the
  * fp64 mean of objective 1 then computed only for the seed sample and the survivors; 0 from fp64 means of both
  * objectives for every candidate (for a model so ill-conditioned that the margins keep everything).  The arg-max pair
- * is bit-identical: only the fp64 kernels' values reach it. */
+ * is bit-identical: only the fp64 kernels' values reach it.
+ * omb_debug_set(ctx, OMB_DEBUG_ARGMAX_STAGED, m) picks the order of that path where the seed comes from the bound
+ * (OMB_DEBUG_ARGMAX_PRUNE 1 or 3) and the screen is on: 1 (default) staged — the screen of objective 1 alone for every
+ * candidate, a bound from it that holds for any mean of objective 0, the seed (the smallest screened mean of objective 1
+ * in each run of 256 candidates) and a first list by that bound, and objective 0's screen and the full bound only for
+ * that list; 0 both objectives' screen and the full bound for every candidate.  The staged order wins where objective 1's mean rules most candidates out; where objective 0 decides
+ * (the first list keeps most of the batch) it costs an extra pass over the list — measured 8.4 % behind 0 at 2^20
+ * candidates with the flagship's two objectives swapped, where the list keeps 83 % — and 0 is the order to use.  The
+ * arg-max pair is bit-identical (omb_argmax_stage_stats reports the lists' sizes). */
 enum {
   OMB_DEBUG_SPIN_LIMIT = 1,
   OMB_DEBUG_COV_TABLE = 2,
@@ -170,7 +178,8 @@ enum {
   OMB_DEBUG_PATHS_LIBCOS = 14,
   OMB_DEBUG_HVI_PATHS_CHUNK = 15,
   OMB_DEBUG_ARGMAX_PRUNE = 16,
-  OMB_DEBUG_ARGMAX_SCREEN = 17
+  OMB_DEBUG_ARGMAX_SCREEN = 17,
+  OMB_DEBUG_ARGMAX_STAGED = 18
 };
 int omb_debug_set(omb_ctx* ctx, int what, int64_t value);
 
@@ -207,6 +216,13 @@ int omb_posterior(omb_ctx* ctx, int n_obj, const double* Xc_dev, int64_t N, doub
  * two-phase path prunes with it (OMB_DEBUG_ARGMAX_SCREEN). */
 int omb_posterior_screen(omb_ctx* ctx, const double* Xc_dev, int64_t N, int n_obj, double* mu_out_dev,
                           double* eps_out_dev);
+
+/* omb_posterior_screen of objective `obj` alone for the candidates idx_dev[0 .. *count_dev − 1] (int32 indices into the
+ * N candidates, *count_dev ≤ N, both on the device): μ̃ and ε go to mu_dev[idx], eps_dev[idx] (N each, the objective's
+ * own row) with the bits omb_posterior_screen gives them; unlisted slots are left alone.  The staged arg-max path's
+ * second screen (OMB_DEBUG_ARGMAX_STAGED). */
+int omb_posterior_screen_list(omb_ctx* ctx, const double* Xc_dev, int64_t N, const int32_t* idx_dev,
+                               const int32_t* count_dev, int obj, double* mu_dev, double* eps_dev);
 
 /* EHVI for 2 objectives (util_functions.py:136-167 + EHVI_2D_aux :81-128).
  *   pf_sorted_dev (P, 2): Pareto front sorted by f2 ascending (util_functions.py:98)
@@ -376,6 +392,10 @@ int omb_nondominated_stats(omb_ctx* ctx, int64_t* survivors_host, int* rounds_ho
  * the candidates past the seed whose bound kept them.  [2] is stored by the call's kernels: it is that call's once
  * its result has been waited for.  All 0 after a dense call.  Host values; nothing is launched and nothing is waited for. */
 int omb_argmax_prune_stats(omb_ctx* ctx, int64_t* stats_host);
+/* The same call's staged order (OMB_DEBUG_ARGMAX_STAGED): stats_host[0] = 1 if it took it; [1] the candidates past the
+ * seed that objective 1's bound kept (list A); [2] those of them that the full bound kept (list B, omb_argmax_prune_stats'
+ * [2]).  [1] and [2] are stored by the call's kernels, as above.  All 0 otherwise. */
+int omb_argmax_stage_stats(omb_ctx* ctx, int64_t* stats_host);
 
 /* Hypervolume-based PoI of EMO (emo.py:176-228): cells_dev (C, 2, 2) [upper, lower]. */
 int omb_hvpoi(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,

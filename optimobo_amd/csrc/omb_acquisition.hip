@@ -769,8 +769,9 @@ hipError_t launch_pof_scale(hipStream_t stream, int c, const double* mu, const d
 // kernel's own sum (each stripe a dozen rounded operations on terms of that size).  A NaN on either side compares
 // false and keeps the candidate; so does τ ≤ 0.  Strict "<": a candidate tied with τ stays.
 
-// One allocation: the pairs, τ, the counts, the two lists, the per-workgroup counts, the flags, the margined bounds and
-// the screen's μ̃ and ε rows, 16-byte aligned each.
+// One allocation: the pairs, τ, the counts, the two lists, the per-workgroup counts, the flags, the margined bounds,
+// the screen's μ̃ and ε rows, and the staged order's list A with its own per-workgroup counts, 16-byte
+// aligned each.
 static int64_t prune_ws_layout(char* base, int64_t N, PruneWs* ws) {
   int64_t off = 0;
   auto take = [&](int64_t bytes) {
@@ -788,6 +789,8 @@ static int64_t prune_ws_layout(char* base, int64_t N, PruneWs* ws) {
   ws->ubm = reinterpret_cast<double*>(take(sizeof(double) * N));
   ws->scr_mu = reinterpret_cast<double*>(take(sizeof(double) * 2 * N));
   ws->scr_eps = reinterpret_cast<double*>(take(sizeof(double) * 2 * N));
+  ws->list_a = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * N));
+  ws->block_cnt_b = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * ((N + kPruneBlock - 1) / kPruneBlock)));
   ws->stats_host = nullptr;
   return off;
 }
@@ -1117,6 +1120,190 @@ hipError_t launch_prune_threshold(hipStream_t stream, int64_t N, const PruneWs& 
                      ws.tau, N, ws.keep, ws.block_cnt);
   const hipError_t e = hipGetLastError();
   return e != hipSuccess ? e : launch_prune_compact(stream, N, ws);
+}
+
+// ------------------------------------------------------------------- the staged order: objective 1 first
+// The second factor of the bound, h(μ₀) = ψ(a, a, μ₀, sA) − (b − μ₀)⁺, rises below b and falls above it, so over all μ₀
+// it is at most C_i = ψ(a_i, a_i, b_i, sA) = sA·φ((a_i − b_i)/sA) + (a_i − b_i)·Φ((a_i − b_i)/sA), and
+//     value ≤ UB ≤ UB₁(μ₁) = Σ_i C_i·ψ(y2_i, y2_i, μ₁, sB)
+// needs objective 1's mean alone.  One workgroup per seed group as prune_bound_seed_kernel; the prologue computes C_i
+// and W_i = |a_i| + |b_i| + 2M₀ + sA into LDS, M₀ = σ_f²(0)·Σ_k |α_k(0)|·(1 + 2⁻²⁰) ≥ |μ₀| of the fp64 kernels (every
+// computed kernel value is at most 1 + 4e-14), so that tiny1 = 64·2⁻⁵²·Σ_i p2_i·W_i + 1e-300 is at least §29's tiny
+// and ubm1 = ub1·(1 + 1e-9) + tiny1 ≥ the value as the fp64 kernels compute it.  m1 is the low end μ̃₁ − ε₁.
+// The group's seed is the candidate with the smallest μ̃₁ — UB₁ decreases in μ₁, so this is the largest UB₁ at the centre
+// of the interval, the better guess where the margins differ from candidate to candidate (any candidate is a valid
+// seed; only the threshold needs the rigorous low end) — under prune_bound_seed_kernel's rules: the lowest index on
+// ties, a NaN never compares, the group's first candidate where none does.
+__global__ __launch_bounds__(kPruneBlock) void prune_bound1_seed_kernel(
+    const double* __restrict__ mu1, const double* __restrict__ eps1, int64_t N, const double* __restrict__ pf, int P,
+    double r0, double sA, double sB, const double* __restrict__ alpha0, int n0, double var0, double* __restrict__ ubm,
+    int32_t* __restrict__ seed_idx, int32_t* __restrict__ counts) {
+#pragma clang fp contract(off)
+  extern __shared__ double sm[];
+  double* y1 = sm;              // P + 1
+  double* y2 = sm + P + 1;      // P
+  double* Ci = y2 + P;          // P
+  double* Wi = Ci + P;          // P
+  __shared__ double red_v[kPruneBlock / 64];
+  __shared__ long long red_i[kPruneBlock / 64];
+  __shared__ double red_a[kPruneBlock / 64];
+  for (int i = threadIdx.x; i < P; i += blockDim.x) {
+    y1[i + 1] = pf[2 * i];
+    y2[i] = pf[2 * i + 1];
+  }
+  if (threadIdx.x == 0) y1[0] = r0;
+  double sa = 0.0;
+  for (int k = threadIdx.x; k < n0; k += blockDim.x) sa += fabs(alpha0[k]);
+  for (int o = 32; o > 0; o >>= 1) sa += __shfl_xor(sa, o);
+  if ((threadIdx.x & 63) == 0) red_a[threadIdx.x >> 6] = sa;
+  __syncthreads();
+  double M0 = 0.0;
+  for (int w = 0; w < kPruneBlock / 64; ++w) M0 += red_a[w];
+  M0 = var0 * M0 * (1.0 + 0x1p-20);
+  const double iA = 1.0 / sA, iB = 1.0 / sB;
+  for (int i = threadIdx.x; i < P; i += blockDim.x) {
+    const double a = y1[i], b = y1[i + 1];
+    const double dab = a - b, t = dab * iA;
+    Ci[i] = sA * npdf_fast(t) + dab * ndtr_fast(t);
+    Wi[i] = fabs(a) + fabs(b) + 2.0 * M0 + sA;
+  }
+  __syncthreads();
+  const int64_t first = (int64_t)blockIdx.x * kPruneSeedGroup;
+  double bv = -__builtin_inf();
+  long long bi = -1;
+#pragma unroll 1
+  for (int j = 0; j < kPruneSeedGroup / kPruneBlock; ++j) {
+    const int64_t c = first + j * kPruneBlock + threadIdx.x;
+    if (c < N) {
+      const double mc = mu1[c];
+      const double m1 = mc - eps1[c];
+      double ub = 0.0, scale = 0.0;
+      for (int i = 0; i < P; ++i) {
+        const double dy = y2[i] - m1;
+        const double u = dy * iB;
+        const double p2 = fmax(sB * npdf_fast(u) + dy * ndtr_fast(u), 0.0);
+        ub += Ci[i] * p2;
+        scale += p2 * Wi[i];
+      }
+      const double tiny = 64.0 * 0x1p-52 * scale + 1e-300;
+      const double v = ub * (1.0 + 1e-9) + tiny;
+      ubm[c] = v;
+      const double score = -mc;
+      if (score == score && argmax_better(score, c, bv, bi)) {
+        bv = score;
+        bi = c;
+      }
+    }
+  }
+  argmax_wave_block(bv, bi, red_v, red_i);
+  if (threadIdx.x == 0) {
+    seed_idx[blockIdx.x] = (int32_t)(bi < 0 ? first : bi);
+    if (blockIdx.x == 0) counts[0] = (int32_t)gridDim.x;
+  }
+}
+
+// The full interval bound on list A: thread j takes idx_a[j], j < *count_a, and keeps it unless τ > 0 and ubm < τ
+// (prune_ubm<true>, the one copy).  Flags and per-workgroup counts over list positions; a workgroup past the count
+// writes a zero count and leaves.
+__global__ __launch_bounds__(kPruneBlock) void prune_bound_list_kernel(
+    const double* __restrict__ mu0, const double* __restrict__ mu1, const double* __restrict__ eps0,
+    const double* __restrict__ eps1, const int32_t* __restrict__ idx_a, const int32_t* __restrict__ count_a,
+    int64_t cap, const double* __restrict__ pf, int P, double r0, double sA, double sB,
+    const double* __restrict__ tau, uint8_t* __restrict__ keep, int32_t* __restrict__ block_cnt) {
+#pragma clang fp contract(off)
+  extern __shared__ double sm[];
+  double* y1 = sm;
+  double* y2 = sm + P + 1;
+  __shared__ int wave_cnt[kPruneBlock / 64];
+  const int64_t na = min((int64_t)*count_a, cap);
+  if ((int64_t)blockIdx.x * kPruneBlock >= na) {
+    if (threadIdx.x == 0) block_cnt[blockIdx.x] = 0;
+    return;
+  }
+  for (int i = threadIdx.x; i < P; i += blockDim.x) {
+    y1[i + 1] = pf[2 * i];
+    y2[i] = pf[2 * i + 1];
+  }
+  if (threadIdx.x == 0) y1[0] = r0;
+  __syncthreads();
+  const int64_t j = (int64_t)blockIdx.x * kPruneBlock + threadIdx.x;
+  const double t = tau[0];
+  bool k = false;
+  if (j < na) {
+    k = true;
+    if (t > 0.0) {
+      const int64_t c = idx_a[j];
+      const double e0 = eps0[c];
+      if (prune_ubm<true>(mu0[c] - e0, mu1[c] - eps1[c], e0, y1, y2, P, sA, sB) < t) k = false;
+    }
+    keep[j] = k ? 1 : 0;
+  }
+  const int nw = __popcll(__ballot(k));
+  if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = nw;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int s = 0;
+    for (int w = 0; w < kPruneBlock / 64; ++w) s += wave_cnt[w];
+    block_cnt[blockIdx.x] = s;
+  }
+}
+
+// The list form of prune_compact_kernel: idx_b[rank] = idx_a[j] for the kept positions j < *count_a, ascending.
+__global__ __launch_bounds__(kPruneBlock) void prune_compact_list_kernel(
+    const uint8_t* __restrict__ keep, const int32_t* __restrict__ idx_a, const int32_t* __restrict__ count_a,
+    int64_t cap, const int32_t* __restrict__ block_off, int32_t* __restrict__ idx_b) {
+  __shared__ int wave_cnt[kPruneBlock / 64];
+  const int64_t na = min((int64_t)*count_a, cap);
+  if ((int64_t)blockIdx.x * kPruneBlock >= na) return;
+  const int64_t j = (int64_t)blockIdx.x * kPruneBlock + threadIdx.x;
+  const bool k = j < na && keep[j] != 0;
+  const unsigned long long b = __ballot(k);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) wave_cnt[wave] = __popcll(b);
+  __syncthreads();
+  int pos = block_off[blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));
+  for (int w = 0; w < wave; ++w) pos += wave_cnt[w];
+  if (k) idx_b[pos] = idx_a[j];
+}
+
+hipError_t launch_prune_bound1_seed(hipStream_t stream, const double* mu1, const double* eps1, int64_t N,
+                                    const double* pf, int P, double r0, double s00, double s01, double sf2,
+                                    const double* alpha0, int n0, const PruneWs& ws) {
+  const int64_t ng = (N + kPruneSeedGroup - 1) / kPruneSeedGroup;
+  if (N < 1 || ng > (1 << 23) || !mu1 || !eps1 || !alpha0 || n0 < 0) return hipErrorInvalidValue;
+  const size_t shm = sizeof(double) * (4 * P + 1);
+  hipLaunchKernelGGL(prune_bound1_seed_kernel, dim3((unsigned)ng), dim3(kPruneBlock), shm, stream, mu1, eps1, N, pf, P,
+                     r0, sf2 * s00, sf2 * s01, alpha0, n0, sf2, ws.ubm, ws.seed_idx, ws.counts);
+  return hipGetLastError();
+}
+
+hipError_t launch_prune_threshold_a(hipStream_t stream, int64_t N, const PruneWs& ws) {
+  // prune_threshold_kernel, the scan and the compaction as they are, into list A: its count to counts[2] and
+  // stats_host[1]
+  PruneWs a = ws;
+  a.surv_idx = ws.list_a;
+  a.counts = ws.counts + 1;
+  a.stats_host = ws.stats_host ? ws.stats_host + 1 : nullptr;
+  return launch_prune_threshold(stream, N, a);
+}
+
+hipError_t launch_prune_bound_list(hipStream_t stream, const double* mu0, const double* mu1, const double* eps0,
+                                   const double* eps1, int64_t cap, const double* pf, int P, double r0, double s00,
+                                   double s01, double sf2, const PruneWs& ws) {
+  const int64_t nb = (cap + kPruneBlock - 1) / kPruneBlock;
+  if (cap < 1 || nb > (1 << 23) || !eps0 || !eps1) return hipErrorInvalidValue;
+  const size_t shm = sizeof(double) * (2 * P + 1);
+  hipLaunchKernelGGL(prune_bound_list_kernel, dim3((unsigned)nb), dim3(kPruneBlock), shm, stream, mu0, mu1, eps0, eps1,
+                     ws.list_a, ws.counts + 2, cap, pf, P, r0, sf2 * s00, sf2 * s01, ws.tau, ws.keep, ws.block_cnt_b);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(1024), 0, stream, ws.block_cnt_b, (int)nb, ws.counts,
+                     ws.stats_host);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(prune_compact_list_kernel, dim3((unsigned)nb), dim3(kPruneBlock), 0, stream, ws.keep, ws.list_a,
+                     ws.counts + 2, cap, ws.block_cnt_b, ws.surv_idx);
+  return hipGetLastError();
 }
 
 }  // namespace omb

@@ -127,6 +127,8 @@ struct omb_ctx {
   int64_t prune_seed = 0;
   int64_t* prune_stats_host = nullptr;
   int64_t* prune_stats_dev = nullptr;
+  // omb_argmax_stage_stats: whether it took the staged order; |A| is prune_stats_host[1], |B| is [0]
+  int stage_taken = 0;
   int nd_rounds = 0;                              // omb_nondominated_stats: the last call's tile passes
   int64_t nd_survivors[kNdMaxRounds + 1] = {};    // and the largest set's survivors after each
   // device fault word (pinned, mapped host memory): kernels mark it, enter() reports it
@@ -155,6 +157,7 @@ struct omb_ctx {
   int posterior_mean_kernel = kMeanKernelAfter;   // OMB_DEBUG_POSTERIOR_MEAN_KERNEL: masked objectives' μ in a launch of its own
   int argmax_prune = 1;          // OMB_DEBUG_ARGMAX_PRUNE: 0 dense, 1 two-phase (seed by bound) from kPruneMinN
                                  // candidates, 2 the strided seed at any N, 3 the seed by bound at any N
+  int argmax_staged = 1;         // OMB_DEBUG_ARGMAX_STAGED: 1 objective 1's screen and bound first, 0 §31's order
   int argmax_screen = 1;         // OMB_DEBUG_ARGMAX_SCREEN: the two-phase path's bound from 1 the fp32 screen, 0 fp64 means
 };
 
@@ -632,10 +635,14 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
   // The seed: each group's best bound — or, under OMB_DEBUG_ARGMAX_PRUNE 2, the strided sample of §29
   const bool seed_by_bound = ctx->argmax_prune != 2;
   const int64_t seed_step = seed_by_bound ? kPruneSeedGroup : kPruneStride;
+  // The staged order where the seed by bound runs on the screen: objective 1's screen and its bound for
+  // all N, objective 0's screen and the full bound only for those that pass
+  const bool staged = two_phase && seed_by_bound && ctx->argmax_screen != 0 && ctx->argmax_staged != 0;
   if (two_phase && (rc = grow_dev(ctx, ctx->prws, (size_t)prune_ws_bytes(N), "arg-max pruning workspace"))) return rc;
   if (result_dev) {
     ctx->prune_taken = two_phase ? 1 : 0;
     ctx->prune_seed = two_phase ? (N + seed_step - 1) / seed_step : 0;
+    ctx->stage_taken = staged ? 1 : 0;
   }
   double* mu = ctx->work.as<double>();
   double* var = mu + (size_t)K * nd;
@@ -708,8 +715,12 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
     // the means and the bound come first; the seed is each group's best bound, so τ is (nearly) the
     // maximum and the threshold kernel leaves a handful of survivors.  §29's order: the strided seed, then the bound.
     if (e == hipSuccess && seed_by_bound && screen)
-      e = launch_posterior_screen(ctx->stream, args, 3u, Xc, N, ws.scr_mu, ws.scr_eps);
-    if (e == hipSuccess && seed_by_bound)
+      e = launch_posterior_screen(ctx->stream, args, staged ? 2u : 3u, Xc, N, ws.scr_mu, ws.scr_eps);
+    // ubm1 from μ̃₁ − ε₁ alone bounds the full bound for every μ₀, so the seed and list A come from it
+    if (e == hipSuccess && staged)
+      e = launch_prune_bound1_seed(ctx->stream, ws.scr_mu + nd, ws.scr_eps + nd, N, pl.geo, pl.P, pl.r[0], pl.s00,
+                                   pl.s01, sf2, args.gp[0].alpha, args.gp[0].n, ws);
+    if (e == hipSuccess && seed_by_bound && !staged)
       e = launch_prune_bound_seed(ctx->stream, bm, bm + nd, N, pl.geo, pl.P, pl.r[0], pl.s00, pl.s01, sf2, ws, be0,
                                   be1);
     if (e == hipSuccess && !seed_by_bound) e = launch_prune_seed(ctx->stream, N, ws);
@@ -721,7 +732,21 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
       e = launch_ehvi2d_argmax_list(ctx->stream, mu_c, var_c, mu + nd, ws.seed_idx, ws.counts, ns, pl.geo, pl.P,
                                     pl.r[0], pl.r[1], pl.s00, pl.s01, pl.mode, ws.partials);
     if (e == hipSuccess) e = launch_argmax_reduce(ctx->stream, ws.partials, nbs, 0, ws.tau);
-    if (e == hipSuccess && seed_by_bound) e = launch_prune_threshold(ctx->stream, N, ws);
+    if (e == hipSuccess && seed_by_bound && !staged) e = launch_prune_threshold(ctx->stream, N, ws);
+    if (staged && nv == 0) {
+      // N = 1, nothing but the seed: both lists empty, their counts and stats words written in stream order
+      if (e == hipSuccess) e = launch_prune_threshold_a(ctx->stream, N, ws);
+      if (e == hipSuccess) e = launch_prune_threshold(ctx->stream, N, ws);
+    } else if (staged) {
+      // list A by the threshold on ubm1, objective 0's screen for list A, the full interval bound on list A → list B
+      if (e == hipSuccess) e = launch_prune_threshold_a(ctx->stream, N, ws);
+      if (e == hipSuccess)
+        e = launch_posterior_screen_gather(ctx->stream, args, 0, Xc, ws.list_a, ws.counts + 2, nv, ws.scr_mu,
+                                           ws.scr_eps);
+      if (e == hipSuccess)
+        e = launch_prune_bound_list(ctx->stream, ws.scr_mu, ws.scr_mu + nd, ws.scr_eps, ws.scr_eps + nd, nv, pl.geo,
+                                    pl.P, pl.r[0], pl.s00, pl.s01, sf2, ws);
+    }
     if (e == hipSuccess && !seed_by_bound && screen)
       e = launch_posterior_screen(ctx->stream, args, 3u, Xc, N, ws.scr_mu, ws.scr_eps);
     if (e == hipSuccess && !seed_by_bound)
@@ -796,7 +821,7 @@ int omb_create(int device, omb_ctx** out) {
     return OMB_ENOMEM;
   }
   *ctx->fault_host = 0;
-  ctx->prune_stats_host[0] = 0;
+  ctx->prune_stats_host[0] = ctx->prune_stats_host[1] = 0;
   ctx->stream = ctx->own_stream;
   *out = ctx;
   return OMB_OK;
@@ -874,6 +899,7 @@ static const DebugSwitch kDebugSwitches[] = {
      "arg-max pruning %lld (0 dense, 1 two-phase for large batches, 2 strided seed at any size, 3 seed by bound at "
      "any size)"},
     {OMB_DEBUG_ARGMAX_SCREEN, &omb_ctx::argmax_screen, 0, 1, nullptr},
+    {OMB_DEBUG_ARGMAX_STAGED, &omb_ctx::argmax_staged, 0, 1, nullptr},
 };
 
 int omb_debug_set(omb_ctx* ctx, int what, int64_t value) {
@@ -1099,6 +1125,24 @@ int omb_posterior_screen(omb_ctx* ctx, const double* Xc_dev, int64_t N, int n_ob
   return OMB_OK;
 }
 
+int omb_posterior_screen_list(omb_ctx* ctx, const double* Xc_dev, int64_t N, const int32_t* idx_dev,
+                               const int32_t* count_dev, int obj, double* mu_dev, double* eps_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if (N < 0 || (N > 0 && (!Xc_dev || !idx_dev || !count_dev || !mu_dev || !eps_dev)))
+    return fail(ctx, OMB_EINVAL, "bad candidate/list/output arguments");
+  if (obj < 0 || obj >= OMB_MAX_OBJ) return fail(ctx, OMB_EINVAL, "objective %d", obj);
+  GPArgs args;
+  int max_R = 0;
+  if ((rc = gather_gp(ctx, obj + 1, &args, &max_R))) return rc;
+  if (args.DP > 8) return fail(ctx, OMB_EUNSUP, "the screened mean needs n_var <= 8 (n_var=%d)", args.d);
+  if (N == 0) return OMB_OK;
+  if ((N + 15) / 16 > 0x7fffffffLL) return fail(ctx, OMB_EUNSUP, "N=%lld too large", (long long)N);
+  hipError_t e = launch_posterior_screen_gather(ctx->stream, args, obj, Xc_dev, idx_dev, count_dev, N, mu_dev, eps_dev);
+  if (e != hipSuccess) return hip_fail(ctx, e, "posterior_screen_list");
+  return OMB_OK;
+}
+
 int omb_ehvi2d(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,
                const double* pf_sorted_dev, int P, const double* r_host, double s00, double s01, int mode,
                double* out_dev) {
@@ -1302,6 +1346,15 @@ int omb_argmax_prune_stats(omb_ctx* ctx, int64_t* stats_host) {
   stats_host[0] = ctx->prune_taken;
   stats_host[1] = ctx->prune_seed;
   stats_host[2] = ctx->prune_taken ? __atomic_load_n(ctx->prune_stats_host, __ATOMIC_ACQUIRE) : 0;
+  return OMB_OK;
+}
+
+int omb_argmax_stage_stats(omb_ctx* ctx, int64_t* stats_host) {
+  if (!ctx) return OMB_EINVAL;
+  if (!stats_host) return fail(ctx, OMB_EINVAL, "null output");
+  stats_host[0] = ctx->stage_taken;
+  stats_host[1] = ctx->stage_taken ? __atomic_load_n(ctx->prune_stats_host + 1, __ATOMIC_ACQUIRE) : 0;
+  stats_host[2] = ctx->stage_taken ? __atomic_load_n(ctx->prune_stats_host, __ATOMIC_ACQUIRE) : 0;
   return OMB_OK;
 }
 

@@ -96,6 +96,12 @@ hipError_t launch_posterior_mean_gather(hipStream_t stream, const GPArgs& args, 
                                         const int32_t* idx, const int32_t* count, int64_t cap, double* mu_row);
 hipError_t launch_posterior_screen(hipStream_t stream, const GPArgs& args, unsigned objs, const double* Xc, int64_t N,
                                    double* mu, double* eps);
+//   launch_posterior_screen_gather  μ̃ and ε of objective `obj` for the listed candidates by posterior_screen_kernel's
+//                                   gathered instantiation, to mu_row[idx[p]], eps_row[idx[p]]: the dense
+//                                   launch's bits
+hipError_t launch_posterior_screen_gather(hipStream_t stream, const GPArgs& args, int obj, const double* Xc,
+                                          const int32_t* idx, const int32_t* count, int64_t cap, double* mu_row,
+                                          double* eps_row);
 
 // Pruning of the EHVI-2D arg-max in OMB_EHVI_REFERENCE (omb_acquisition.hip).  A list is int32 indices into the batch
 // with a device-side count; "seed" is the strided sample 0, kPruneStride, 2·kPruneStride, … or,
@@ -109,16 +115,22 @@ static_assert(kPruneSeedGroup % kPruneBlock == 0 && kPruneSeedGroup >= kPruneStr
 struct PruneWs {
   int32_t* seed_idx;     // ⌈N/kPruneStride⌉ (the seed by bound uses the first ⌈N/kPruneSeedGroup⌉)
   int32_t* surv_idx;     // N
-  int32_t* counts;       // [0] seed count, [1] survivor count
+  int32_t* counts;       // [0] seed count, [1] survivor count, [2] the staged order's list A count
   int32_t* block_cnt;    // ⌈N/kPruneBlock⌉ survivors per workgroup, then (in place) their exclusive prefix sums
-  uint8_t* keep;         // N flags
-  double* ubm;           // N margined bounds ub·(1 + 1e-9) + tiny (the seed by bound)
+  uint8_t* keep;         // N flags (the staged order's second compaction: over list A positions)
+  double* ubm;           // N margined bounds ub·(1 + 1e-9) + tiny (the seed by bound; staged: ubm1)
   double* scr_mu;        // (2, N) the screen's μ̃
   double* scr_eps;       // (2, N) its margins ε
   double* partials;      // 2 × kArgmaxMaxBlocks (value, index) pairs: the seed's, then the survivors'
   double* tau;           // {τ, its index}: the seed sample's arg-max
-  int64_t* stats_host;   // pinned, device-mapped: [0] the survivor count of the last call (a system-scope store)
+  int32_t* list_a;       // N: the staged order's list A, the candidates objective 1's bound leaves
+  int32_t* block_cnt_b;  // ⌈N/kPruneBlock⌉: the full bound's kept count per workgroup of list A positions, then offsets
+  int64_t* stats_host;   // pinned, device-mapped: [0] the survivor count of the last call (a system-scope store),
+                         // [1] the staged order's list A count
 };
+// ≈ 49.3·N bytes: 45.3·N of the two lists' first (seed_idx N/4, surv_idx 4N), block_cnt N/64, keep N, ubm 8N and the
+// screen's rows 32N, and the staged order's list_a 4N and block_cnt_b N/64.  The staged order stores ubm1 in the ubm row
+// and reuses keep for its second compaction's flags.
 int64_t prune_ws_bytes(int64_t N);
 void prune_ws_carve(void* base, int64_t N, PruneWs* ws);
 // seed_idx and counts[0]
@@ -147,6 +159,21 @@ hipError_t launch_prune_bound_seed(hipStream_t stream, const double* mu0, const 
                                    const double* pf, int P, double r0, double s00, double s01, double sf2,
                                    const PruneWs& ws, const double* eps0 = nullptr, const double* eps1 = nullptr);
 hipError_t launch_prune_threshold(hipStream_t stream, int64_t N, const PruneWs& ws);
+// The staged order: objective 1's screen alone decides who gets objective 0's.
+//   launch_prune_bound1_seed  ubm1 = ub1·(1 + 1e-9) + tiny1 from μ̃₁ − ε₁ alone (ub1 = Σ_i C_i·ψ(y2_i, y2_i, ·, σ_f²·s01),
+//                             C_i the supremum over μ₀ of the bound's second factor; alpha0, n0: objective 0's α row
+//                             for M₀ ≥ |μ₀|) to ws.ubm, and the seed of launch_prune_bound_seed by it
+//   launch_prune_threshold_a  launch_prune_threshold into ws.list_a, its count to counts[2] and stats_host[1]
+//   launch_prune_bound_list   the interval bound of launch_prune_bound (mu0, eps0 at original slots) for list A's
+//                             candidates alone against *ws.tau; the kept ones, ascending, to surv_idx, counts[1],
+//                             stats_host[0].  cap: list A's capacity
+hipError_t launch_prune_bound1_seed(hipStream_t stream, const double* mu1, const double* eps1, int64_t N,
+                                    const double* pf, int P, double r0, double s00, double s01, double sf2,
+                                    const double* alpha0, int n0, const PruneWs& ws);
+hipError_t launch_prune_threshold_a(hipStream_t stream, int64_t N, const PruneWs& ws);
+hipError_t launch_prune_bound_list(hipStream_t stream, const double* mu0, const double* mu1, const double* eps0,
+                                   const double* eps1, int64_t cap, const double* pf, int P, double r0, double s00,
+                                   double s01, double sf2, const PruneWs& ws);
 
 // EHVI-2D and the arg-max in one launch (omb_acquisition.hip): each workgroup's (value, index) pair goes to
 // `partials` (2 doubles per workgroup, ehvi2d_argmax_blocks(N) ≤ kArgmaxMaxBlocks); the last workgroup to finish (an

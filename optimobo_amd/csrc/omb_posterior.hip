@@ -1413,10 +1413,15 @@ __device__ __forceinline__ void screen_tile(const d4& cr, const double (&al)[4],
   }
 }
 
-template <int DP, int KIND>
+// GATHER (launch_posterior_screen_gather, an instantiation of its own as posterior_mean_kernel's): the
+// columns are 16 entries each of the device-side list args.idx[0 .. *args.count − 1] (N is the list's capacity), one
+// objective per launch, and μ̃, ε go to the candidate's *original* slot of the objective's own rows mu_out, eps_out.  A
+// wave past the count leaves.  A candidate's μ̃ and ε do not depend on its column: the dense launch's bits.
+template <int DP, int KIND, bool GATHER = false>
 __global__ __launch_bounds__(64 * kMeanWaves, DP == 8 ? 3 : 4) void posterior_screen_kernel(
     GPArgs args, const double* __restrict__ Xc, int64_t N, double* __restrict__ mu_out, double* __restrict__ eps_out) {
   static_assert(DP <= 8, "the candidates' B fragments live in registers");
+  if constexpr (GATHER) N = min((int64_t)*args.count, N);
   using GS = GenShape<DP, KIND, 0>;
   constexpr int KSD = GS::KSD;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1439,7 +1444,8 @@ __global__ __launch_bounds__(64 * kMeanWaves, DP == 8 ? 3 : 4) void posterior_sc
     lsl[s] = g.ls[jl[s]];
   }
   auto load_raw = [&](int64_t c, double (&x)[KSD]) {
-    const int64_t ci = min(16 * c + (lane & 15), N - 1);
+    int64_t ci = min(16 * c + (lane & 15), N - 1);
+    if constexpr (GATHER) ci = args.idx[ci];
 #pragma unroll
     for (int s = 0; s < KSD; ++s) x[s] = Xc[ci * d + jl[s]];
   };
@@ -1493,8 +1499,9 @@ __global__ __launch_bounds__(64 * kMeanWaves, DP == 8 ? 3 : 4) void posterior_sc
     S += __shfl_xor(S, 32);
     const int64_t c = 16 * col + lane;
     if (lane < 16 && c < N) {
-      mu_out[(int64_t)obj * N + c] = g.variance * acc;
-      eps_out[(int64_t)obj * N + c] = fma(0x1p-24 * (1.0 + 0x1p-10) * g.variance, (double)S, 0x1p-64 * g.variance);
+      const int64_t o = GATHER ? (int64_t)args.idx[c] : (int64_t)obj * N + c;
+      mu_out[o] = g.variance * acc;
+      eps_out[o] = fma(0x1p-24 * (1.0 + 0x1p-10) * g.variance, (double)S, 0x1p-64 * g.variance);
     }
   }
 }
@@ -2206,21 +2213,46 @@ static hipError_t launch_posterior_screen_dp(hipStream_t stream, const GPArgs& a
   return hipGetLastError();
 }
 
-// which = 0: the gathered mean launch (N the list's capacity, mu the objective's row); 1: the screen (eps its margins)
+// the gathered screen of the one objective in args.obj_sel over the list args.idx / args.count (capacity cap)
+template <int DP, int KIND>
+static hipError_t launch_posterior_screen_gather_dp(hipStream_t stream, const GPArgs& args, const double* Xc,
+                                                    int64_t cap, double* mu_row, double* eps_row) {
+  static int per_cu = 0;
+  if (per_cu == 0) {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, posterior_screen_kernel<DP, KIND, true>, 64 * kMeanWaves,
+                                                     0) != hipSuccess || nb <= 0)
+      nb = 4;
+    per_cu = nb;
+  }
+  const int64_t wgs = ((cap + 15) / 16 + kMeanWaves - 1) / kMeanWaves;
+  const int64_t resident = (int64_t)per_cu * device_cu_count();
+  const dim3 grid((unsigned)std::max<int64_t>(1, std::min(wgs, resident)), 1);
+  hipLaunchKernelGGL((posterior_screen_kernel<DP, KIND, true>), grid, dim3(64 * kMeanWaves), 0, stream, args, Xc, cap,
+                     mu_row, eps_row);
+  return hipGetLastError();
+}
+
+// which = 0: the gathered mean launch (N the list's capacity, mu the objective's row); 1: the screen (eps its margins);
+// 2: the gathered screen (N the capacity, mu and eps the objective's rows)
 template <int KIND>
 static hipError_t launch_posterior_screen_kind(hipStream_t stream, const GPArgs& args, int which, const double* Xc,
                                                int64_t N, double* mu, double* eps) {
   switch (args.DP) {
     case 2:
+      if (which == 2) return launch_posterior_screen_gather_dp<2, KIND>(stream, args, Xc, N, mu, eps);
       return which ? launch_posterior_screen_dp<2, KIND>(stream, args, Xc, N, mu, eps)
                    : launch_posterior_mean_gather_dp<2, KIND>(stream, args, Xc, N, mu);
     case 4:
+      if (which == 2) return launch_posterior_screen_gather_dp<4, KIND>(stream, args, Xc, N, mu, eps);
       return which ? launch_posterior_screen_dp<4, KIND>(stream, args, Xc, N, mu, eps)
                    : launch_posterior_mean_gather_dp<4, KIND>(stream, args, Xc, N, mu);
     case 6:
+      if (which == 2) return launch_posterior_screen_gather_dp<6, KIND>(stream, args, Xc, N, mu, eps);
       return which ? launch_posterior_screen_dp<6, KIND>(stream, args, Xc, N, mu, eps)
                    : launch_posterior_mean_gather_dp<6, KIND>(stream, args, Xc, N, mu);
     case 8:
+      if (which == 2) return launch_posterior_screen_gather_dp<8, KIND>(stream, args, Xc, N, mu, eps);
       return which ? launch_posterior_screen_dp<8, KIND>(stream, args, Xc, N, mu, eps)
                    : launch_posterior_mean_gather_dp<8, KIND>(stream, args, Xc, N, mu);
     default: return hipErrorInvalidValue;
@@ -2251,6 +2283,20 @@ hipError_t launch_posterior_screen(hipStream_t stream, const GPArgs& args_in, un
   if (args.gp[0].kind == OMB_KERNEL_RBF)
     return launch_posterior_screen_kind<OMB_KERNEL_RBF>(stream, args, 1, Xc, N, mu, eps);
   return launch_posterior_screen_kind<OMB_KERNEL_MATERN52>(stream, args, 1, Xc, N, mu, eps);
+}
+
+hipError_t launch_posterior_screen_gather(hipStream_t stream, const GPArgs& args_in, int obj, const double* Xc,
+                                          const int32_t* idx, const int32_t* count, int64_t cap, double* mu_row,
+                                          double* eps_row) {
+  if (args_in.DP > 8 || obj < 0 || obj >= OMB_MAX_OBJ || !idx || !count || cap < 1) return hipErrorInvalidValue;
+  GPArgs args = args_in;
+  args.ec = exp_coef();
+  args.obj_sel = 1u << obj;
+  args.idx = idx;
+  args.count = count;
+  if (args.gp[obj].kind == OMB_KERNEL_RBF)
+    return launch_posterior_screen_kind<OMB_KERNEL_RBF>(stream, args, 2, Xc, cap, mu_row, eps_row);
+  return launch_posterior_screen_kind<OMB_KERNEL_MATERN52>(stream, args, 2, Xc, cap, mu_row, eps_row);
 }
 
 template <int KIND>

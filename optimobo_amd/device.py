@@ -105,7 +105,10 @@ class AcqContext:
         candidates on (default) / in two phases with the strided seed at any size / in two phases seeded by the
         bound at any size (bit-identical pair; see ``argmax_prune_stats``); ("argmax_screen", 0/1) feeds that path's
         bound fp64 means of every candidate / ``posterior_screen``'s means and margins (default; bit-identical
-        pair)."""
+        pair); ("argmax_staged", 0/1) runs the seeded-by-bound path with both objectives' screen and the full bound
+        for every candidate / staged (default): objective 1's screen and a bound from it alone for every candidate,
+        objective 0's screen and the full bound only for those it keeps — 0 is the order for batches where
+        objective 0 decides (bit-identical pair; see ``argmax_stage_stats``)."""
         code = getattr(_lib, "DEBUG_" + str(what).upper(), None)
         if code is None:
             raise KeyError(what)
@@ -176,6 +179,24 @@ class AcqContext:
         self._stream()
         self._check(self.lib.omb_posterior_screen(self._h, _ptr(Xc), N, n_obj, _ptr(mu), _ptr(eps)),
                     "omb_posterior_screen")
+        return mu, eps
+
+    def posterior_screen_list(self, Xc, idx, count, obj, mu, eps):
+        """omb_posterior_screen_list: ``posterior_screen`` of objective ``obj`` alone for the candidates
+        ``idx[:count]`` (int32 device tensors; ``count`` one element), written in place to ``mu[idx]``, ``eps[idx]``
+        (fp64 device rows of N) with ``posterior_screen``'s bits; unlisted slots are left alone."""
+        Xc = _dev_f64(Xc, self.device)
+        self._check_width(Xc, obj)
+        N = Xc.shape[0]
+        if idx.dtype != torch.int32 or count.dtype != torch.int32 or idx.numel() > N or count.numel() != 1:
+            raise ValueError("posterior_screen_list: idx (<= N) and count (1) must be int32 device tensors")
+        if mu.dtype != torch.float64 or eps.dtype != torch.float64 or mu.numel() != N or eps.numel() != N:
+            raise ValueError("posterior_screen_list: mu and eps must be fp64 rows of N")
+        if not (idx.is_contiguous() and mu.is_contiguous() and eps.is_contiguous()):
+            raise ValueError("posterior_screen_list: contiguous tensors only")
+        self._stream()
+        self._check(self.lib.omb_posterior_screen_list(self._h, _ptr(Xc), N, _ptr(idx), _ptr(count), int(obj),
+                                                       _ptr(mu), _ptr(eps)), "omb_posterior_screen_list")
         return mu, eps
 
     # ------------------------------------------------------------------ acquisitions
@@ -370,6 +391,14 @@ class AcqContext:
         waited for).  (False, 0, 0) after a dense call."""
         st = (ctypes.c_int64 * 3)()
         self._check(self.lib.omb_argmax_prune_stats(self._h, st), "omb_argmax_prune_stats")
+        return bool(st[0]), int(st[1]), int(st[2])
+
+    def argmax_stage_stats(self):
+        """omb_argmax_stage_stats: the same call → (staged, |A|, |B|): whether it took the staged order
+        ("argmax_staged"), the candidates past the seed that objective 1's bound kept, and those of them that the
+        full bound kept (``argmax_prune_stats``'s survivors).  (False, 0, 0) otherwise."""
+        st = (ctypes.c_int64 * 3)()
+        self._check(self.lib.omb_argmax_stage_stats(self._h, st), "omb_argmax_stage_stats")
         return bool(st[0]), int(st[1]), int(st[2])
 
     def hvpoi(self, mu, var, cells, out=None):
