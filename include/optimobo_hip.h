@@ -159,9 +159,15 @@ const char* omb_last_error(const omb_ctx* ctx);
  * candidate, a bound from it that holds for any mean of objective 0, the seed (the smallest screened mean of objective 1
  * in each run of 256 candidates) and a first list by that bound, and objective 0's screen and the full bound only for
  * that list; 0 both objectives' screen and the full bound for every candidate.  The staged order wins where objective 1's mean rules most candidates out; where objective 0 decides
- * (the first list keeps most of the batch) it costs an extra pass over the list — measured 8.4 % behind 0 at 2^20
- * candidates with the flagship's two objectives swapped, where the list keeps 83 % — and 0 is the order to use.  The
- * arg-max pair is bit-identical (omb_argmax_stage_stats reports the lists' sizes). */
+ * (the first list keeps most of the batch) it costs an extra pass over the list — measured 1.9 % behind 0 at 2^20
+ * candidates with the flagship's two objectives swapped, where the list keeps 83 % (8.4 % before the first list was
+ * drawn by a cut, OMB_DEBUG_ARGMAX_CUT) — and 0 is the order to use.  The
+ * arg-max pair is bit-identical (omb_argmax_stage_stats reports the lists' sizes).
+ * omb_debug_set(ctx, OMB_DEBUG_ARGMAX_CUT, m) picks how the staged order draws that first list: 1 (default) by one
+ * cut — objective 1's bound decreases in its one argument, the low end of the screened mean, so one workgroup solves
+ * bound(m*) = the seed's best value once per call and a candidate is dropped where its low end is at least m*; 0 by
+ * evaluating the bound for every candidate.  The lists agree but for candidates whose bound lies within 1e-7 of the
+ * seed's best value, and the arg-max pair is bit-identical (omb_argmax_cut_stats reports m*). */
 enum {
   OMB_DEBUG_SPIN_LIMIT = 1,
   OMB_DEBUG_COV_TABLE = 2,
@@ -179,7 +185,8 @@ enum {
   OMB_DEBUG_HVI_PATHS_CHUNK = 15,
   OMB_DEBUG_ARGMAX_PRUNE = 16,
   OMB_DEBUG_ARGMAX_SCREEN = 17,
-  OMB_DEBUG_ARGMAX_STAGED = 18
+  OMB_DEBUG_ARGMAX_STAGED = 18,
+  OMB_DEBUG_ARGMAX_CUT = 19
 };
 int omb_debug_set(omb_ctx* ctx, int what, int64_t value);
 
@@ -396,6 +403,11 @@ int omb_argmax_prune_stats(omb_ctx* ctx, int64_t* stats_host);
  * seed that objective 1's bound kept (list A); [2] those of them that the full bound kept (list B, omb_argmax_prune_stats'
  * [2]).  [1] and [2] are stored by the call's kernels, as above.  All 0 otherwise. */
 int omb_argmax_stage_stats(omb_ctx* ctx, int64_t* stats_host);
+/* The same call's cut (OMB_DEBUG_ARGMAX_CUT): stats_host[0] = 1 if the staged order drew its first list by the cut;
+ * [1] m*, the smallest value found whose bound lies below [2] τ₀, the seed's best value (+∞: nothing could be
+ * dropped); [3] the bound at m* (NaN where m* is +∞).  [1] to [3] are stored by the call's kernels, as above.  All 0
+ * otherwise. */
+int omb_argmax_cut_stats(omb_ctx* ctx, double* stats_host);
 
 /* Hypervolume-based PoI of EMO (emo.py:176-228): cells_dev (C, 2, 2) [upper, lower]. */
 int omb_hvpoi(omb_ctx* ctx, const double* mu_dev, const double* var_dev, int64_t ld, int64_t N,

@@ -37,6 +37,7 @@ DEBUG_HVI_PATHS_CHUNK = 15
 DEBUG_ARGMAX_PRUNE = 16
 DEBUG_ARGMAX_SCREEN = 17
 DEBUG_ARGMAX_STAGED = 18
+DEBUG_ARGMAX_CUT = 19
 MAX_OBJ, MAX_DIM, MAX_TRAIN, MAX_TRAIN_DENSE = 8, 256, 1024, 16384
 CON_VIOLATION = 1              # OMB_CON_VIOLATION: omb_hvi_paths_con's flag (infeasible paths score −violation)
 HVI_PATHS_CHUNK = 1 << 18      # OMB_HVI_PATHS_CHUNK: candidates per pass of the chain under plan_hvi_paths
@@ -78,6 +79,7 @@ SIGNATURES = {
     "omb_nondominated_stats": (_i, [_p, ctypes.POINTER(_i64), ctypes.POINTER(_i)]),
     "omb_argmax_prune_stats": (_i, [_p, ctypes.POINTER(_i64)]),
     "omb_argmax_stage_stats": (_i, [_p, ctypes.POINTER(_i64)]),
+    "omb_argmax_cut_stats": (_i, [_p, _dp]),
     "omb_hvpoi": (_i, [_p, _p, _p, _i64, _i64, _p, _i, _p]),
     "omb_expdec": (_i, [_p, _i, _p, _p, _i64, _i64, _p, _i, _i, _dp, _dp, _dp, _dp, _d, _p]),
     "omb_ei": (_i, [_p, _p, _p, _i64, _d, _d, _p]),

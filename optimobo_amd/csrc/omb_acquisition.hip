@@ -770,8 +770,8 @@ hipError_t launch_pof_scale(hipStream_t stream, int c, const double* mu, const d
 // false and keeps the candidate; so does τ ≤ 0.  Strict "<": a candidate tied with τ stays.
 
 // One allocation: the pairs, τ, the counts, the two lists, the per-workgroup counts, the flags, the margined bounds,
-// the screen's μ̃ and ε rows, and the staged order's list A with its own per-workgroup counts, 16-byte
-// aligned each.
+// the screen's μ̃ and ε rows, the staged order's list A with its own per-workgroup counts and the cut's
+// four doubles, 16-byte aligned each.
 static int64_t prune_ws_layout(char* base, int64_t N, PruneWs* ws) {
   int64_t off = 0;
   auto take = [&](int64_t bytes) {
@@ -791,6 +791,7 @@ static int64_t prune_ws_layout(char* base, int64_t N, PruneWs* ws) {
   ws->scr_eps = reinterpret_cast<double*>(take(sizeof(double) * 2 * N));
   ws->list_a = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * N));
   ws->block_cnt_b = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * ((N + kPruneBlock - 1) / kPruneBlock)));
+  ws->cut = reinterpret_cast<double*>(take(sizeof(double) * 4));
   ws->stats_host = nullptr;
   return off;
 }
@@ -1202,6 +1203,235 @@ __global__ __launch_bounds__(kPruneBlock) void prune_bound1_seed_kernel(
   }
 }
 
+// ------------------------------------------------------------ objective 1's bound as one cut on μ̃₁ − ε₁
+// UB₁ decreases in μ₁ and the seed needs no ψ, so stage 1 is a scalar cut: the seeds by the smallest μ̃₁ alone, one
+// workgroup solves ubm1(m*) = τ₀ after the seeds' τ₀ is known, and a candidate goes to list A unless μ̃₁ − ε₁ ≥ m*.
+// prune_bound1_seed_kernel's geometry and seed rule, bit for bit — the smallest comparable μ̃₁, the lowest index on
+// ties, a NaN never compares, the group's first candidate where none does, counts[0] — with no ψ, no prologue and no
+// ubm store.
+__global__ __launch_bounds__(kPruneBlock) void prune_seed1_kernel(const double* __restrict__ mu1, int64_t N,
+                                                                  int32_t* __restrict__ seed_idx,
+                                                                  int32_t* __restrict__ counts) {
+  __shared__ double red_v[kPruneBlock / 64];
+  __shared__ long long red_i[kPruneBlock / 64];
+  const int64_t first = (int64_t)blockIdx.x * kPruneSeedGroup;
+  double bv = -__builtin_inf();
+  long long bi = -1;
+  for (int j = 0; j < kPruneSeedGroup / kPruneBlock; ++j) {
+    const int64_t c = first + j * kPruneBlock + threadIdx.x;
+    if (c < N) {
+      const double score = -mu1[c];
+      if (score == score && argmax_better(score, c, bv, bi)) {
+        bv = score;
+        bi = c;
+      }
+    }
+  }
+  argmax_wave_block(bv, bi, red_v, red_i);
+  if (threadIdx.x == 0) {
+    seed_idx[blockIdx.x] = (int32_t)(bi < 0 ? first : bi);   // first < N: the grid is ⌈N/kPruneSeedGroup⌉
+    if (blockIdx.x == 0) counts[0] = (int32_t)gridDim.x;
+  }
+}
+
+// ubm1(m) as prune_bound1_seed_kernel computes it, the stripes spread over the 64 lanes of one wave (lane l takes
+// stripes l, l + 64, …) and summed by a butterfly, so every lane returns the same bits; D = Σ_i C_i·Φ(u_i), the
+// negative of dUB₁/dm.  Another order of the sum than the serial loop's: at most P·2⁻⁵³ relative, inside the 1e-9.
+__device__ __forceinline__ double cut_ubm1(double m, const double* y2, const double* Ci, const double* Wi, int P,
+                                           int lane, double sB, double iB, double& D) {
+#pragma clang fp contract(off)
+  double ub = 0.0, scale = 0.0, d = 0.0;
+  for (int i = lane; i < P; i += 64) {
+    const double dy = y2[i] - m;
+    const double u = dy * iB;
+    const double cdf = ndtr_fast(u);
+    const double p2 = fmax(sB * npdf_fast(u) + dy * cdf, 0.0);
+    ub += Ci[i] * p2;
+    scale += p2 * Wi[i];
+    d += Ci[i] * cdf;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    ub += __shfl_xor(ub, o);
+    scale += __shfl_xor(scale, o);
+    d += __shfl_xor(d, o);
+  }
+  D = d;
+  const double tiny = 64.0 * 0x1p-52 * scale + 1e-300;
+  return ub * (1.0 + 1e-9) + tiny;
+}
+
+// The cut.  One workgroup, launched after the seeds' arg-max has written τ₀ = tau[0].  All kPruneBlock threads run
+// prune_bound1_seed_kernel's prologue (C_i, W_i, M₀: the same expressions in the same order); wave 0 then finds m* with
+// the computed ubm1(m*) < τ₀:
+//   bracket  ubm1 at the largest y2.  Below τ₀: step left by (y2 range + sB)·2^k, at most kCutBracketSteps times, until a
+//            point is not below.  Not below: the right end is that y2 + 40·sB, where every ψ has underflowed and ubm1
+//            is 1e-300; if even that is not below τ₀ there is no bracket.
+//   solve    Newton on log ubm1 (its tangent overshoots to the verified side, then converges from there) towards
+//            τ₀·(1 − 5e-8), a bisection step wherever the proposal leaves the bracket; at most kCutSolveSteps
+//            evaluations, stops once τ₀·(1 − 1e-7) ≤ ubm1(hi) < τ₀ or the bracket's ends are neighbouring doubles.
+//   walk     at most kCutWalkSteps predecessors of hi that still test below τ₀.
+// hi is only ever a point whose computed ubm1 tested below τ₀, so whatever stops the loops m* = hi is verified; no
+// such point, τ₀ not > 0 (zero, negative, −∞, NaN), a non-finite M₀, C_i or W_i: m* = +∞, which keeps everything.
+// Fixed trip counts, nothing spins, nothing waits on another workgroup.  cut = {m*, τ₀, ubm1(m*) (NaN without a cut)},
+// mirrored to the pinned stats words (system-scope stores, as the counts').
+constexpr int kCutBracketSteps = 64;
+constexpr int kCutSolveSteps = 64;
+constexpr int kCutWalkSteps = 3;
+__global__ __launch_bounds__(kPruneBlock) void prune_cut_kernel(const double* __restrict__ pf, int P, double r0,
+                                                                double sA, double sB,
+                                                                const double* __restrict__ alpha0, int n0,
+                                                                double var0, const double* __restrict__ tau,
+                                                                double* __restrict__ cut, int64_t* stats_host) {
+#pragma clang fp contract(off)
+  extern __shared__ double sm[];
+  double* y1 = sm;              // P + 1
+  double* y2 = sm + P + 1;      // P
+  double* Ci = y2 + P;          // P
+  double* Wi = Ci + P;          // P
+  __shared__ double red_a[kPruneBlock / 64];
+  for (int i = threadIdx.x; i < P; i += blockDim.x) {
+    y1[i + 1] = pf[2 * i];
+    y2[i] = pf[2 * i + 1];
+  }
+  if (threadIdx.x == 0) y1[0] = r0;
+  double sa = 0.0;
+  for (int k = threadIdx.x; k < n0; k += blockDim.x) sa += fabs(alpha0[k]);
+  for (int o = 32; o > 0; o >>= 1) sa += __shfl_xor(sa, o);
+  if ((threadIdx.x & 63) == 0) red_a[threadIdx.x >> 6] = sa;
+  __syncthreads();
+  double M0 = 0.0;
+  for (int w = 0; w < kPruneBlock / 64; ++w) M0 += red_a[w];
+  M0 = var0 * M0 * (1.0 + 0x1p-20);
+  const double iA = 1.0 / sA, iB = 1.0 / sB;
+  for (int i = threadIdx.x; i < P; i += blockDim.x) {
+    const double a = y1[i], b = y1[i + 1];
+    const double dab = a - b, t = dab * iA;
+    Ci[i] = sA * npdf_fast(t) + dab * ndtr_fast(t);
+    Wi[i] = fabs(a) + fabs(b) + 2.0 * M0 + sA;
+  }
+  __syncthreads();
+  if (threadIdx.x >= 64) return;
+  const int lane = threadIdx.x;
+  const double inf = __builtin_inf();
+  const double t = tau[0];
+  bool fin = fabs(M0) < inf;   // false on a NaN
+  double ymax = -inf, ymin = inf;
+  for (int i = lane; i < P; i += 64) {
+    fin = fin && fabs(Ci[i]) < inf && fabs(Wi[i]) < inf;
+    ymax = fmax(ymax, y2[i]);
+    ymin = fmin(ymin, y2[i]);
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    ymax = fmax(ymax, __shfl_xor(ymax, o));
+    ymin = fmin(ymin, __shfl_xor(ymin, o));
+  }
+  fin = __all(fin) != 0 && fabs(ymax) < inf && fabs(ymin) < inf;
+  double hi = inf, uhi = __builtin_nan(""), lo = -inf;   // hi: verified below τ₀; lo: tested, not below
+  if (fin && t > 0.0) {
+    double D;
+    double f = cut_ubm1(ymax, y2, Ci, Wi, P, lane, sB, iB, D);
+    double mN = ymax, fN = f, DN = D;   // the point the next Newton step starts from
+    bool have_lo = false;
+    if (f < t) {
+      hi = ymax;
+      uhi = f;
+      double step = (ymax - ymin) + sB;
+      for (int k = 0; k < kCutBracketSteps && !have_lo; ++k) {
+        const double m = ymax - step;
+        step = 2.0 * step;
+        f = cut_ubm1(m, y2, Ci, Wi, P, lane, sB, iB, D);
+        if (f < t) {
+          hi = m;
+          uhi = f;
+          mN = m;
+          fN = f;
+          DN = D;
+        } else {
+          lo = m;
+          have_lo = true;
+        }
+      }
+    } else {
+      lo = ymax;
+      have_lo = true;
+      const double m = ymax + 40.0 * sB;
+      f = cut_ubm1(m, y2, Ci, Wi, P, lane, sB, iB, D);
+      if (f < t) {
+        hi = m;
+        uhi = f;
+      }
+    }
+    if (have_lo && hi < inf) {
+      const double tt = t * (1.0 - 5e-8), tw = t * (1.0 - 1e-7);
+      bool done = uhi >= tw;
+      for (int k = 0; k < kCutSolveSteps && !done; ++k) {
+        double m = mN + fN * log(fN / tt) / (DN * (1.0 + 1e-9));
+        if (!(m > lo && m < hi)) m = lo + 0.5 * (hi - lo);
+        if (!(m > lo && m < hi)) break;   // neighbouring doubles: hi's predecessor is not below τ₀
+        f = cut_ubm1(m, y2, Ci, Wi, P, lane, sB, iB, D);
+        mN = m;
+        fN = f;
+        DN = D;
+        if (f < t) {
+          hi = m;
+          uhi = f;
+          done = f >= tw;
+        } else {
+          lo = m;
+        }
+      }
+      for (int k = 0; k < kCutWalkSteps; ++k) {
+        const double m = nextafter(hi, -inf);
+        if (!(m > lo)) break;
+        f = cut_ubm1(m, y2, Ci, Wi, P, lane, sB, iB, D);
+        if (!(f < t)) break;
+        hi = m;
+        uhi = f;
+      }
+    }
+  }
+  if (lane == 0) {
+    cut[0] = hi;
+    cut[1] = t;
+    cut[2] = uhi;
+    if (stats_host) {
+      long long* sh = reinterpret_cast<long long*>(stats_host);
+      __hip_atomic_store(sh, __builtin_bit_cast(long long, hi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(sh + 1, __builtin_bit_cast(long long, t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(sh + 2, __builtin_bit_cast(long long, uhi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+
+// prune_threshold_kernel by the cut: keep = not its group's seed and not (a cut exists and μ̃₁ − ε₁ ≥ m*).  The low end
+// is prune_bound1_seed_kernel's expression; a NaN or −∞ low end never compares and stays, as a NaN or +∞ ubm1 does
+// there, and m* = +∞ keeps everything, a +∞ low end included.
+__global__ __launch_bounds__(kPruneBlock) void prune_threshold_cut_kernel(const double* __restrict__ mu1,
+                                                                          const double* __restrict__ eps1,
+                                                                          const int32_t* __restrict__ seed_idx,
+                                                                          const double* __restrict__ cut, int64_t N,
+                                                                          uint8_t* __restrict__ keep,
+                                                                          int32_t* __restrict__ block_cnt) {
+#pragma clang fp contract(off)
+  __shared__ int wave_cnt[kPruneBlock / 64];
+  const int64_t c = (int64_t)blockIdx.x * kPruneBlock + threadIdx.x;
+  const double ms = cut[0];
+  bool k = false;
+  if (c < N) {
+    const double m1 = mu1[c] - eps1[c];
+    k = c != (int64_t)seed_idx[c / kPruneSeedGroup] && !(ms < __builtin_inf() && m1 >= ms);
+    keep[c] = k ? 1 : 0;
+  }
+  const int nw = __popcll(__ballot(k));
+  if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = nw;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int s = 0;
+    for (int w = 0; w < kPruneBlock / 64; ++w) s += wave_cnt[w];
+    block_cnt[blockIdx.x] = s;
+  }
+}
+
 // The full interval bound on list A: thread j takes idx_a[j], j < *count_a, and keeps it unless τ > 0 and ubm < τ
 // (prune_ubm<true>, the one copy).  Flags and per-workgroup counts over list positions; a workgroup past the count
 // writes a zero count and leaves.
@@ -1277,14 +1507,38 @@ hipError_t launch_prune_bound1_seed(hipStream_t stream, const double* mu1, const
   return hipGetLastError();
 }
 
-hipError_t launch_prune_threshold_a(hipStream_t stream, int64_t N, const PruneWs& ws) {
-  // prune_threshold_kernel, the scan and the compaction as they are, into list A: its count to counts[2] and
-  // stats_host[1]
+hipError_t launch_prune_seed1(hipStream_t stream, const double* mu1, int64_t N, const PruneWs& ws) {
+  const int64_t ng = (N + kPruneSeedGroup - 1) / kPruneSeedGroup;
+  if (N < 1 || ng > (1 << 23) || !mu1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(prune_seed1_kernel, dim3((unsigned)ng), dim3(kPruneBlock), 0, stream, mu1, N, ws.seed_idx,
+                     ws.counts);
+  return hipGetLastError();
+}
+
+hipError_t launch_prune_cut(hipStream_t stream, const double* pf, int P, double r0, double s00, double s01, double sf2,
+                            const double* alpha0, int n0, const PruneWs& ws) {
+  if (P < 0 || !alpha0 || n0 < 0) return hipErrorInvalidValue;
+  const size_t shm = sizeof(double) * (4 * P + 1);
+  hipLaunchKernelGGL(prune_cut_kernel, dim3(1), dim3(kPruneBlock), shm, stream, pf, P, r0, sf2 * s00, sf2 * s01, alpha0,
+                     n0, sf2, ws.tau, ws.cut, ws.stats_host ? ws.stats_host + 2 : nullptr);
+  return hipGetLastError();
+}
+
+hipError_t launch_prune_threshold_a(hipStream_t stream, int64_t N, const PruneWs& ws, const double* mu1,
+                                    const double* eps1) {
+  // the threshold kernel (by the cut where mu1 and eps1 are given), the scan and the compaction as they are, into
+  // list A: its count to counts[2] and stats_host[1]
   PruneWs a = ws;
   a.surv_idx = ws.list_a;
   a.counts = ws.counts + 1;
   a.stats_host = ws.stats_host ? ws.stats_host + 1 : nullptr;
-  return launch_prune_threshold(stream, N, a);
+  if (!mu1) return launch_prune_threshold(stream, N, a);
+  const int64_t nb = (N + kPruneBlock - 1) / kPruneBlock;
+  if (N < 1 || nb > (1 << 23) || !eps1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(prune_threshold_cut_kernel, dim3((unsigned)nb), dim3(kPruneBlock), 0, stream, mu1, eps1,
+                     ws.seed_idx, ws.cut, N, a.keep, a.block_cnt);
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? e : launch_prune_compact(stream, N, a);
 }
 
 hipError_t launch_prune_bound_list(hipStream_t stream, const double* mu0, const double* mu1, const double* eps0,

@@ -129,6 +129,9 @@ struct omb_ctx {
   int64_t* prune_stats_dev = nullptr;
   // omb_argmax_stage_stats: whether it took the staged order; |A| is prune_stats_host[1], |B| is [0]
   int stage_taken = 0;
+  // omb_argmax_cut_stats: whether the staged order took objective 1's bound as a cut; m*, τ₀ and
+  // ubm1(m*) are the bits in prune_stats_host[2..4]
+  int cut_taken = 0;
   int nd_rounds = 0;                              // omb_nondominated_stats: the last call's tile passes
   int64_t nd_survivors[kNdMaxRounds + 1] = {};    // and the largest set's survivors after each
   // device fault word (pinned, mapped host memory): kernels mark it, enter() reports it
@@ -159,6 +162,7 @@ struct omb_ctx {
                                  // candidates, 2 the strided seed at any N, 3 the seed by bound at any N
   int argmax_staged = 1;         // OMB_DEBUG_ARGMAX_STAGED: 1 objective 1's screen and bound first, 0 §31's order
   int argmax_screen = 1;         // OMB_DEBUG_ARGMAX_SCREEN: the two-phase path's bound from 1 the fp32 screen, 0 fp64 means
+  int argmax_cut = 1;            // OMB_DEBUG_ARGMAX_CUT: the staged order's first list by 1 one cut on μ̃₁ − ε₁, 0 ubm1 per candidate
 };
 
 namespace {
@@ -638,11 +642,14 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
   // The staged order where the seed by bound runs on the screen: objective 1's screen and its bound for
   // all N, objective 0's screen and the full bound only for those that pass
   const bool staged = two_phase && seed_by_bound && ctx->argmax_screen != 0 && ctx->argmax_staged != 0;
+  // ubm1 decreases in μ̃₁ − ε₁, so the staged order's first list is one cut on that number
+  const bool cut = staged && ctx->argmax_cut != 0;
   if (two_phase && (rc = grow_dev(ctx, ctx->prws, (size_t)prune_ws_bytes(N), "arg-max pruning workspace"))) return rc;
   if (result_dev) {
     ctx->prune_taken = two_phase ? 1 : 0;
     ctx->prune_seed = two_phase ? (N + seed_step - 1) / seed_step : 0;
     ctx->stage_taken = staged ? 1 : 0;
+    ctx->cut_taken = cut ? 1 : 0;
   }
   double* mu = ctx->work.as<double>();
   double* var = mu + (size_t)K * nd;
@@ -717,7 +724,9 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
     if (e == hipSuccess && seed_by_bound && screen)
       e = launch_posterior_screen(ctx->stream, args, staged ? 2u : 3u, Xc, N, ws.scr_mu, ws.scr_eps);
     // ubm1 from μ̃₁ − ε₁ alone bounds the full bound for every μ₀, so the seed and list A come from it
-    if (e == hipSuccess && staged)
+    // the seed is the smallest μ̃₁ and needs no bound; the bound becomes one cut once τ₀ is known
+    if (e == hipSuccess && cut) e = launch_prune_seed1(ctx->stream, ws.scr_mu + nd, N, ws);
+    if (e == hipSuccess && staged && !cut)
       e = launch_prune_bound1_seed(ctx->stream, ws.scr_mu + nd, ws.scr_eps + nd, N, pl.geo, pl.P, pl.r[0], pl.s00,
                                    pl.s01, sf2, args.gp[0].alpha, args.gp[0].n, ws);
     if (e == hipSuccess && seed_by_bound && !staged)
@@ -733,13 +742,18 @@ int run_chain(omb_ctx* ctx, const double* Xc, bool sobol, int64_t start, int64_t
                                     pl.r[0], pl.r[1], pl.s00, pl.s01, pl.mode, ws.partials);
     if (e == hipSuccess) e = launch_argmax_reduce(ctx->stream, ws.partials, nbs, 0, ws.tau);
     if (e == hipSuccess && seed_by_bound && !staged) e = launch_prune_threshold(ctx->stream, N, ws);
+    if (e == hipSuccess && cut)
+      e = launch_prune_cut(ctx->stream, pl.geo, pl.P, pl.r[0], pl.s00, pl.s01, sf2, args.gp[0].alpha, args.gp[0].n, ws);
+    const double* cm = cut ? ws.scr_mu + nd : nullptr;   // the threshold by the cut reads μ̃₁ and ε₁
+    const double* ce = cut ? ws.scr_eps + nd : nullptr;
     if (staged && nv == 0) {
       // N = 1, nothing but the seed: both lists empty, their counts and stats words written in stream order
-      if (e == hipSuccess) e = launch_prune_threshold_a(ctx->stream, N, ws);
+      if (e == hipSuccess) e = launch_prune_threshold_a(ctx->stream, N, ws, cm, ce);
       if (e == hipSuccess) e = launch_prune_threshold(ctx->stream, N, ws);
     } else if (staged) {
-      // list A by the threshold on ubm1, objective 0's screen for list A, the full interval bound on list A → list B
-      if (e == hipSuccess) e = launch_prune_threshold_a(ctx->stream, N, ws);
+      // list A by the threshold on ubm1 (or by the cut), objective 0's screen for list A, the full interval bound on
+      // list A → list B
+      if (e == hipSuccess) e = launch_prune_threshold_a(ctx->stream, N, ws, cm, ce);
       if (e == hipSuccess)
         e = launch_posterior_screen_gather(ctx->stream, args, 0, Xc, ws.list_a, ws.counts + 2, nv, ws.scr_mu,
                                            ws.scr_eps);
@@ -813,7 +827,7 @@ int omb_create(int device, omb_ctx** out) {
       hipHostMalloc(&ctx->fit_host, sizeof(double) * (OMB_MAX_DIM + 8), hipHostMallocMapped | hipHostMallocCoherent) !=
           hipSuccess ||
       hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->fit_dev), ctx->fit_host, 0) != hipSuccess ||
-      hipHostMalloc(&ctx->prune_stats_host, sizeof(int64_t) * 2, hipHostMallocMapped | hipHostMallocCoherent) !=
+      hipHostMalloc(&ctx->prune_stats_host, sizeof(int64_t) * 5, hipHostMallocMapped | hipHostMallocCoherent) !=
           hipSuccess ||
       hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->prune_stats_dev), ctx->prune_stats_host, 0) !=
           hipSuccess) {
@@ -821,7 +835,7 @@ int omb_create(int device, omb_ctx** out) {
     return OMB_ENOMEM;
   }
   *ctx->fault_host = 0;
-  ctx->prune_stats_host[0] = ctx->prune_stats_host[1] = 0;
+  for (int i = 0; i < 5; ++i) ctx->prune_stats_host[i] = 0;
   ctx->stream = ctx->own_stream;
   *out = ctx;
   return OMB_OK;
@@ -900,6 +914,7 @@ static const DebugSwitch kDebugSwitches[] = {
      "any size)"},
     {OMB_DEBUG_ARGMAX_SCREEN, &omb_ctx::argmax_screen, 0, 1, nullptr},
     {OMB_DEBUG_ARGMAX_STAGED, &omb_ctx::argmax_staged, 0, 1, nullptr},
+    {OMB_DEBUG_ARGMAX_CUT, &omb_ctx::argmax_cut, 0, 1, nullptr},
 };
 
 int omb_debug_set(omb_ctx* ctx, int what, int64_t value) {
@@ -1355,6 +1370,19 @@ int omb_argmax_stage_stats(omb_ctx* ctx, int64_t* stats_host) {
   stats_host[0] = ctx->stage_taken;
   stats_host[1] = ctx->stage_taken ? __atomic_load_n(ctx->prune_stats_host + 1, __ATOMIC_ACQUIRE) : 0;
   stats_host[2] = ctx->stage_taken ? __atomic_load_n(ctx->prune_stats_host, __ATOMIC_ACQUIRE) : 0;
+  return OMB_OK;
+}
+
+int omb_argmax_cut_stats(omb_ctx* ctx, double* stats_host) {
+  if (!ctx) return OMB_EINVAL;
+  if (!stats_host) return fail(ctx, OMB_EINVAL, "null output");
+  stats_host[0] = ctx->cut_taken;
+  for (int i = 0; i < 3; ++i) {
+    const int64_t bits = __atomic_load_n(ctx->prune_stats_host + 2 + i, __ATOMIC_ACQUIRE);
+    double v;
+    memcpy(&v, &bits, sizeof(v));
+    stats_host[1 + i] = ctx->cut_taken ? v : 0.0;
+  }
   return OMB_OK;
 }
 

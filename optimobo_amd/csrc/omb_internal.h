@@ -125,12 +125,13 @@ struct PruneWs {
   double* tau;           // {τ, its index}: the seed sample's arg-max
   int32_t* list_a;       // N: the staged order's list A, the candidates objective 1's bound leaves
   int32_t* block_cnt_b;  // ⌈N/kPruneBlock⌉: the full bound's kept count per workgroup of list A positions, then offsets
+  double* cut;           // {m*, τ₀, ubm1(m*), unused}: objective 1's bound as a cut on μ̃₁ − ε₁
   int64_t* stats_host;   // pinned, device-mapped: [0] the survivor count of the last call (a system-scope store),
-                         // [1] the staged order's list A count
+                         // [1] the staged order's list A count, [2..4] the bits of the cut's three doubles
 };
 // ≈ 49.3·N bytes: 45.3·N of the two lists' first (seed_idx N/4, surv_idx 4N), block_cnt N/64, keep N, ubm 8N and the
 // screen's rows 32N, and the staged order's list_a 4N and block_cnt_b N/64.  The staged order stores ubm1 in the ubm row
-// and reuses keep for its second compaction's flags.
+// (under the cut of §34 nothing does) and reuses keep for its second compaction's flags.
 int64_t prune_ws_bytes(int64_t N);
 void prune_ws_carve(void* base, int64_t N, PruneWs* ws);
 // seed_idx and counts[0]
@@ -170,7 +171,18 @@ hipError_t launch_prune_threshold(hipStream_t stream, int64_t N, const PruneWs& 
 hipError_t launch_prune_bound1_seed(hipStream_t stream, const double* mu1, const double* eps1, int64_t N,
                                     const double* pf, int P, double r0, double s00, double s01, double sf2,
                                     const double* alpha0, int n0, const PruneWs& ws);
-hipError_t launch_prune_threshold_a(hipStream_t stream, int64_t N, const PruneWs& ws);
+hipError_t launch_prune_threshold_a(hipStream_t stream, int64_t N, const PruneWs& ws, const double* mu1 = nullptr,
+                                    const double* eps1 = nullptr);
+// Objective 1's bound as one cut: ubm1 decreases in its one argument, so "ubm1 < τ₀" is "μ̃₁ − ε₁ ≥ m*".
+//   launch_prune_seed1        launch_prune_bound1_seed's seeds (the smallest μ̃₁ of each group, the same rule) and
+//                             counts[0] with no bound evaluated and ws.ubm left alone
+//   launch_prune_cut          one workgroup, after *ws.tau is written: m* with the computed ubm1(m*) < τ₀ and
+//                             ubm1(m*) ≥ τ₀·(1 − 1e-7) (or m*'s predecessor not below τ₀), +∞ where nothing may be
+//                             dropped; {m*, τ₀, ubm1(m*)} to ws.cut and stats_host[2..4]
+//   launch_prune_threshold_a  with mu1, eps1: keep = not the seed and not (m* < ∞ and μ̃₁ − ε₁ ≥ m*) against ws.cut
+hipError_t launch_prune_seed1(hipStream_t stream, const double* mu1, int64_t N, const PruneWs& ws);
+hipError_t launch_prune_cut(hipStream_t stream, const double* pf, int P, double r0, double s00, double s01, double sf2,
+                            const double* alpha0, int n0, const PruneWs& ws);
 hipError_t launch_prune_bound_list(hipStream_t stream, const double* mu0, const double* mu1, const double* eps0,
                                    const double* eps1, int64_t cap, const double* pf, int P, double r0, double s00,
                                    double s01, double sf2, const PruneWs& ws);

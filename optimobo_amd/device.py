@@ -108,7 +108,9 @@ class AcqContext:
         pair); ("argmax_staged", 0/1) runs the seeded-by-bound path with both objectives' screen and the full bound
         for every candidate / staged (default): objective 1's screen and a bound from it alone for every candidate,
         objective 0's screen and the full bound only for those it keeps — 0 is the order for batches where
-        objective 0 decides (bit-identical pair; see ``argmax_stage_stats``)."""
+        objective 0 decides (bit-identical pair; see ``argmax_stage_stats``); ("argmax_cut", 0/1) draws the staged
+        order's first list by evaluating objective 1's bound for every candidate / by one cut on the low end of its
+        screened mean, solved once per call (default; bit-identical pair; see ``argmax_cut_stats``)."""
         code = getattr(_lib, "DEBUG_" + str(what).upper(), None)
         if code is None:
             raise KeyError(what)
@@ -400,6 +402,15 @@ class AcqContext:
         st = (ctypes.c_int64 * 3)()
         self._check(self.lib.omb_argmax_stage_stats(self._h, st), "omb_argmax_stage_stats")
         return bool(st[0]), int(st[1]), int(st[2])
+
+    def argmax_cut_stats(self):
+        """omb_argmax_cut_stats: the same call → (cut, m*, τ₀, ubm1(m*)): whether the staged order drew its first
+        list by the cut ("argmax_cut"), the cut on the low end of objective 1's screened mean (+inf: nothing could
+        be dropped), the seed's best value and objective 1's bound at m* (NaN where m* is +inf).
+        (False, 0.0, 0.0, 0.0) otherwise."""
+        st = (ctypes.c_double * 4)()
+        self._check(self.lib.omb_argmax_cut_stats(self._h, st), "omb_argmax_cut_stats")
+        return bool(st[0]), float(st[1]), float(st[2]), float(st[3])
 
     def hvpoi(self, mu, var, cells, out=None):
         N = mu.shape[1]
