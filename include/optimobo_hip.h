@@ -39,6 +39,8 @@ extern "C" {
 #define OMB_HVI_PATHS_CHUNK 262144 /* candidates per pass of the fused chain under an omb_plan_hvi_paths plan */
 #define OMB_NONDOM_SETS 16         /* point sets of one omb_nondominated call */
 #define OMB_NONDOM_POINTS 16777216 /* points per set of omb_nondominated (2^24) */
+#define OMB_HV_POINTS 1024         /* kept rows per set of omb_hypervolume / omb_hypervolume_contrib */
+#define OMB_HV_MAX_WORK 274877906944LL /* point tests (cells × kept rows × variants) of one such call (2^38) */
 
 enum {
   OMB_OK = 0,
@@ -394,6 +396,41 @@ int omb_nondominated(omb_ctx* ctx, int k, int S, const double* y_dev, int64_t ld
  * most 4) and survivors_host[r] (5 entries; those past *rounds_host are 0) the largest set's survivors after pass r —
  * what the final pass then tested against itself is the last of them.  Host values; nothing is launched. */
 int omb_nondominated_stats(omb_ctx* ctx, int64_t* survivors_host, int* rounds_host);
+
+/* The exact hypervolume (everything minimised) that each of S independent point sets dominates below the reference
+ * point r_host (k host doubles).  y_dev and mask_dev have omb_nondominated's layout: coordinate j of point i of set s
+ * is y_dev[(j·S + s)·ld + i], and row i belongs to set s when mask_dev[s·ldm + i] != 0 (mask_dev NULL: every row, ldm
+ * is then only checked against N).  A row is KEPT when every coordinate is finite and < r_j: NaN, ±∞ and y_j ≥ r_j
+ * drop it.  The set need not be non-dominated: dominated rows, duplicates and ties change nothing.
+ *   hv_dev[s] = the hypervolume of set s; 0.0 for a set with no kept row
+ * A grid sweep (omb_hypervolume.hip): objectives 0..k-3 are cut at the kept rows' distinct values, and
+ * every cell's weight times the area of the 2-D staircase of the rows that reach it is summed — exact arithmetic on
+ * exactly the dominated region, cells × kept rows point tests, every addition of positive terms, in a tree whose
+ * shape depends on the cell count alone: the result is bitwise the same whatever ld, ldm, S, the set's slot, the order
+ * of the rows and the number of dropped rows.
+ * SYNCHRONISES: the kept count and the grid sizes are read back once to size the second launch.  Scratch is a context
+ * buffer grown on demand.  Touches no plan, no GP state and no paths.
+ *   OMB_EINVAL  k outside [1, OMB_MAX_OBJ], S outside [1, OMB_NONDOM_SETS], N < 0, ld < N or ldm < N, a NULL r_host or
+ *               a non-finite r_j, a NULL hv_dev, a NULL y_dev with N > 0, y_dev or hv_dev off 8-byte alignment — in
+ *               this order
+ *   OMB_EUNSUP  N > OMB_NONDOM_POINTS; then, after the first launch, a set with more than OMB_HV_POINTS kept rows; then
+ *               Σ_s cells_s × kept_s above OMB_HV_MAX_WORK
+ * A refused call writes nothing to hv_dev.  N = 0 returns OMB_OK and writes hv_dev[s] = 0.0. */
+int omb_hypervolume(omb_ctx* ctx, int k, int S, const double* y_dev, int64_t ld, int64_t N, const uint8_t* mask_dev,
+                    int64_t ldm, const double* r_host, double* hv_dev);
+/* One set (y_dev (k, N) at pitch ld, mask_dev N bytes or NULL) and what every row adds to it:
+ *   hv_dev[0]      = HV(set), as omb_hypervolume gives it, bit for bit
+ *   contrib_dev[i] = HV(set) − HV(set without row i) for a kept row i, 0.0 for a dropped or masked-out row   (i < N)
+ * Both hypervolumes are sums over the whole set's grid in the same tree, so a row whose removal changes no cell's
+ * staircase — a duplicate, a row that another kept row dominates — gets exactly 0.0, not a rounding of it; the other
+ * rows' values carry the rounding of both sums (about 2·(n + k + 48)·2^-53·HV at worst).  cells × kept × (kept + 1) point
+ * tests.  SYNCHRONISES like omb_hypervolume.
+ *   OMB_EINVAL  omb_hypervolume's (S = 1, ldm = N), a NULL contrib_dev where a NULL hv_dev is refused, contrib_dev off
+ *               8-byte alignment with the other two
+ *   OMB_EUNSUP  N > OMB_NONDOM_POINTS; more than OMB_HV_POINTS kept rows; cells × kept × (kept + 1) above OMB_HV_MAX_WORK
+ * A refused call writes nothing to either output.  N = 0 returns OMB_OK and writes hv_dev[0] = 0.0 only. */
+int omb_hypervolume_contrib(omb_ctx* ctx, int k, const double* y_dev, int64_t ld, int64_t N, const uint8_t* mask_dev,
+                            const double* r_host, double* hv_dev, double* contrib_dev);
 /* The last omb_eval_argmax[_sobol] call on this context (OMB_DEBUG_ARGMAX_PRUNE): stats_host[0] = 1 if it took the
  * two-phase path, 0 if the dense chain; [1] the candidates of its seed (⌈N/256⌉, or ⌈N/16⌉ under the value 2); [2]
  * the candidates past the seed whose bound kept them.  [2] is stored by the call's kernels: it is that call's once

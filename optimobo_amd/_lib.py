@@ -43,6 +43,8 @@ CON_VIOLATION = 1              # OMB_CON_VIOLATION: omb_hvi_paths_con's flag (in
 HVI_PATHS_CHUNK = 1 << 18      # OMB_HVI_PATHS_CHUNK: candidates per pass of the chain under plan_hvi_paths
 NONDOM_SETS = 16               # OMB_NONDOM_SETS: point sets of one omb_nondominated call
 NONDOM_POINTS = 1 << 24        # OMB_NONDOM_POINTS: points per set of omb_nondominated
+HV_POINTS = 1024               # OMB_HV_POINTS: kept rows per set of omb_hypervolume
+HV_MAX_WORK = 1 << 38          # OMB_HV_MAX_WORK: point tests of one omb_hypervolume / omb_hypervolume_contrib call
 
 _p = ctypes.c_void_p
 _d = ctypes.c_double
@@ -77,6 +79,9 @@ SIGNATURES = {
     # non-dominated filter
     "omb_nondominated": (_i, [_p, _i, _i, _p, _i64, _i64, _p, _i64, _p]),
     "omb_nondominated_stats": (_i, [_p, ctypes.POINTER(_i64), ctypes.POINTER(_i)]),
+    # exact hypervolume
+    "omb_hypervolume": (_i, [_p, _i, _i, _p, _i64, _i64, _p, _i64, _dp, _p]),
+    "omb_hypervolume_contrib": (_i, [_p, _i, _p, _i64, _i64, _p, _dp, _p, _p]),
     "omb_argmax_prune_stats": (_i, [_p, ctypes.POINTER(_i64)]),
     "omb_argmax_stage_stats": (_i, [_p, ctypes.POINTER(_i64)]),
     "omb_argmax_cut_stats": (_i, [_p, _dp]),

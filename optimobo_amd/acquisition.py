@@ -180,6 +180,30 @@ class AcquisitionEngine:
         Yd = Y if isinstance(Y, torch.Tensor) else self._dev(Y)
         return self.ctx.nondominated(Yd.to(device=self.device, dtype=torch.float64), S)
 
+    def _point_rows(self, Y):
+        Yd = Y if isinstance(Y, torch.Tensor) else self._dev(Y)
+        return Yd.to(device=self.device, dtype=torch.float64)
+
+    def hypervolume(self, Y, ref, S=1, mask=None):
+        """``AcqContext.hypervolume`` over the engine's context: the exact hypervolume below ``ref`` of Y (k, N) —
+        S = 1 — or of each of the S sets of Y (k, S, N), a device tensor or host values (coordinates along the first
+        axis, as ``nondominated`` takes them) → (S,) on the device."""
+        return self.ctx.hypervolume(self._point_rows(Y), ref, S, mask)
+
+    def hypervolume_contributions(self, Y, ref, mask=None):
+        """``AcqContext.hypervolume_contributions`` over the engine's context: Y (k, N) → (hv (1,), contributions
+        (N,)) on the device."""
+        return self.ctx.hypervolume_contributions(self._point_rows(Y), ref, mask)
+
+    def path_front_hypervolumes(self, Xc, ref):
+        """The hypervolume below ``ref`` of every installed sample path's Pareto set over the candidates Xc (N, d) —
+        S draws from the posterior of the attainable hypervolume → (S,) on the device.  ``path_values``,
+        ``nondominated`` and ``hypervolume`` on the device tensors of one another: no value crosses to the host
+        between the three calls."""
+        Y = self.path_values(Xc)                                    # (n_obj, S, N)
+        mask, _ = self.ctx.nondominated(Y, Y.shape[1])
+        return self.ctx.hypervolume(Y, ref, Y.shape[1], mask)
+
     def path_fronts(self, Xc):
         """The Pareto set of every installed sample path (``sample_paths(S)``) over the candidates Xc (N, d): one
         ``path_values`` and one ``nondominated`` call over the S sets → a list of S pairs (index (P_s,) int64
@@ -1018,11 +1042,16 @@ class AcquisitionEngine:
 _ENGINES = {}
 
 
-def engine_for(models, device=None):
-    """Process-wide engine per device with ``models`` resident."""
+def device_engine(device=None):
+    """The process-wide engine of ``device``, whatever models it holds (for what reads none: ``hypervolume``)."""
     if device is None:
         device = torch.cuda.current_device() if torch.cuda.is_available() else 0
     eng = _ENGINES.get(device)
     if eng is None:
         eng = _ENGINES[device] = AcquisitionEngine(device)
-    return eng.load_models(models)
+    return eng
+
+
+def engine_for(models, device=None):
+    """Process-wide engine per device with ``models`` resident."""
+    return device_engine(device).load_models(models)

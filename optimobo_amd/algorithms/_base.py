@@ -12,8 +12,8 @@ import numpy as np
 
 from .. import pareto
 from .. import util_functions
-from .._lib import OMB_ENOTPD, OMBError
-from ..acquisition import engine_for
+from .._lib import OMB_ENOTPD, OMB_EUNSUP, OMBError
+from ..acquisition import device_engine, engine_for
 from ..gp import GPRegression, Matern52, apply_noise_option, check_noise_option, fit_concurrently
 from ..parallel import agree_host_rng
 from ..result import Constrained_Res, Res
@@ -34,6 +34,10 @@ class BODriver:
     model_front = False          # likewise; _model_front: whether the driver takes model_front=True
     model_front_candidates = 1 << 18
     _model_front = False
+    # the keyword's default (instance attributes only under "device"); _device_hypervolume: whether the driver takes it
+    hypervolume = "host"
+    hypervolume_fallbacks = 0
+    _device_hypervolume = True
     model_front_min_feasibility = 0.5    # constraints: the probability of feasibility a member of the model front needs
     # constraints="paths": the width of the sigmoid that stands for the feasibility indicator in the noisy EHVI / EI
     # (0.0: the indicator itself; a Thompson batch always takes the indicator)
@@ -43,7 +47,7 @@ class BODriver:
                  refine_rounds=2, seed=None, device=None, polish=True, starts=None, noise=0.0, batch_size=1,
                  constraints=None, batch_strategy="believer", thompson_sampler="joint", log_acquisition=False,
                  acquisition=None, mes_samples=8, mes_candidates=1 << 16, path_gradients=False, model_front=False,
-                 model_front_candidates=1 << 18):
+                 model_front_candidates=1 << 18, hypervolume="host"):
         self.test_problem = test_problem
         self.max_point = max_point
         self.ideal_point = ideal_point
@@ -142,6 +146,19 @@ class BODriver:
                 raise ValueError(f"model_front_candidates must be an integer >= 1, not {model_front_candidates!r}")
             self.model_front = True
             self.model_front_candidates = int(model_front_candidates)
+        # where the hypervolume trace is computed (not in the reference, which calls pygmo): "host" is
+        # ``pareto.hypervolume``, the run without the keyword; "device" the exact sweep of
+        # ``AcquisitionEngine.hypervolume`` — the same number to rounding — which falls back to the host function for
+        # a front it refuses (more than 1024 rows, or above its work cap) and counts that in
+        # ``hypervolume_fallbacks``.  Nothing a proposal is computed from reads it: the run picks the same points.
+        if not isinstance(hypervolume, str) or hypervolume not in ("host", "device"):
+            raise ValueError(f"hypervolume must be 'host' or 'device', not {hypervolume!r}")
+        if hypervolume == "device":
+            if not self._device_hypervolume:
+                raise ValueError(f"{type(self).__name__} does not support hypervolume='device' (it computes its own "
+                                 "trace; the drivers whose trace is BODriver's do)")
+            self.hypervolume = "device"
+            self.hypervolume_fallbacks = 0   # trace entries that the host function computed after all
         self.thompson_fallbacks = 0   # Thompson iterations that fell back to the believer batch
         self._iteration = 0
         self._mes_picks = 0
@@ -319,6 +336,15 @@ class BODriver:
         scal.set_bounds(lo, hi)       # reference mode: None raises AttributeError, as the reference does
 
     def _hypervolume(self, ysample):
+        if self.hypervolume == "device" and np.size(ysample):
+            try:
+                hv = device_engine(self.device).hypervolume(np.ascontiguousarray(np.atleast_2d(ysample).T),
+                                                            self.max_point)
+                return float(hv[0])
+            except OMBError as e:
+                if e.code != OMB_EUNSUP:
+                    raise
+                self.hypervolume_fallbacks += 1
         return pareto.hypervolume(ysample, self.max_point)
 
     def _model(self, X, y):

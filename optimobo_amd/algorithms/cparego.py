@@ -63,6 +63,7 @@ class ParEGO_C1(BODriver):  # noqa: N801 — reference class name
     ``batch_size`` is accepted through ``BODriver`` and ignored: one proposal per iteration, as in the reference (ParEGO_C2 likewise)."""
 
     _rows_have_g = False      # C1 keeps [X | y | S] rows, C2 [X | y | g | S]
+    _device_hypervolume = False   # the trace is computed here, against the samples' own maximum, on the host
 
     def __init__(self, test_problem, ideal_point=None, max_point=None, **kw):
         super().__init__(test_problem, ideal_point, max_point, **kw)

@@ -27,7 +27,14 @@ from ..result import Res
 class TuRBO_1:  # noqa: N801 — reference class name
     """https://doi.org/10.48550/arXiv.1910.01739 — one trust region (turbo.py:17-304)."""
 
-    def __init__(self, test_problem, batch_size, ideal_point=None, max_point=None, device=None, noise=0.0):
+    def __init__(self, test_problem, batch_size, ideal_point=None, max_point=None, device=None, noise=0.0,
+                 hypervolume="host"):
+        # BODriver's keyword: TuRBO computes its own trace (its reference point moves with the samples), on the host
+        if not isinstance(hypervolume, str) or hypervolume not in ("host", "device"):
+            raise ValueError(f"hypervolume must be 'host' or 'device', not {hypervolume!r}")
+        if hypervolume == "device":
+            raise ValueError(f"{type(self).__name__} does not support hypervolume='device' (it computes its own "
+                             "trace; the drivers whose trace is BODriver's do)")
         self.test_problem = test_problem
         self.max_point = max_point
         self.ideal_point = ideal_point
@@ -195,10 +202,11 @@ class TuRBO_1:  # noqa: N801 — reference class name
 class TuRBO_M(TuRBO_1):  # noqa: N801 — reference class name
     """TuRBO-m: several trust regions competing for one batch (turbo.py:307-574)."""
 
-    def __init__(self, test_problem, ideal_point, max_point, batch_size, n_trust_regions, device=None, noise=0.0):
+    def __init__(self, test_problem, ideal_point, max_point, batch_size, n_trust_regions, device=None, noise=0.0,
+                 hypervolume="host"):
         self.n_trust_regions = n_trust_regions
         super().__init__(test_problem=test_problem, ideal_point=ideal_point, max_point=max_point,
-                         batch_size=batch_size, device=device, noise=noise)
+                         batch_size=batch_size, device=device, noise=noise, hypervolume=hypervolume)
         self.succtol = 3
         self.failtol = max(5, self.n_vars)
         self.hypers = [{} for _ in range(self.n_trust_regions)]

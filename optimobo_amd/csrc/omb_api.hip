@@ -121,6 +121,8 @@ struct omb_ctx {
   DevBuf nws;    // omb_nondominated: slot counters | final-pass counts | the first survivor list (S, N)
   DevBuf nws2;   // omb_nondominated: the second survivor list (S, survivors of the first pass)
   DevBuf prws;   // the arg-max chain's two-phase path: lists, flags, counts and pairs (PruneWs)
+  DevBuf vws;    // omb_hypervolume: header | totals | one HvSet per set
+  DevBuf vws2;   // omb_hypervolume: the cells' partial sums and their reduction's scratch
   // omb_argmax_prune_stats: whether the last arg-max chain took the two-phase path, its seed sample, and the survivor
   // count its scan kernel stores (pinned, device-mapped)
   int prune_taken = 0;
@@ -854,7 +856,7 @@ int omb_destroy(omb_ctx* ctx) {
   if (ctx->result_host) (void)hipHostFree(ctx->result_host);
   if (ctx->info_host) (void)hipHostFree(ctx->info_host);
   for (DevBuf* b : {&ctx->geo, &ctx->work, &ctx->tws, &ctx->ichol, &ctx->sws, &ctx->ews, &ctx->fws, &ctx->dws, &ctx->gws,
-                    &ctx->aws, &ctx->hws, &ctx->pws, &ctx->nws, &ctx->nws2, &ctx->prws})
+                    &ctx->aws, &ctx->hws, &ctx->pws, &ctx->nws, &ctx->nws2, &ctx->prws, &ctx->vws, &ctx->vws2})
     if (b->p) (void)hipFree(b->p);
   if (ctx->stage) (void)hipHostFree(ctx->stage);
   if (ctx->sob) (void)hipFree(ctx->sob);
@@ -1345,6 +1347,67 @@ int omb_nondominated(omb_ctx* ctx, int k, int S, const double* y_dev, int64_t ld
                                  count_dev);
   if (e != hipSuccess) return hip_fail(ctx, e, "nondominated final pass");
   return OMB_OK;
+}
+
+namespace {
+
+// omb_hypervolume (per_point false: S sets → hv_dev[s]) and omb_hypervolume_contrib (per_point true: one set →
+// hv_dev[0] and contrib_dev), after their checks.  vws: header (kHvMaxS, kHvHdr) | totals (kHvPoints + 1) | HvSet × S.
+int run_hypervolume(omb_ctx* ctx, int k, int S, const double* y_dev, int64_t ld, int64_t N, const uint8_t* mask_dev,
+                    int64_t ldm, const double* r_host, bool per_point, double* hv_dev, double* contrib_dev) {
+  int rc;
+  if (N == 0) {
+    OMB_HIP(ctx, hipMemsetAsync(hv_dev, 0, sizeof(double) * (size_t)S, ctx->stream));
+    return OMB_OK;
+  }
+  constexpr size_t kHdrBytes = sizeof(int32_t) * (size_t)kHvMaxS * kHvHdr;
+  constexpr size_t kTotBytes = sizeof(double) * (size_t)(kHvPoints + 1);
+  if ((rc = grow_dev(ctx, ctx->vws, kHdrBytes + kTotBytes + sizeof(HvSet) * (size_t)S, "hypervolume sets"))) return rc;
+  char* base = ctx->vws.as<char>();
+  int32_t* hdr = reinterpret_cast<int32_t*>(base);
+  double* tot = reinterpret_cast<double*>(base + kHdrBytes);
+  HvSet* sets = reinterpret_cast<HvSet*>(base + kHdrBytes + kTotBytes);
+  HvRef ref{};
+  for (int j = 0; j < k; ++j) ref.r[j] = r_host[j];
+  hipError_t e = launch_hv_prep(ctx->stream, k, S, y_dev, ld, N, mask_dev, ldm, ref, hdr, sets);
+  if (e != hipSuccess) return hip_fail(ctx, e, "hypervolume preparation");
+  int32_t host_hdr[kHvMaxS * kHvHdr];
+  OMB_HIP(ctx, hipMemcpyAsync(host_hdr, hdr, sizeof(int32_t) * (size_t)S * kHvHdr, hipMemcpyDeviceToHost, ctx->stream));
+  OMB_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  int64_t max_cells = 0;
+  if ((rc = check_hv_work(E(ctx), k, S, host_hdr, per_point ? 1 : 0, &max_cells))) return rc;
+  const int V = per_point ? host_hdr[0] + 1 : S;
+  const int64_t nb = hv_cell_blocks(max_cells), nb2 = hv_reduce_blocks(nb);
+  if ((rc = grow_dev(ctx, ctx->vws2, sizeof(double) * (size_t)V * (size_t)(nb + nb2), "hypervolume partial sums")))
+    return rc;
+  double* partials = ctx->vws2.as<double>();
+  e = launch_hv_cells(ctx->stream, k, V, per_point, max_cells, hdr, sets, ref, partials, partials + (size_t)V * nb,
+                      per_point ? tot : hv_dev);
+  if (e != hipSuccess) return hip_fail(ctx, e, "hypervolume cells");
+  if (per_point) {
+    OMB_HIP(ctx, hipMemsetAsync(contrib_dev, 0, sizeof(double) * (size_t)N, ctx->stream));
+    e = launch_hv_contrib(ctx->stream, tot, hdr, sets, hv_dev, contrib_dev);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hypervolume contributions");
+  }
+  return OMB_OK;
+}
+
+}  // namespace
+
+int omb_hypervolume(omb_ctx* ctx, int k, int S, const double* y_dev, int64_t ld, int64_t N, const uint8_t* mask_dev,
+                    int64_t ldm, const double* r_host, double* hv_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if ((rc = check_hypervolume(E(ctx), k, S, y_dev, ld, N, mask_dev, ldm, r_host, hv_dev, 0, nullptr))) return rc;
+  return run_hypervolume(ctx, k, S, y_dev, ld, N, mask_dev, ldm, r_host, false, hv_dev, nullptr);
+}
+
+int omb_hypervolume_contrib(omb_ctx* ctx, int k, const double* y_dev, int64_t ld, int64_t N, const uint8_t* mask_dev,
+                            const double* r_host, double* hv_dev, double* contrib_dev) {
+  int rc = enter(ctx);
+  if (rc) return rc;
+  if ((rc = check_hypervolume(E(ctx), k, 1, y_dev, ld, N, mask_dev, N, r_host, hv_dev, 1, contrib_dev))) return rc;
+  return run_hypervolume(ctx, k, 1, y_dev, ld, N, mask_dev, N, r_host, true, hv_dev, contrib_dev);
 }
 
 int omb_nondominated_stats(omb_ctx* ctx, int64_t* survivors_host, int* rounds_host) {

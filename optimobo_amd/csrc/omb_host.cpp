@@ -282,6 +282,66 @@ int check_nondominated(std::string* err, int k, int S, const void* y, int64_t ld
   return OMB_OK;
 }
 
+int check_hypervolume(std::string* err, int k, int S, const void* y, int64_t ld, int64_t N, const void* mask,
+                      int64_t ldm, const double* r, const void* hv, int contrib, const void* out) {
+  (void)mask;   // bytes at any address, or null for every row
+  if (k < 1 || k > OMB_MAX_OBJ) return errf(err, OMB_EINVAL, "k=%d outside [1, %d]", k, OMB_MAX_OBJ);
+  if (S < 1 || S > kHvMaxS) return errf(err, OMB_EINVAL, "S=%d outside [1, %d]", S, kHvMaxS);
+  if (N < 0) return errf(err, OMB_EINVAL, "N=%lld < 0", (long long)N);
+  if (ld < N || ldm < N)
+    return errf(err, OMB_EINVAL, "ld=%lld or ldm=%lld < N=%lld", (long long)ld, (long long)ldm, (long long)N);
+  if (!r) return errf(err, OMB_EINVAL, "null reference point");
+  for (int j = 0; j < k; ++j)
+    if (!(r[j] >= -1.79769313486231570815e308 && r[j] <= 1.79769313486231570815e308)) return errf(err, OMB_EINVAL, "reference point coordinate %d is not finite", j);
+  if (!hv || (contrib && !out)) return errf(err, OMB_EINVAL, "null output pointer");
+  if (N > 0 && !y) return errf(err, OMB_EINVAL, "null point pointer");
+  if (((uintptr_t)y & 7) || ((uintptr_t)hv & 7) || (contrib && ((uintptr_t)out & 7)))
+    return errf(err, OMB_EINVAL, "y or an output not 8-byte aligned");
+  if (N > kHvMaxN) return errf(err, OMB_EUNSUP, "N=%lld above %lld rows per set", (long long)N, (long long)kHvMaxN);
+  return OMB_OK;
+}
+
+namespace {
+int64_t sat_mul(int64_t a, int64_t b) {   // a, b ≥ 0
+  int64_t p;
+  return __builtin_mul_overflow(a, b, &p) ? INT64_MAX : p;
+}
+}  // namespace
+
+int64_t hv_cells(int g, const int32_t* nj) {
+  int64_t cells = 1;
+  for (int j = 0; j < g; ++j) {
+    if (nj[j] < 1) return 0;
+    cells = sat_mul(cells, nj[j]);
+  }
+  return cells;
+}
+
+int check_hv_work(std::string* err, int k, int S, const int32_t* hdr, int per_point, int64_t* max_cells) {
+  const int g = k > 2 ? k - 2 : 0;
+  int64_t work = 0;
+  *max_cells = 0;
+  for (int s = 0; s < S; ++s) {
+    const int32_t* h = hdr + (size_t)s * kHvHdr;
+    const int64_t n = h[0];
+    if (n > kHvPoints)
+      return errf(err, OMB_EUNSUP, "set %d keeps more than %d rows below the reference point", s, kHvPoints);
+    if (n < 0) return errf(err, OMB_EHIP, "set %d: kept count %lld", s, (long long)n);
+    if (n == 0) continue;
+    for (int j = 0; j < g; ++j)
+      if (h[1 + j] < 1 || h[1 + j] > n)
+        return errf(err, OMB_EHIP, "set %d: grid %d has %d values for %lld rows", s, j, h[1 + j], (long long)n);
+    const int64_t cells = hv_cells(g, h + 1);
+    const int64_t w = sat_mul(sat_mul(cells, n), per_point ? n + 1 : 1);
+    work = w > INT64_MAX - work ? INT64_MAX : work + w;
+    if (cells > *max_cells) *max_cells = cells;
+  }
+  if (work > OMB_HV_MAX_WORK)
+    return errf(err, OMB_EUNSUP, "%lld point tests above %lld (cells x kept rows x variants)", (long long)work,
+                (long long)OMB_HV_MAX_WORK);
+  return OMB_OK;
+}
+
 int check_box_lists(std::string* err, int k, int S, int C, const int32_t* box_off, const uint16_t* boxes) {
   for (int s = 0; s < S; ++s) {
     std::string one;

@@ -144,6 +144,32 @@ inline bool nd_another_round(int rounds_done, int64_t before, int64_t now) {
 }
 // Workgroups per set of the final pass over at most M survivors (at least one: an empty set still writes its count).
 inline int64_t nd_final_blocks(int64_t M) { return M < 1 ? 1 : (M + kNdTile - 1) / kNdTile; }
+// Exact hypervolume (omb_hypervolume / omb_hypervolume_contrib, omb_hypervolume.hip).
+constexpr int kHvMaxS = OMB_NONDOM_SETS;        // point sets of one call
+constexpr int64_t kHvMaxN = OMB_NONDOM_POINTS;  // rows per set
+constexpr int kHvPoints = OMB_HV_POINTS;        // kept rows per set = lanes of the preparation workgroup
+constexpr int kHvGrid = OMB_MAX_OBJ - 2;        // grid objectives at most
+constexpr int kHvHdr = 8;                       // ints per set of the header: n, n_0..n_5, one spare
+constexpr int kHvCellLanes = 512;               // lanes of a cell workgroup
+constexpr int kHvCellsPerLane = 4;
+constexpr int64_t kHvBlockCells = (int64_t)kHvCellLanes * kHvCellsPerLane;
+constexpr int kHvReduceLanes = 256;             // a reduction workgroup adds 2·kHvReduceLanes partial sums
+// omb_hypervolume (contrib: 0) and omb_hypervolume_contrib (contrib: 1, called with S = 1 and ldm = N), in this order:
+// OMB_EINVAL for k outside [1, OMB_MAX_OBJ], S outside [1, kHvMaxS], N < 0, ld < N or ldm < N, a null r or a non-finite
+// r_j, a null hv (contrib: or a null out), (N > 0) a null y, or y / hv / out off 8-byte alignment; OMB_EUNSUP for
+// N > kHvMaxN.  The mask is bytes and may be null.
+int check_hypervolume(std::string* err, int k, int S, const void* y, int64_t ld, int64_t N, const void* mask,
+                      int64_t ldm, const double* r, const void* hv, int contrib, const void* out);
+// Π of the g grid sizes nj[0..g-1] (1 for g = 0), saturating at INT64_MAX; 0 when one of them is < 1.
+int64_t hv_cells(int g, const int32_t* nj);
+// What the preparation kernel left for S sets of k objectives (hdr: S rows of kHvHdr ints), before the cell launch is
+// sized from it: OMB_EUNSUP for a set with more than kHvPoints kept rows, OMB_EHIP for a header no preparation can
+// leave (n < 0, a grid size outside [1, n]), then OMB_EUNSUP for Σ_s cells_s·n_s·variants above OMB_HV_MAX_WORK
+// (variants: n_s + 1 with per_point, else 1; every product and the sum saturate).  *max_cells: the largest set's cells.
+int check_hv_work(std::string* err, int k, int S, const int32_t* hdr, int per_point, int64_t* max_cells);
+// Workgroups per set (variant) of the cell launch, at least one; partial sums after one reduction pass over m.
+inline int64_t hv_cell_blocks(int64_t cells) { return cells < 1 ? 1 : (cells - 1) / kHvBlockCells + 1; }
+inline int64_t hv_reduce_blocks(int64_t m) { return m < 1 ? 1 : (m - 1) / (2 * kHvReduceLanes) + 1; }
 // check_box_list over every list of a host (box_off[S], 2k) list whose offsets passed check_hvi_paths.
 int check_box_lists(std::string* err, int k, int S, int C, const int32_t* box_off, const uint16_t* boxes);
 // Candidates per pass of the fused chain under an omb_plan_hvi_paths plan (the default of OMB_DEBUG_HVI_PATHS_CHUNK):

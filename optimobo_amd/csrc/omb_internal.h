@@ -308,6 +308,33 @@ hipError_t launch_nd_final(hipStream_t stream, int k, int S, const double* y, in
                            int64_t pitch, const int32_t* cnt, int64_t Mmax, uint8_t* mask, int64_t ldm,
                            int32_t* blockcnt, int64_t* count);
 
+// Exact hypervolume (omb_hypervolume.hip; omb_hypervolume / omb_hypervolume_contrib), sets in omb_nondominated's layout.
+struct HvRef {
+  double r[OMB_MAX_OBJ];
+};
+// What launch_hv_prep leaves of one set for launch_hv_cells: the kept points sorted by (y_{k-2}, y_{k-1}, row) — k = 1:
+// (0, y_0) —, their grid ranks as 16-bit fields (objectives 0..3 in rlo, 4..5 in rhi), their rows, and per grid
+// objective j its n_j distinct values followed by r_j.  n and the n_j are in the header: hdr[s·kHvHdr + 0 | 1 + j].
+struct HvSet {
+  double xs[kHvPoints], ys[kHvPoints];
+  uint64_t rlo[kHvPoints];
+  uint32_t rhi[kHvPoints];
+  int32_t orig[kHvPoints];
+  double grid[kHvGrid][kHvPoints + 1];
+};
+//   launch_hv_prep     filters, sorts and ranks the S sets (1 ≤ N ≤ kHvMaxN; mask may be null); a set with more than
+//                      kHvPoints kept rows leaves a count above kHvPoints and nothing else
+//   launch_hv_cells    out[v] = Σ_c w(c)·A(c) for v < V: the sets 0..V-1, or (per_point) set 0 whole and without its
+//                      sorted point v − 1.  max_cells: the largest set's cell count (check_hv_work).  partials holds
+//                      V·hv_cell_blocks(max_cells) doubles, scratch V·hv_reduce_blocks(that)
+//   launch_hv_contrib  hv[0] = tot[0], contrib[orig[v]] = tot[0] − tot[v + 1] for the set's n kept points
+hipError_t launch_hv_prep(hipStream_t stream, int k, int S, const double* y, int64_t ld, int64_t N,
+                          const uint8_t* mask, int64_t ldm, const HvRef& ref, int32_t* hdr, HvSet* sets);
+hipError_t launch_hv_cells(hipStream_t stream, int k, int V, bool per_point, int64_t max_cells, const int32_t* hdr,
+                           const HvSet* sets, const HvRef& ref, double* partials, double* scratch, double* out);
+hipError_t launch_hv_contrib(hipStream_t stream, const double* tot, const int32_t* hdr, const HvSet* set, double* hv,
+                             double* contrib);
+
 // Deterministic arg-max; `partials` must hold kArgmaxMaxBlocks (val, idx) pairs followed by one zeroed ticket word
 // (one_pass: both passes in one launch, the last workgroup to arrive reducing; it leaves the word zeroed again).
 constexpr int kArgmaxMaxBlocks = 1024;

@@ -343,6 +343,86 @@ class AcqContext:
                                                None if u is None else _ptr(u)), "omb_hvi_paths_con")
         return (out, u[:, :N]) if per_path else out
 
+    def _point_sets(self, what, Y, S):
+        """Y (k, N) with S = 1 or (k, S, N), rows possibly pitched → (Y (k, S, N), k, S, N, ld) in the layout of
+        omb_nondominated / omb_hypervolume: row j·S + s at pitch ld."""
+        if not isinstance(Y, torch.Tensor) or Y.dtype != torch.float64 or Y.device != self.device:
+            raise ValueError(f"{what}: Y must be an fp64 tensor on {self.device}")
+        S = int(S)
+        if Y.dim() == 2 and S == 1:
+            Y = Y[:, None, :]
+        if Y.dim() != 3 or Y.shape[1] != S and S != 1:
+            raise ValueError(f"{what}: Y {tuple(Y.shape)} is not (k, N) with S = 1 or (k, S, N)")
+        k, S, N = Y.shape
+        # row j·S + s at pitch ld: the set stride where there are several sets, else the coordinate stride
+        ld = Y.stride(1) if S > 1 else (Y.stride(0) if k > 1 else max(N, 1))
+        if N > 0 and ((N > 1 and Y.stride(2) != 1) or ld < N or (S > 1 and k > 1 and Y.stride(0) != S * ld)):
+            raise ValueError(f"{what}: Y needs unit column stride and evenly pitched rows (row j·S + s at pitch ld)")
+        ld = max(int(ld), N, 1) if N == 0 else int(ld)
+        return Y, k, S, N, ld
+
+    def _set_mask(self, what, mask, S, N):
+        """A bool / uint8 mask (S, ldm ≥ N) — (N,) with S = 1 — on the device with unit column stride →
+        (uint8 view, ldm); (None, N) for no mask."""
+        if mask is None:
+            return None, max(N, 1)
+        if isinstance(mask, torch.Tensor) and mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        if isinstance(mask, torch.Tensor) and mask.dim() == 1 and S == 1:
+            mask = mask[None, :]
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or mask.device != self.device \
+                or mask.dim() != 2 or mask.shape[0] != S or mask.shape[1] < N \
+                or (mask.shape[1] > 1 and mask.stride(1) != 1) or (S > 1 and mask.stride(0) < N):
+            raise ValueError(f"{what}: mask must be a bool or uint8 ({S}, ldm >= {N}) tensor on {self.device} with "
+                             "unit column stride")
+        return mask, int(mask.stride(0)) if S > 1 else max(mask.shape[1], N, 1)
+
+    def _ref_point(self, what, ref, k):
+        r = np.ascontiguousarray(np.asarray(ref.detach().cpu() if isinstance(ref, torch.Tensor) else ref,
+                                            dtype=np.float64).reshape(-1))
+        if r.size != k:
+            raise ValueError(f"{what}: the reference point has {r.size} coordinates for {k} objectives")
+        return r
+
+    def hypervolume(self, Y, ref, S=1, mask=None):
+        """omb_hypervolume: the exact hypervolume (minimisation) that each of S independent point sets dominates
+        below the reference point ``ref`` (k host values) — Y (k, N) with S = 1 or (k, S, N), as ``nondominated``
+        takes it; ``mask`` (S, N) bool / uint8 (``nondominated``'s, say) picks the rows of every set, None takes all
+        → (S,) fp64 on the device.  A row counts when every coordinate is finite and < ref_j; the rows need not be
+        non-dominated or distinct; a set without such a row has hypervolume 0.0.  The result is bitwise the same
+        whatever the pitch, the set's slot, the order of the rows and the number of dropped ones.  ``OMBError`` with
+        code ``OMB_EUNSUP`` for a set with more than ``_lib.HV_POINTS`` counted rows or a call above
+        ``_lib.HV_MAX_WORK`` point tests (``pareto.hypervolume`` has no such bound).  The call synchronises the
+        stream (it reads the grid sizes to size its second launch)."""
+        Y, k, S, N, ld = self._point_sets("hypervolume", Y, S)
+        m, ldm = self._set_mask("hypervolume", mask, S, N)
+        r = self._ref_point("hypervolume", ref, k)
+        hv = torch.empty(S, dtype=torch.float64, device=self.device)
+        self._stream()
+        self._check(self.lib.omb_hypervolume(self._h, k, S, _ptr(Y), ld, N, None if m is None else _ptr(m),
+                                             max(ldm, N), r.ctypes.data_as(_lib._dp), _ptr(hv)), "omb_hypervolume")
+        return hv
+
+    def hypervolume_contributions(self, Y, ref, mask=None):
+        """omb_hypervolume_contrib: one set Y (k, N) (``mask`` (N,) bool / uint8 or None) → (hv (1,) fp64,
+        contributions (N,) fp64) on the device: contributions[i] = HV(set) − HV(set without row i).  Exactly 0.0 for
+        a row that does not count (masked out, a coordinate not finite or ≥ ref_j), for a duplicate and for a row
+        that another counted row dominates; ``hv`` is ``hypervolume``'s value, bit for bit.  The row to drop when
+        an archive is truncated is the counted row with the least contribution.  Refusals and synchronisation as
+        ``hypervolume``; the work is (n + 1) times its."""
+        Y, k, S, N, ld = self._point_sets("hypervolume_contributions", Y, 1)
+        if S != 1:
+            raise ValueError("hypervolume_contributions: one set, Y (k, N)")
+        m, _ = self._set_mask("hypervolume_contributions", mask, 1, N)
+        r = self._ref_point("hypervolume_contributions", ref, k)
+        hv = torch.empty(1, dtype=torch.float64, device=self.device)
+        contrib = torch.empty(max(N, 1), dtype=torch.float64, device=self.device)
+        self._stream()
+        self._check(self.lib.omb_hypervolume_contrib(self._h, k, _ptr(Y), ld, N, None if m is None else _ptr(m),
+                                                     r.ctypes.data_as(_lib._dp), _ptr(hv), _ptr(contrib)),
+                    "omb_hypervolume_contrib")
+        return hv, contrib[:N]
+
     def nondominated(self, Y, S=1, out=None):
         """omb_nondominated: the non-dominated points (minimisation) of S independent point sets — Y (k, N) with
         S = 1 (the layout of ``posterior``'s mean) or (k, S, N) as ``paths_eval`` returns it (rows may be pitched) →
@@ -351,19 +431,7 @@ class AcqContext:
         ordinary values.  On NaN-free input it is ``pareto.nondominated_mask``, bit for bit.  ``out``: a uint8
         (S, ldm ≥ N) tensor with unit column stride to take the mask (columns past N stay untouched).  The call
         synchronises the stream (it reads the sieve's survivor counts to size its later passes)."""
-        if not isinstance(Y, torch.Tensor) or Y.dtype != torch.float64 or Y.device != self.device:
-            raise ValueError(f"nondominated: Y must be an fp64 tensor on {self.device}")
-        S = int(S)
-        if Y.dim() == 2 and S == 1:
-            Y = Y[:, None, :]
-        if Y.dim() != 3 or Y.shape[1] != S and S != 1:
-            raise ValueError(f"nondominated: Y {tuple(Y.shape)} is not (k, N) with S = 1 or (k, S, N)")
-        k, S, N = Y.shape
-        # row j·S + s at pitch ld: the set stride where there are several sets, else the coordinate stride
-        ld = Y.stride(1) if S > 1 else (Y.stride(0) if k > 1 else max(N, 1))
-        if N > 0 and ((N > 1 and Y.stride(2) != 1) or ld < N or (S > 1 and k > 1 and Y.stride(0) != S * ld)):
-            raise ValueError("nondominated: Y needs unit column stride and evenly pitched rows (row j·S + s at pitch ld)")
-        ld = max(int(ld), N, 1) if N == 0 else int(ld)
+        Y, k, S, N, ld = self._point_sets("nondominated", Y, S)
         if out is None:
             out = torch.empty((S, N), dtype=torch.uint8, device=self.device)
         elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != self.device \
